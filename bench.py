@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the MI355X mCCS allreduce path.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds everything else the benchmark measures or checks: the bit-exact
+gate against a+b, the same-buffer rate, the copy calibration, the host-CPU
+baselines and, for N > 1, the extra configs and legs of mccs_amd/ring_bench.py.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 
 N == 1 (BASELINE.json configs[1]): device-resident chunk reduce, two 128 MiB
 fp32 buffers -> elementwise sum kernel (mccs_hip_reduce).  One step = one
@@ -12,8 +18,8 @@ ring allreduce of a 128 MiB fp32 bucket per rank over xGMI P2P FIFOs
 (mccs_hip allreduce, no RCCL).  One step = one allreduce; value = algbw =
 S / t (reference definition, allreduce_bench/src/main.rs:168).
 
-Prints ONE JSON line on rank 0.  cpu_baseline: the oracle's threaded C
-elementwise sum (oracle/mccs_oracle.c, kind "port") timed on this host.
+Prints ONE JSON line on rank 0.  cpu_baseline (--full): the oracle's threaded
+C elementwise sum (oracle/mccs_oracle.c, kind "port") timed on this host.
 """
 from __future__ import annotations
 
@@ -61,7 +67,15 @@ def parse():
     ap.add_argument("--no-extra", action="store_true",
                     help="N>1: skip the extra BASELINE configs[3] line (fp16 1 GiB) reported in config")
     ap.add_argument("--no-hot", action="store_true", help="skip the same-buffer measurement (profiling)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the bit-exact gate, same-buffer rate, "
+                         "copy calibration, CPU baselines, and for N>1 the extra configs and legs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's output as DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if not args.full:  # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_hot = args.no_extra = True
+    return args
 
 
 def cpu_threads() -> int:
@@ -226,6 +240,29 @@ def load_pmc_traffic(tag: str):
         return None
 
 
+DUMP_MAX_ELEMS = 8 << 20  # per array: 32 MiB as float32
+
+
+def dump_outputs(path: str, tensors: dict) -> None:
+    """Writes each device tensor (what a caller of the timed path receives
+    after its last step) as path/<name>.npy in float32, which holds fp32,
+    fp16 and bf16 exactly.  A tensor of more than DUMP_MAX_ELEMS elements is
+    sampled at that many indices drawn once from a fixed seed (sorted, the
+    same for every run of the same shape)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in tensors.items():
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator()
+            g.manual_seed(0x6D636373)
+            idx = torch.randint(0, flat.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            flat = flat.index_select(0, idx.to(flat.device))
+        np.save(os.path.join(path, name + ".npy"), flat.float().cpu().numpy())
+
+
 def bench_reduce(args) -> dict:
     import torch
 
@@ -269,12 +306,13 @@ def bench_reduce(args) -> dict:
         cur[0] += 1
         mccs_amd.reduce(c_, [a_, b_], count=n, dtype=code, stream=stream)
 
-    # correctness gate on the exact timed buffers: fp32/fp16/bf16 a+b is one
-    # correctly rounded add, so the torch result is bit-identical
+    # one untimed pass over every rotated set; --full: correctness gate on the
+    # exact timed buffers (fp32/fp16/bf16 a+b is one correctly rounded add, so
+    # the torch result is bit-identical)
     for _ in range(nsets):
         step()
     torch.cuda.synchronize()
-    for a_, b_, c_ in sets:
+    for a_, b_, c_ in sets if args.full else ():
         ref = (a_.float() + b_.float()).to(tdt) if tdt != torch.float32 else a_ + b_
         if not torch.equal(c_, ref):
             raise SystemExit("bench_reduce: result mismatch vs a+b")
@@ -308,6 +346,8 @@ def bench_reduce(args) -> dict:
     avg_launch_s = total_ms / K / 1e3  # kernel + same-stream launch boundary
     achieved = alg_bytes / avg_launch_s / 1e9
     value = alg_bytes * K / (total_ms / 1e3) / 1e9
+    if args.dump_outputs:  # before the --full legs below reuse the destination buffers
+        dump_outputs(args.dump_outputs, {"reduce_out": sets[(cur[0] - 1) % nsets][2]})
 
     # same-buffer ("hot") rate for reference: inputs may partly stay in the MALL
     hot_gbps = None
@@ -463,7 +503,7 @@ def main():
     if world > 1 or args.gpus > 1:
         from mccs_amd import ring_bench
 
-        out = ring_bench.run(args, cpu_sum_baseline=ring_cpu_baseline)
+        out = ring_bench.run(args, cpu_sum_baseline=ring_cpu_baseline, dump_outputs=dump_outputs)
         if out is None:  # non-zero rank
             return
     else:

@@ -749,10 +749,12 @@ def ring_line(*, world, steps, warmup, per_step_s, nbytes, dt_name, comm_info, r
     return line
 
 
-def run(args, cpu_sum_baseline=None):
+def run(args, cpu_sum_baseline=None, dump_outputs=None):
     """`cpu_sum_baseline(world, nbytes, dtype_code) -> dict`: the host-CPU
     baseline leg, supplied by bench.py (it times the oracle's threaded C sum,
-    which the product package never imports)."""
+    which the product package never imports).  `dump_outputs(dir, {name:
+    tensor})`: bench.py's writer for --dump-outputs (rank 0's receive buffer
+    after the last timed AllReduce)."""
     import torch
     import torch.distributed as dist
 
@@ -774,13 +776,13 @@ def run(args, cpu_sum_baseline=None):
         if getattr(args, "jobs", None) in ("setup2", "setup2-interleaved"):
             return run_setup2(args, torch, dist, C, rank, world, device, dev,
                               interleaved=args.jobs.endswith("interleaved"), cpu_sum_baseline=cpu_sum_baseline)
-        return _run_ring(args, torch, dist, C, rank, world, device, dev, ndev, cpu_sum_baseline)
+        return _run_ring(args, torch, dist, C, rank, world, device, dev, ndev, cpu_sum_baseline, dump_outputs)
     finally:
         if dist.is_initialized():
             dist.destroy_process_group()
 
 
-def _run_ring(args, torch, dist, C, rank, world, device, dev, ndev, cpu_sum_baseline=None):
+def _run_ring(args, torch, dist, C, rank, world, device, dev, ndev, cpu_sum_baseline=None, dump_outputs=None):
     budget = Budget(dist)
     exchange = _exchange_factory(dist, world)
     dt_name = args.dtype
@@ -821,6 +823,8 @@ def _run_ring(args, torch, dist, C, rank, world, device, dev, ndev, cpu_sum_base
     C.ring_profile(device, reset=True)
     per_step = max_over_ranks(dist, time_steps(torch, dist, comm, step_for(comm), args.warmup, K)) / K
     prof = C.ring_profile(device, reset=True)
+    if rank == 0 and dump_outputs is not None and getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, {"allreduce_recv_rank0": y})
     ok = exact_sum_ok(torch, C, comm, rank, world, n, tdt, code, dev)
     if os.environ.get("MCCS_BENCH_INJECT_MISMATCH") == "1":
         ok = False  # fault injection: the bench must exit non-zero

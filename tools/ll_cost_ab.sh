@@ -5,6 +5,8 @@
 # cost, guard on), and the 2-process N = 2 rehearsal, whose direct sweep
 # times the one-slot (deployment-shape) LL launch.
 set -e
+LOGS=${AB_LOGS:-ab_logs}  # one log per variant and repetition
+mkdir -p "$LOGS"
 TR="python -m torch.distributed.run --nnodes=1 --master-addr 127.0.0.1"
 for i in 1 2 3; do
  for v in prev new; do
@@ -14,8 +16,8 @@ import json, sys
 sys.path.insert(0, 'tools')
 import guard_control as g
 out = {n: g.cost(n, 'll', 32 << 10, True)[1:] for n in (2, 4, 8)}
-print(json.dumps(out))" > gpurun_out/llab_vnode_${v}_$i.log 2>&1
-  timeout -k 10 200 $TR --nproc-per-node 2 --master-port 2992$i bench.py --gpus 2 > gpurun_out/llab_n2_${v}_$i.log 2>&1
+print(json.dumps(out))" > "$LOGS/llab_vnode_${v}_$i.log" 2>&1
+  timeout -k 10 200 $TR --nproc-per-node 2 --master-port 2992$i bench.py --gpus 2 --full > "$LOGS/llab_n2_${v}_$i.log" 2>&1
   echo "$v $i done"
  done
 done
