@@ -2,7 +2,10 @@
 //
 // Semantics follow the reference functors (src/collectives/src/reduce_kernel.h):
 //   FuncSum/FuncProd  x+y, x*y in T, integers wrap (:16-30, :72-103 for int8/uint8)
-//   FuncMax/FuncMin   (x<y)?y:x / (x<y)?x:y for integers, float, double (:32-46)
+//   FuncMax/FuncMin   (x<y)?y:x / (x<y)?x:y for integers (:32-46); float and double
+//                     are specialised to fmaxf/fminf / fmax/fmin (:435-463): one
+//                     NaN operand yields the other, +0 > -0 in either order
+//                     (v_max/v_min_f32/f64 order the zeros that way)
 //   half / bfloat16   computed in binary32 and rounded once to nearest even; this
 //                     is bit-identical to __hadd2/__hmul2 (:237-259, :287-309)
 //                     because binary32 has >= 2p+2 bits for p = 11 and p = 8;
@@ -90,11 +93,13 @@ __device__ __forceinline__ typename Elem<DT>::T scalar_op(typename Elem<DT>::T x
   } else if constexpr (DT == mccsBfloat16) {
     float r = f32_op_fmax<OP>(bf16_lo(x), bf16_lo(y));
     return (T)(pack_bf16x2(r, 0.f) & 0xffffu);
-  } else if constexpr (DT == mccsFloat32 || DT == mccsFloat64) {
+  } else if constexpr (DT == mccsFloat32) {
+    return f32_op_fmax<OP>(x, y);
+  } else if constexpr (DT == mccsFloat64) {
     if constexpr (OP == OpSum) return x + y;
     else if constexpr (OP == OpProd) return x * y;
-    else if constexpr (OP == OpMax) return (x < y) ? y : x;
-    else return (x < y) ? x : y;
+    else if constexpr (OP == OpMax) return fmax(x, y);
+    else return fmin(x, y);
   } else {
     return int_op<T, OP>(x, y);
   }

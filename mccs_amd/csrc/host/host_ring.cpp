@@ -83,24 +83,36 @@ T iop(int op, T x, T y) {
   }
 }
 
+// fmaxf/fminf/fmax/fmin as the reference's device computes them
+// (reduce_kernel.h:338-463): one NaN operand yields the other, and +0 > -0 in
+// either operand order (libm's fmax leaves the order of the zeros open).
+template <typename T>
+T fmax_ref(T x, T y) {
+  if (x != x) return y;
+  if (y != y) return x;
+  if (x == y) return std::signbit(x) ? y : x;
+  return x < y ? y : x;
+}
+
+template <typename T>
+T fmin_ref(T x, T y) {
+  if (x != x) return y;
+  if (y != y) return x;
+  if (x == y) return std::signbit(x) ? x : y;
+  return x < y ? x : y;
+}
+
 template <typename T>
 T fop(int op, T x, T y) {
   switch (op) {
     case mccsDevSum: return x + y;
     case mccsDevProd: return x * y;
-    case mccsDevMax: return x < y ? y : x;
-    default: return x < y ? x : y;
+    case mccsDevMax: return fmax_ref(x, y);
+    default: return fmin_ref(x, y);
   }
 }
 
-float hop(int op, float x, float y) {
-  switch (op) {
-    case mccsDevSum: return x + y;
-    case mccsDevProd: return x * y;
-    case mccsDevMax: return std::fmax(x, y);
-    default: return std::fmin(x, y);
-  }
-}
+float hop(int op, float x, float y) { return fop<float>(op, x, y); }
 
 // out[i] = fn(x[i], y[i]); out may alias either input
 void apply(int dt, int op, void* out, const void* x, const void* y, size_t n) {

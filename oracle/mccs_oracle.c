@@ -8,8 +8,10 @@
  *
  * Restated from (paths relative to the reference root):
  *   element ops ........ src/collectives/src/reduce_kernel.h:16-30 (FuncSum/FuncProd),
- *                        :32-46 (generic Max/Min), :237-259 (FuncSum<half> = __hadd2,
- *                        fp16 RNE), :338-404 (Max/Min<half>: fmaxf/fminf), :357-384 (bf16)
+ *                        :32-46 (generic Max/Min: integers), :237-259 (FuncSum<half> =
+ *                        __hadd2, fp16 RNE), :338-404 (Max/Min<half>: fmaxf/fminf),
+ *                        :357-384 (bf16), :435-463 (Max/Min<float>, <double>: fmaxf/fminf,
+ *                        fmax/fmin)
  *   reduce / reduce-copy  src/collectives/src/common_kernel.h:485-685 (ReduceOrCopyMulti:
  *                        vals = src[0]; vals = fn(vals, src[i]); stored to every dst)
  *   ring schedule ...... src/collectives/src/all_reduce.h:10-87 (runRing: chunk size,
@@ -116,14 +118,31 @@ DEF_INT_OPS(ops_u32, uint32_t, uint32_t)
 DEF_INT_OPS(ops_i64, int64_t, uint64_t)
 DEF_INT_OPS(ops_u64, uint64_t, uint64_t)
 
+/* fmaxf/fminf/fmax/fmin as the reference's device computes them: one NaN
+ * operand yields the other (two yield NaN), and +0 > -0 in either operand
+ * order.  Written out because C's fmax leaves the order of the zeros to the
+ * libm.  Binary32 operands pass through double unchanged. */
+static double fmax_ref(double x, double y) {
+  if (x != x) return y;
+  if (y != y) return x;
+  if (x == y) return signbit(x) ? y : x;
+  return x < y ? y : x;
+}
+static double fmin_ref(double x, double y) {
+  if (x != x) return y;
+  if (y != y) return x;
+  if (x == y) return signbit(x) ? x : y;
+  return x < y ? x : y;
+}
+
 #define DEF_FP_OPS(NAME, T)                                                                    \
   static void NAME(int op, T *out, const T *x, const T *y, size_t n) {                         \
     size_t i;                                                                                  \
     switch (op) {                                                                              \
       case OP_SUM: for (i = 0; i < n; ++i) out[i] = x[i] + y[i]; break;                        \
       case OP_PROD: for (i = 0; i < n; ++i) out[i] = x[i] * y[i]; break;                       \
-      case OP_MAX: for (i = 0; i < n; ++i) out[i] = (x[i] < y[i]) ? y[i] : x[i]; break;        \
-      case OP_MIN: for (i = 0; i < n; ++i) out[i] = (x[i] < y[i]) ? x[i] : y[i]; break;        \
+      case OP_MAX: for (i = 0; i < n; ++i) out[i] = (T)fmax_ref(x[i], y[i]); break;            \
+      case OP_MIN: for (i = 0; i < n; ++i) out[i] = (T)fmin_ref(x[i], y[i]); break;            \
     }                                                                                          \
   }
 DEF_FP_OPS(ops_f32, float)
@@ -135,8 +154,8 @@ static float fp_apply(int op, float a, float b) {
   switch (op) {
     case OP_SUM: return a + b;
     case OP_PROD: return a * b;
-    case OP_MAX: return fmaxf(a, b);
-    default: return fminf(a, b);
+    case OP_MAX: return (float)fmax_ref(a, b);
+    default: return (float)fmin_ref(a, b);
   }
 }
 static void ops_f16(int op, uint16_t *out, const uint16_t *x, const uint16_t *y, size_t n) {

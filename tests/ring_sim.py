@@ -58,10 +58,15 @@ def rank_program(rank_index, n, count, nch, bid, nthreads, buff_size, itemsize):
         g += loop
 
 
-def simulate(inputs, op, nch, nthreads, buff_size=1 << 22, ring=None):
+def simulate(inputs, op, nch, nthreads, buff_size=1 << 22, ring=None, fn=None):
     """inputs: list of per-rank 1-D numpy arrays; ring: one send-order list for
     every channel, or a list of per-channel lists (default 0..n-1).
+    fn(op, x, y): the element functor (default: numpy's own ops on the arrays'
+    dtype, op a name); with a hook, op is passed through to it and the arrays
+    may be raw storage bits (they are only sliced, copied and handed to fn).
     Returns the list of per-rank outputs."""
+    if fn is None:
+        fn = _fn
     n = len(inputs)
     count = inputs[0].size
     itemsize = inputs[0].dtype.itemsize
@@ -97,9 +102,9 @@ def simulate(inputs, op, nch, nthreads, buff_size=1 << 22, ring=None):
                     if prim == "send":
                         msg = ins[r][sl].copy()
                     elif prim == "recvReduceSend":
-                        msg = _fn(op, ins[r][sl], recv)
+                        msg = fn(op, ins[r][sl], recv)
                     elif prim == "recvReduceCopySend":
-                        msg = _fn(op, ins[r][sl], recv)
+                        msg = fn(op, ins[r][sl], recv)
                         outs[r][sl] = msg
                     elif prim == "recvCopySend":
                         outs[r][sl] = recv

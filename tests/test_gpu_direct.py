@@ -512,7 +512,7 @@ def test_ll_several_words_per_thread(orc, monkeypatch, inplace):
 @pytest.mark.parametrize("op", [0, 2, 3])
 def test_direct_nan_and_inf(orc, code, op, variant):
     """NaN / +-Inf inputs through each direct kernel: the same per-type
-    operators as the ring (float Max/Min (x < y) ? y : x, half/bf16 fmaxf),
+    operators as the ring (Max/Min of float, half and bf16 are fmaxf / fminf),
     so the NaN positions and every other bit equal the ring's (the oracle)."""
     n, count = 3, 30011
     comms = C.init_all([0] * n, _cfg(variant))

@@ -241,9 +241,9 @@ def test_reduce_beyond_2pow31_elements():
 @pytest.mark.parametrize("nsrcs", [2, 3])
 def test_reduce_nan_and_inf(orc, code, op, nsrcs):
     """NaN / +-Inf (2 % each) in every source: the per-type operators of
-    reduce_kernel.h decide what survives (float / double Max/Min
-    (x < y) ? y : x keep a NaN first operand and drop a NaN second one; half and
-    bf16 go through fmaxf / fminf, which drop either).  NaN positions match
+    reduce_kernel.h decide what survives (Max/Min of all four fp types go
+    through fmaxf / fminf / fmax / fmin, :338-463, which drop a NaN operand on
+    either side and keep NaN only when every operand is one).  NaN positions match
     the oracle's and every other element is bit-exact (payloads not compared)."""
     rng = np.random.default_rng(7 * code + op + 100 * nsrcs)
     n = 50021

@@ -141,10 +141,11 @@ def test_allreduce_prod_half_types(orc, n, code):
 @pytest.mark.parametrize("code", [F32, F16, BF16, F64])
 def test_allreduce_nan_and_inf(orc, code, op):
     """NaN and +-Inf inputs (1 % each) through the ring at n = 3: the
-    reference's per-type operators decide what survives -- float / double
-    Max/Min are (x < y) ? y : x, so a NaN second operand is dropped; half and
-    bf16 Max/Min go through fmaxf / fminf, which drop either NaN
-    (reduce_kernel.h:32-46,338-404) -- and Inf - Inf makes NaN in Sum.  The NaN
+    reference's per-type operators decide what survives -- Max/Min of float,
+    double, half and bf16 all go through fmaxf / fminf / fmax / fmin, which
+    drop a NaN operand on either side (reduce_kernel.h:338-463; the generic
+    (x < y) ? y : x of :32-46 serves integers only) -- and Inf - Inf makes NaN
+    in Sum.  The NaN
     positions must match the oracle's and every other element bit for bit
     (NaN payloads are not compared: the reference's hardware makes its own)."""
     n, count = 3, 65537
