@@ -42,6 +42,9 @@ typedef enum {
  * ReduceOrCopyMulti (src/collectives/src/common_kernel.h:624-685), as a
  * standalone full-chip launch: y = src[0] (op) src[1] (op) ... in the element
  * type, written to every dst.  dst may alias src[0] (in-place a += b).
+ * Tested (tests/test_gpu_footprint.py): any dst may be src[0] itself, also
+ * among several dsts; no other overlap of buffers is supported; nothing
+ * outside [dst, dst + count) is written, whatever the operands' alignment.
  * dtype: mccsDevDataType_t; op: mccsDevSum/Prod/Max/Min.
  * ====================================================================== */
 #define MCCS_REDUCE_MAX_SRCS 8

@@ -370,6 +370,8 @@ static hipError_t launch_lds(const ReduceArgs& a, int pol, int bpc, hipStream_t 
 
 // (U, S, W) run-time -> template.  The default (2, 3, 4) exists for every
 // dtype/op; the tuning grid only for Sum over fp32/fp16/bf16.
+// (tests/test_gpu_footprint.py mirrors this table and dispatch()'s choice of
+// loop and tile in LDS_GRID / kernel_tile: change them together.)
 template <int DT, int OP>
 static hipError_t launch_lds_cfg(const ReduceArgs& a, const ReduceTune& t, bool* ok, hipStream_t st) {
   *ok = true;
