@@ -187,8 +187,16 @@ static mccsResult_t wait_work_queue(Comm* c, uint32_t target) {
     uint32_t all = c->work_next;
     for (int ch = 0; ch < c->nch; ++ch)
       if (ackd[ch] != c->chan_next[ch]) all = rolling_min_u32(all, ackd[ch]);
+    // a quiesced channel moves on with the others, its expected value with it
+    // (NCCL waitWorkFifoAvailable: workFifoSent = ackdAll).  plan.rs:404-410
+    // writes the done word only: from the next wait on, the idle channel looks
+    // busy at that value, the minimum cannot pass it, and the host stops once
+    // it needs an entry one ring depth beyond it.
     for (int ch = 0; ch < c->nch; ++ch)
-      if (ackd[ch] == c->chan_next[ch]) __atomic_store_n(&c->h_done[ch], all, __ATOMIC_RELAXED);
+      if (ackd[ch] == c->chan_next[ch]) {
+        c->chan_next[ch] = all;
+        __atomic_store_n(&c->h_done[ch], all, __ATOMIC_RELAXED);
+      }
     c->work_acked_min = all;
     if (!rolling_less_u32(c->work_acked_min + c->work_depth, target)) return mccsSuccess;
     if ((spins & 0xfffff) == 0xfffff && comm_query_last_launch(c) == hipSuccess) {

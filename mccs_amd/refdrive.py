@@ -34,6 +34,17 @@ gets can be timed and its results checked:
   doneAcks, rolling acks), plan.rs:602-669 (get_task_schema, launch_plan:
   grid = #channels, block = nthreads, e.g. 544).
 
+What it drives: `RefDrivenRank.all_reduce` (one task per plan, one element
+per work, one work per channel: the shape bench.py times),
+`RefDrivenRank.all_gather` (the AllGather kernel, always a plan of its own)
+and `RefDrivenRank.plan` (pre_launch_schedule's batch, plan.rs:111-169:
+consecutive AllReduce tasks of one dtype and op in one launch, channels
+picked by running load so block id b need not sit on channel b, up to 10
+elements per work, a new work at every nWarps change, later works chained
+through workNext relative to the head, block = the largest nthreads).  The
+host-only part of a plan is `build_plan` (`plan_queues` + `WorkRing.place` +
+`layout_works`), unit-tested on CPU.
+
 The launch goes through mccs_hip_launch_coll (the kernel symbol plus
 hipLaunchKernel, the call plan.rs:659-666 makes with cudaLaunchKernel).
 The reference-named kernels run the reference hand-off policy (system-scope
@@ -48,6 +59,7 @@ import time
 from . import _lib as L
 from . import abi
 
+FUNC_ALLGATHER = 2  # mccsFuncAllGather
 FUNC_ALLREDUCE = 4  # mccsFuncAllReduce
 META = 4096  # SendBufMeta / RecvBufMeta, each padded to a page (meta.rs:7-67)
 WORK_DEPTH = 1024  # entries of the host-mapped work ring (power of two; the reference has 65536)
@@ -186,17 +198,29 @@ def reference_rings(n: int, nch: int) -> list[list[int]]:
 class WorkRing:
     """plan.rs's work-FIFO bookkeeping (upload_work's slot reservation,
     wait_work_queue's rolling acknowledgements, plan.rs:380-541), host-only so
-    it is unit-tested on CPU.  One work per selected channel per launch.
+    it is unit-tested on CPU.  A launch over k channels takes k "first" works
+    (channel i's at start + i) followed by the m later works of the channels
+    that have more than one (plan.rs:451-503).
 
-    Acknowledgement value: plan.rs:461-470 gives a channel's single (first
-    and last) work DoneAcks(new_subsequent_start + 1) = first + k + 1, one
-    entry PAST the launch's last entry.  Once that launch is read, the
-    host's acked_min therefore also covers the first entry of the NEXT
-    launch, which may not have been read yet: a host a full ring ahead can
-    overwrite it (tests/test_refdrive_host.py reproduces the overwrite).
-    By default the acknowledgement here is the launch's end, first + k
-    (exact; NCCL's doneAcks is likewise one past the channel's last work);
-    `reference_acks=True` keeps the reference arithmetic."""
+    Acknowledgement value: plan.rs:461-470 gives a channel's last work
+    DoneAcks(new_subsequent_start + 1), new_subsequent_start being the slot
+    the next later work would take.  For a channel with a single (first and
+    last) work that is start + k + (later works of the channels before it)
+    + 1: with no later works at all, start + k + 1, one entry PAST the
+    launch's last entry.  Once that launch is read, the host's acked_min
+    therefore also covers the first entry of the NEXT launch, which may not
+    have been read yet: a host a full ring ahead can overwrite it
+    (tests/test_refdrive_host.py reproduces the overwrite).  For a channel
+    with several works it is the slot after that channel's own last work,
+    which is exact.
+    By default (exact) a channel with several works keeps that value, the slot
+    after its own last work, and a channel with a single work acknowledges the
+    launch's end, start + k + m, as host/plan.cpp does: a channel that loaded
+    its last work has read all of its works below either value, and the
+    launch's entries that other channels have not read yet stay covered by the
+    minimum over busy channels (NCCL's doneAcks is likewise one past the
+    channel's last work).  `reference_acks=True` keeps the reference
+    arithmetic for the single-work channels too."""
 
     def __init__(self, nch: int, depth: int = WORK_DEPTH, reference_acks: bool = False):
         assert depth & (depth - 1) == 0
@@ -205,6 +229,29 @@ class WorkRing:
         self.next_available = 0
         self.chan_next = [0] * nch
         self.acked_min = 0
+
+    @staticmethod
+    def place(next_available: int, k: int, depth: int) -> int:
+        """Where a launch with k first works starts: at next_available, or at
+        the ring start when the FIRST works would cross the ring's end
+        (plan.rs:434-440; the later works are not looked at, so they may
+        cross it)."""
+        mask = depth - 1
+        start = next_available
+        if ((start + k - 1) & mask) < (start & mask):
+            start = (start + mask) & ~mask & 0xFFFFFFFF
+        return start
+
+    @staticmethod
+    def acks_for(start: int, nworks, reference_acks: bool) -> list[int]:
+        """doneAcks of each channel's last work; nworks[i] = number of works
+        of the launch's i-th channel (see the class docstring)."""
+        out, nss, end = [], start + len(nworks), start + sum(nworks)
+        for w in nworks:
+            nss += w - 1  # now one past this channel's last later work, if it has any
+            single = nss + 1 if reference_acks else end
+            out.append((single if w == 1 else nss) & 0xFFFFFFFF)
+        return out
 
     def _wait(self, target: int, read_done, write_done, timeout_s: float) -> None:
         """plan.rs:380-422."""
@@ -219,6 +266,13 @@ class WorkRing:
                     ackd_all = _rolling_min(ackd_all, ackd[c])
             for c in range(self.nch):
                 if ackd[c] == self.chan_next[c]:
+                    # a quiesced channel moves on with the others; its expected
+                    # value moves with it (NCCL enqueue.cc waitWorkFifoAvailable:
+                    # workFifoSent = ackdAll).  plan.rs:404-410 writes the done
+                    # word only: from the next wait on, the idle channel looks
+                    # busy at that value, the minimum cannot pass it, and the
+                    # host stops once it needs an entry one ring depth beyond it
+                    self.chan_next[c] = ackd_all
                     write_done(c, ackd_all)
             self.acked_min = ackd_all
             if not _rolling_less((self.acked_min + self.depth) & 0xFFFFFFFF, target & 0xFFFFFFFF):
@@ -227,23 +281,138 @@ class WorkRing:
                 raise RuntimeError("reference-driven work ring: no acknowledgement (kernel stuck?)")
             time.sleep(0)
 
-    def reserve(self, chans, read_done, write_done, timeout_s: float = 60.0):
-        """Slots for one launch over `chans` (ascending channel ids): returns
-        (first slot counter, doneAcks).  Wraps to the ring start rather than
-        splitting a launch's works, and waits until the slots are acknowledged
-        (upload_work, plan.rs:424-443)."""
-        k = len(chans)
-        mask = self.depth - 1
-        start = self.next_available
-        if ((start + k - 1) & mask) < (start & mask):
-            start = (start + mask) & ~mask & 0xFFFFFFFF
-            self.next_available = start
-        self._wait(start + k, read_done, write_done, timeout_s)
-        acks = (start + k + (1 if self.reference_acks else 0)) & 0xFFFFFFFF
-        for c in chans:
-            self.chan_next[c] = acks
-        self.next_available = (start + k) & 0xFFFFFFFF
+    def reserve_works(self, chans, nworks, read_done, write_done, timeout_s: float = 60.0):
+        """Slots for one launch over `chans` (ascending channel ids) whose
+        i-th channel has nworks[i] >= 1 works: k = len(chans) first works and
+        m = sum(nworks) - k later ones.  Returns (first slot counter, doneAcks
+        per channel).  The wrap test looks at k only, as the reference's does;
+        the wait covers start + k + m (upload_work, plan.rs:424-443)."""
+        k, total = len(chans), sum(nworks)
+        assert len(nworks) == k and all(w >= 1 for w in nworks) and total <= self.depth
+        start = self.place(self.next_available, k, self.depth)
+        self.next_available = start
+        self._wait(start + total, read_done, write_done, timeout_s)
+        acks = self.acks_for(start, nworks, self.reference_acks)
+        for c, a in zip(chans, acks):
+            self.chan_next[c] = a
+        self.next_available = (start + total) & 0xFFFFFFFF
         return start, acks
+
+    def reserve(self, chans, read_done, write_done, timeout_s: float = 60.0):
+        """One work per channel: returns (first slot counter, doneAcks).  Wraps
+        to the ring start rather than splitting a launch's works, and waits
+        until the slots are acknowledged (upload_work, plan.rs:424-443)."""
+        start, acks = self.reserve_works(chans, [1] * len(chans), read_done, write_done, timeout_s)
+        return start, acks[0]
+
+
+class Plan:
+    """What build_plan returns: `works` = [(slot counter, mccsDevWork)] in
+    upload order (slot = counter & (depth - 1)); `start` the head's counter,
+    `end` the ring's next_available after it; `chans` the channels that got
+    work (ascending, block b of the grid runs chans[b]), `nworks` their work
+    counts, `acks` their doneAcks; `mask`, `grid`, `block` the launch;
+    `tasks` = per task (k, nthreads of that task, channel ids in selection =
+    block-id order)."""
+
+    def __init__(self):
+        self.works, self.tasks, self.chans, self.nworks, self.acks = [], [], [], [], []
+        self.start = self.end = self.mask = self.grid = self.block = 0
+
+
+def plan_queues(tasks, nch: int, func: int = FUNC_ALLREDUCE, nranks: int = 1, schema=None):
+    """pre_launch_schedule's merge of one plan's tasks (plan.rs:111-302):
+    tasks = [(send_ptr, recv_ptr, count, dtype)].  Per task get_task_schema
+    on its own bytes (count * n for an AllGather, task.rs:95-102),
+    select_best_channels on this plan's running coll_bytes (ties by id), bid =
+    position in the selection, and enqueue_work_elem_coll: an element joins
+    the channel's last work while nWarps is the same and the work has fewer
+    than MCCS_MAX_WORK_ELEMENTS.  Returns (queues, per_task, block): queues[c]
+    = list of works, each a list of (task index, nWarps, bid, nChannels)."""
+    if schema is None:
+        lib = L.load()
+
+        def schema(total, channels):
+            a, b = ctypes.c_int(), ctypes.c_int()
+            lib.mccs_task_schema(total, channels, ctypes.byref(a), ctypes.byref(b))
+            return a.value, b.value
+    load = [0] * nch
+    queues = [[] for _ in range(nch)]
+    per_task, block = [], 0
+    for t, (_, _, count, dtype) in enumerate(tasks):
+        nbytes = count * ESIZE[dtype]
+        k, nthr = schema(nbytes * nranks if func == FUNC_ALLGATHER else nbytes, nch)
+        sel = sorted(range(nch), key=lambda i: (load[i], i))[:k]
+        for bid, c in enumerate(sel):
+            load[c] += nbytes
+            q = queues[c]
+            if q and q[-1][0][1] == nthr // 32 and len(q[-1]) < abi.MCCS_MAX_WORK_ELEMENTS:
+                q[-1].append((t, nthr // 32, bid, k))
+            else:
+                q.append([(t, nthr // 32, bid, k)])
+        per_task.append((k, nthr, sel))
+        block = max(block, nthr)
+    return queues, per_task, block
+
+
+def layout_works(tasks, queues, start: int, depth: int = WORK_DEPTH, reference_acks: bool = False):
+    """upload_work (plan.rs:424-541) for a launch whose head is at counter
+    `start`: channel i's first work at start + i, the later works behind all
+    first works, each non-last work's workNext = its successor's slot minus
+    the head's slot (negative when the later works cross the ring's end),
+    isLast + inFifo + doneAcks on each channel's last work (the reference
+    leaves inFifo clear on the others).  Returns (works, chans, nworks, acks)."""
+    mask_q = depth - 1
+    chans = [c for c in range(len(queues)) if queues[c]]
+    nworks = [len(queues[c]) for c in chans]
+    acks = WorkRing.acks_for(start, nworks, reference_acks)
+    works, nss = [], start + len(chans)
+    for nth, c in enumerate(chans):
+        q = queues[c]
+        for wid, elems in enumerate(q):
+            w = abi.mccsDevWork()
+            w.header.type = 1  # mccsDevWorkTypeColl
+            if wid == len(q) - 1:
+                w.header.isLast, w.header.inFifo = 1, 1
+                w.header.doneAcks = acks[nth]
+            else:
+                nxt = nss if wid == 0 else nss + 1
+                w.header.workNext = (nxt & mask_q) - (start & mask_q)
+            for i, (t, nwarps, bid, k) in enumerate(elems):
+                e = w.elems[i]
+                e.isUsed, e.nWarps = 1, nwarps
+                e.sendbuff, e.recvbuff, e.count = tasks[t][0], tasks[t][1], tasks[t][2]
+                e.bid, e.nChannels = bid, k
+            if wid == 0:
+                at = start + nth
+            else:
+                at, nss = nss, nss + 1
+            works.append((at & 0xFFFFFFFF, w))
+    return works, chans, nworks, acks
+
+
+def build_plan(tasks, nch: int, next_available: int, depth: int = WORK_DEPTH, reference_acks: bool = False,
+               func: int = FUNC_ALLREDUCE, nranks: int = 1, schema=None, reserve=None) -> Plan:
+    """The host-only part of one plan, no GPU and no waiting: the tasks
+    ([(send_ptr, recv_ptr, count, dtype)], one dtype and op), the channel
+    count and the ring's next_available in; the work structs and their slots
+    out (see Plan).  `reserve(chans, nworks) -> (start, acks)` replaces the
+    plain placement where a live ring has to wait for the slots
+    (WorkRing.reserve_works; RefDrivenRank passes it)."""
+    p = Plan()
+    queues, p.tasks, p.block = plan_queues(tasks, nch, func, nranks, schema)
+    chans = [c for c in range(nch) if queues[c]]
+    if reserve is None:
+        p.start = WorkRing.place(next_available, len(chans), depth)
+    else:
+        p.start, acks = reserve(chans, [len(queues[c]) for c in chans])
+    p.works, p.chans, p.nworks, p.acks = layout_works(tasks, queues, p.start, depth, reference_acks)
+    assert p.chans == chans and (reserve is None or p.acks == acks)
+    p.end = (p.start + len(p.works)) & 0xFFFFFFFF
+    p.grid = len(chans)
+    for c in p.chans:
+        p.mask |= 1 << c
+    return p
 
 
 class RefDrivenRank:
@@ -252,19 +421,20 @@ class RefDrivenRank:
     `allgather(obj) -> list` exchanges picklable objects between the ranks
     (torch.distributed.all_gather_object over gloo in the bench).  `rings`:
     one send order per channel (comm_patterns_override, config.rs:32-47);
-    default the reference ring on every channel."""
+    default the reference ring on every channel.  `work_depth`: entries of
+    the work ring (a power of two)."""
 
     def __init__(self, rank: int, n: int, device: int, allgather, nch: int = 2, rings=None,
                  buff_size: int = 1 << 22, locality: str = "sender", fifo: str = "device",
-                 watchdog_ms: int | None = None):
+                 watchdog_ms: int | None = None, work_depth: int = WORK_DEPTH):
         if not 2 <= n or not 1 <= nch <= abi.MCCS_MAX_NCHANNELS or locality not in ("sender", "receiver") \
-                or fifo not in ("device", "host"):
+                or fifo not in ("device", "host") or work_depth < 2 * nch or work_depth & (work_depth - 1):
             raise ValueError("bad reference-driven configuration")
         self.rank, self.n, self.device, self.nch, self.buff = rank, n, device, nch, buff_size
         self.rings = [list(r) for r in (rings or reference_rings(n, nch))]
         if len(self.rings) != nch or any(sorted(r) != list(range(n)) for r in self.rings):
             raise ValueError("each channel needs a ring over every rank")
-        self.locality, self.fifo = locality, fifo
+        self.locality, self.fifo, self.work_depth = locality, fifo, work_depth
         self.lib = L.load()
         h = hip()
         _ok(h.hipSetDevice(device), "hipSetDevice")
@@ -361,7 +531,7 @@ class RefDrivenRank:
     def _build_device_structs(self) -> None:
         h, rank, n, nch, buff_size, locality = hip(), self.rank, self.n, self.nch, self.buff, self.locality
         # -- host-mapped sync: work ring + workFifoDone (device.rs:56-64)
-        self.h_work, self.d_work = self._host_mapped(abi.MCCS_WORK_SIZE * WORK_DEPTH)
+        self.h_work, self.d_work = self._host_mapped(abi.MCCS_WORK_SIZE * self.work_depth)
         self.h_done, self.d_done = self._host_mapped(4 * abi.MCCS_MAX_NCHANNELS)
         ctypes.memset(self.h_done, 0, 4 * abi.MCCS_MAX_NCHANNELS)
         self.d_abort = self._dev_alloc(64)
@@ -395,7 +565,7 @@ class RefDrivenRank:
             ch.workFifoDone = self.d_done + 4 * c
         self.d_comm = self._upload(bytes(hc))
         # -- planner state (plan.rs)
-        self.ring = WorkRing(nch)
+        self.ring = WorkRing(nch, self.work_depth)
         self.launches = 0
         self._works = {}
 
@@ -450,7 +620,7 @@ class RefDrivenRank:
         # set bits of channelMask in ascending order
         load = [0] * self.nch
         chans = sorted(sorted(range(self.nch), key=lambda i: (load[i], i))[:k])
-        mask_q = WORK_DEPTH - 1
+        mask_q = self.work_depth - 1
         start, acks = self.ring.reserve(chans, self._read_done, self._write_done)
         key = (send_ptr, recv_ptr, count, k, nthr)
         works = self._works.get(key)
@@ -481,6 +651,57 @@ class RefDrivenRank:
         L.check(rc, "mccs_hip_launch_coll")
         self.launches += 1
         self.last_plan = (k, nthr, [self.rings[c] for c in chans])
+
+    def _launch_plan(self, tasks, func: int, dtype: int, op: int, stream: int) -> Plan:
+        """finalize_one_plan + launch_plan for `tasks`: the channel queues,
+        the ring reservation (wrap on the first works, flow control on all of
+        them), upload_work's layout, one launch with grid = #channels that got
+        work and block = the largest nthreads of the merged tasks."""
+        ring = self.ring
+        p = build_plan(tasks, self.nch, ring.next_available, ring.depth, ring.reference_acks, func, self.n,
+                       reserve=lambda chans, nworks: ring.reserve_works(chans, nworks, self._read_done,
+                                                                        self._write_done))
+        assert p.end == ring.next_available
+        mask_q = ring.depth - 1
+        for at, w in p.works:
+            ctypes.memmove(self.h_work + (at & mask_q) * abi.MCCS_WORK_SIZE, ctypes.addressof(w), abi.MCCS_WORK_SIZE)
+        rc = self.lib.mccs_hip_launch_coll(func, dtype, op, self.d_comm, p.mask,
+                                           self.d_work + (p.start & mask_q) * abi.MCCS_WORK_SIZE, p.grid, p.block,
+                                           stream)
+        L.check(rc, "mccs_hip_launch_coll")
+        self.launches += 1
+        self.last_launch = (func, dtype, op, p.mask, p.grid, p.block)
+        return p
+
+    def plan(self, tasks, stream: int) -> Plan | None:
+        """One batched plan, as pre_launch_schedule merges consecutive
+        AllReduce tasks of one dtype and op (plan.rs:111-169): tasks =
+        [(send_ptr, recv_ptr, count, dtype, op)], zero counts dropped.
+        Returns the Plan; `last_tasks` holds per task (k, nthreads of that
+        task, [rings[c] for c in its selection order]), from which the caller
+        computes the expected values."""
+        tasks = [t for t in tasks if t[2] > 0]
+        if not tasks:
+            return None
+        dtype, op = tasks[0][3], tasks[0][4]
+        if any(t[3] != dtype or t[4] != op for t in tasks):
+            raise ValueError("one plan merges tasks of one dtype and op only")
+        p = self._launch_plan([t[:4] for t in tasks], FUNC_ALLREDUCE, dtype, op, stream)
+        self.last_tasks = [(k, nthr, [self.rings[c] for c in sel]) for k, nthr, sel in p.tasks]
+        self.last_plan = self.last_tasks[-1]
+        return p
+
+    def all_gather(self, send_ptr: int, recv_ptr: int, nbytes: int, stream: int) -> Plan | None:
+        """One AllGather task through plan.rs's path: a plan of its own (the
+        reference never batches AllGathers: reduce_op is None, plan.rs:122-131),
+        schema from nbytes * n (task.rs:95-102), element count = nbytes, the
+        one AllGather kernel (int8, op 0).  nbytes = 0 launches nothing."""
+        if nbytes == 0:
+            return None
+        p = self._launch_plan([(send_ptr, recv_ptr, nbytes, 0)], FUNC_ALLGATHER, 0, 0, stream)
+        k, nthr, sel = p.tasks[0]
+        self.last_plan = (k, nthr, [self.rings[c] for c in sel])
+        return p
 
     def aborted(self) -> bool:
         v = ctypes.c_int32()

@@ -20,6 +20,9 @@ launches, prims_simple.h:318-319,461) and then 1100 back-to-back launches,
 so the 1024-entry work ring wraps and flow-controls on workFifoDone
 (plan.rs:380-541).  Results are compared bit for bit with the oracle,
 workFifoDone with doneAcks, and conn->step across ranks.
+
+REFDRV_MODE selects one of the further modes instead (class Modes below):
+allgather, batched, small, odd, edge.  Unset: the run described above.
 """
 import json
 import os
@@ -52,6 +55,8 @@ def main():
 
     if os.environ.get("REFDRV_BIG") == "1":
         return big_case(torch, dist, refdrive, orc, rank, n, dev, allgather)
+    if os.environ.get("REFDRV_MODE"):
+        return Modes(torch, dist, refdrive, orc, rank, n, dev, allgather).run(os.environ["REFDRV_MODE"])
     rot = list(range(1, n)) + [0]
     variants = [("ref_sender", 2, None, "sender", "device"),
                 ("rotated_receiver", 2, [rot, rot[::-1]], "receiver", "device"),
@@ -128,6 +133,408 @@ def main():
                           "final_steps": allres[0][k]["steps"]}), flush=True)
     dist.barrier()
     dist.destroy_process_group()
+
+
+# comm_patterns_override: tests/test_gpu_ring.py's two channels whose orders do
+# not start at rank 0 and are no rotations of each other, cut down to the world
+OVERRIDE8 = [[3, 0, 6, 1, 7, 2, 5, 4], [4, 5, 2, 7, 1, 6, 0, 3]]
+F16, F32, I32, I8 = 6, 7, 2, 0
+NTHR_OF_BUCKET = {5000: 96, 10000: 160, 20000: 288, 40000: 544}  # get_task_schema, plan.rs:602-635
+
+
+class Modes:
+    """REFDRV_MODE = allgather | batched | small | odd | edge: what plan.rs's
+    host side does beyond one aligned AllReduce per plan (see each method).
+    Every mode runs on the reference ring with the FIFO at the sender and on a
+    two-channel ring override with the FIFO at the receiver.  After every
+    stream.synchronize() the abort flag is read (set: exit 3, nothing more is
+    issued) and workFifoDone is compared with the host's expectation on every
+    channel; conn->step is compared across ranks at the end.  Nothing is
+    retried."""
+
+    def __init__(self, torch, dist, refdrive, orc, rank, n, dev, allgather):
+        self.torch, self.dist, self.refdrive, self.orc = torch, dist, refdrive, orc
+        self.rank, self.n, self.dev, self.allgather = rank, n, dev, allgather
+        self.stream = torch.cuda.Stream()
+        self.results, self.reached, self.calls = {}, {}, []
+
+    # -- scaffolding ----------------------------------------------------------------
+    def variants(self, host=False):
+        ov = [[r for r in ring if r < self.n] for ring in OVERRIDE8]
+        vs = [("ref_sender", None, "sender", "device"), ("override_receiver", ov, "receiver", "device")]
+        if host:
+            vs += [(name + "_hostfifo", rings, loc, "host") for name, rings, loc, _ in vs]
+        return vs
+
+    def open(self, variant, **kw):
+        _, rings, loc, fifo = variant
+        rr = self.refdrive.RefDrivenRank(self.rank, self.n, self.dev, self.allgather, nch=2, rings=rings,
+                                         locality=loc, fifo=fifo, **kw)
+        if not getattr(rr.lib.mccs_hip_launch_coll, "spied", False):  # record every launch by symbol
+            real, calls = rr.lib.mccs_hip_launch_coll, self.calls
+
+            def spy(func, dtype, op, comm, mask, work, grid, block, stream):
+                calls.append((func, dtype, op, grid, block))
+                return real(func, dtype, op, comm, mask, work, grid, block, stream)
+
+            spy.spied = True
+            rr.lib.mccs_hip_launch_coll = spy
+        return rr
+
+    def barrier(self):
+        self.torch.cuda.synchronize()
+        self.dist.barrier()
+
+    def dev_bytes(self, x):
+        return self.torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).copy()).cuda()
+
+    def fill(self, nbytes):
+        return self.torch.full((nbytes,), 0xA5, dtype=self.torch.uint8, device="cuda")
+
+    def finish(self, rr, key, check):
+        """Synchronize, stop on an abort, then run check() -> '' or what is wrong."""
+        self.stream.synchronize()
+        if rr.aborted():
+            print(f"rank {self.rank}: abortFlag is set after {key}; stopping", flush=True)
+            sys.exit(3)
+        why = check() or ""
+        done = rr.done_acks()
+        if any(done[c] != rr.ring.chan_next[c] for c in range(rr.nch)):
+            why += f" workFifoDone {done} != expected {rr.ring.chan_next}"
+        self.results[key] = {"ok": not why, "why": why[:400], "steps": rr.steps()}
+
+    def reach(self, key, ok):
+        self.reached[key] = bool(ok)
+
+    def run(self, mode):
+        getattr(self, "mode_" + mode)()
+        for k, ok in self.reached.items():
+            self.results["reached/" + k] = {"ok": ok, "why": "" if ok else "not reached", "steps": []}
+        allres = self.allgather(self.results)
+        if self.rank == 0:
+            merged, why = {}, {}
+            for k in self.results:
+                steps = [r[k]["steps"] for r in allres]
+                merged[k] = all(r[k]["ok"] for r in allres) and all(s == steps[0] for s in steps)
+                if not merged[k]:
+                    why[k] = [r[k]["why"] for r in allres] + [str(steps)]
+            print(json.dumps({"world": self.n, "mode": mode, "cases": merged, "all_ok": all(merged.values()),
+                              "why": dict(list(why.items())[:6]), "reached": self.reached,
+                              "launches": len(self.calls)}), flush=True)
+        self.dist.barrier()
+        self.dist.destroy_process_group()
+
+    def oracle(self, code, op, xs, plan, rr):
+        k, nthr, rings = plan
+        return self.orc.ring_allreduce(code, op, xs, nchannels=k, nthreads=nthr, buff_size=rr.buff, ring_orders=rings)
+
+    @staticmethod
+    def same(got, exp):
+        return "" if np.array_equal(np.ascontiguousarray(got).view(np.uint8),
+                                    np.ascontiguousarray(exp).view(np.uint8)) else "result differs "
+
+    # -- allgather --------------------------------------------------------------------
+    def mode_allgather(self):
+        """mccsKernel_AllGather_RING_SIMPLE_Sum_int8_t (all_gather.h:7-79): sizes
+        from one byte to several loops, out of place and in place (send = recv +
+        rank * nbytes: directSend), against the concatenation by rank index."""
+        import vnode
+        from mccs_amd import comm as C
+
+        n, rank, rd = self.n, self.rank, self.refdrive
+        inplace_seen = two_channels = 0
+        for v in self.variants(host=True):
+            rr, host = self.open(v), v[3] == "host"
+            for nbytes in (1000, 65539) if host else (1, 13, 1000, 4096, 65539, 1 << 20, (5 << 20) + 3):
+                xs = [np.random.default_rng([nbytes, r]).integers(0, 256, nbytes, dtype=np.uint8) for r in range(n)]
+                exp = np.concatenate(xs)
+                for inplace in (False, True):
+                    # every byte of the output differs from the expectation before the call
+                    recv = self.dev_bytes(~exp)
+                    send = None
+                    if inplace:
+                        recv[rank * nbytes:(rank + 1) * nbytes].copy_(self.torch.from_numpy(xs[rank]))
+                    else:
+                        send = self.dev_bytes(xs[rank])
+                    send_ptr = recv.data_ptr() + rank * nbytes if inplace else send.data_ptr()
+                    self.barrier()
+                    p = rr.all_gather(send_ptr, recv.data_ptr(), nbytes, self.stream.cuda_stream)
+
+                    def check():
+                        why = self.same(recv.cpu().numpy(), exp)
+                        if send is not None and not np.array_equal(send.cpu().numpy(), xs[rank]):
+                            why += "source modified "
+                        k, nthr = C.task_schema(nbytes * n, 2)
+                        if p.tasks != [(k, nthr, list(range(k)))] or self.calls[-1] != (rd.FUNC_ALLGATHER, 0, 0, k, nthr):
+                            why += f"plan {p.tasks} launch {self.calls[-1]} "
+                        return why
+
+                    self.finish(rr, f"{v[0]}/ag/{nbytes}/{'in' if inplace else 'out'}", check)
+                    inplace_seen += inplace
+                    two_channels += p.grid == 2
+            if host:
+                rr.close(self.dist.barrier)
+                continue
+            # the reference's own check (allgather_proto): int32 2042 + r, 1 MiB per rank
+            cnt = (1 << 20) // 4
+            send, recv = self.dev_bytes(np.full(cnt, 2042 + rank, np.int32)), self.fill(n << 20)
+            self.barrier()
+            rr.all_gather(send.data_ptr(), recv.data_ptr(), 1 << 20, self.stream.cuda_stream)
+            self.finish(rr, f"{v[0]}/ag/int32_fill", lambda: self.same(
+                recv.cpu().numpy().view(np.int32), np.repeat(np.arange(2042, 2042 + n, dtype=np.int32), cnt)))
+            # AllGathers and AllReduces alternating on the same structures: steps persist
+            for rnd in range(3):
+                nbytes, count = 65539, 70001
+                gs = [np.random.default_rng([rnd, nbytes, r]).integers(0, 256, nbytes, dtype=np.uint8)
+                      for r in range(n)]
+                send, recv = self.dev_bytes(gs[rank]), self.fill(n * nbytes)
+                self.barrier()
+                rr.all_gather(send.data_ptr(), recv.data_ptr(), nbytes, self.stream.cuda_stream)
+                self.finish(rr, f"{v[0]}/alternate{rnd}/ag", lambda: self.same(recv.cpu().numpy(), np.concatenate(gs)))
+                xs = [vnode.gen(F32, count, np.random.default_rng([rnd, count, r])) * np.float32(0.7) for r in range(n)]
+                send, recv = self.dev_bytes(xs[rank]), self.fill(4 * count)
+                self.barrier()
+                rr.all_reduce(send.data_ptr(), recv.data_ptr(), count, F32, 0, self.stream.cuda_stream)
+                self.finish(rr, f"{v[0]}/alternate{rnd}/ar",
+                            lambda: self.same(recv.cpu().numpy(), self.oracle(F32, 0, xs, rr.last_plan, rr)))
+            rr.close(self.dist.barrier)
+        # per device variant 7 sizes twice, the fill and 3 alternating; per host variant 2 sizes twice
+        launched = sum(1 for c in self.calls if c[:3] == (rd.FUNC_ALLGATHER, 0, 0))
+        self.reach("allgather_symbol_launched", launched == 2 * (14 + 1 + 3) + 2 * 4 and inplace_seen and two_channels)
+
+    # -- batched ----------------------------------------------------------------------
+    def mode_batched(self):
+        """pre_launch_schedule's batch (plan.rs:111-169) through RefDrivenRank.plan:
+        several AllReduce tasks in one launch, channels by running load, chained
+        works, block = the largest nthreads."""
+        import vnode
+
+        n, rank = self.n, self.rank
+        st = self.stream.cuda_stream
+        for v in self.variants():
+            rr = self.open(v, work_depth=64)  # step (c) walks to the ring's end with single launches
+            override = v[1] is not None
+            # (a) 12 fp32 Sum tasks of mixed sizes, 1000 + 7919 i, the two
+            # one-channel tasks larger first: channel 0 then carries more
+            # bytes than channel 1 and every two-channel task is selected
+            # [1, 0] (in ascending order of i all of them get [0, 1])
+            counts = [1000 + 7919 * i for i in (1, 0) + tuple(range(2, 12))]
+            # vnode.gen's fp32 values are multiples of 2^-23 in [-1, 1): no sum
+            # of two of them rounds, so every three-term sum is one rounding of
+            # the exact value whatever the order.  Scaled by 0.7 the values
+            # fill the mantissa and the summation order shows.
+            xs = [[vnode.gen(F32, c, np.random.default_rng([c, r])) * np.float32(0.7) for r in range(n)]
+                  for c in counts]
+            send, recv = [self.dev_bytes(x[rank]) for x in xs], [self.fill(4 * c) for c in counts]
+            self.barrier()
+            p = rr.plan([(send[t].data_ptr(), recv[t].data_ptr(), counts[t], F32, 0) for t in range(12)], st)
+            order_matters = []
+
+            def check_fp():
+                why = ""
+                for t in range(12):
+                    exp = self.oracle(F32, 0, xs[t], rr.last_tasks[t], rr)
+                    if self.same(recv[t].cpu().numpy(), exp):
+                        why += f"task {t} differs "
+                    k, nthr, sel = p.tasks[t]
+                    asc = self.oracle(F32, 0, xs[t], (k, nthr, [rr.rings[c] for c in sorted(sel)]), rr)
+                    order_matters.append(not np.array_equal(asc, exp))
+                if override and not any(order_matters):
+                    why += "vacuous: ascending channel order gives the same values "
+                return why
+
+            self.finish(rr, f"{v[0]}/fp32x12", check_fp)
+            nthrs = {nthr for _, nthr, _ in p.tasks}
+            self.reach(f"{v[0]}/chained_work_mixed_block",
+                       max(p.nworks) > 1 and {96, 544} <= nthrs and p.block == 544 and self.calls[-1][3:] == (2, 544))
+            self.reach(f"{v[0]}/selection_not_identity", any(k == 2 and sel == [1, 0] for k, _, sel in p.tasks))
+            if override:
+                self.reach("override_order_decides_values", any(order_matters))
+            # (b) 21 int32 tasks, two channels each: three works per channel
+            counts = [16384 + 3 * t for t in range(21)]
+            send = [self.dev_bytes(np.full(c, 2042 + rank + t, np.int32)) for t, c in enumerate(counts)]
+
+            def int_plan(key):
+                recv = [self.fill(4 * c) for c in counts]
+                p = rr.plan([(send[t].data_ptr(), recv[t].data_ptr(), counts[t], I32, 0) for t in range(21)], st)
+
+                def check():
+                    bad = [t for t in range(21) if not np.all(
+                        recv[t].cpu().numpy().view(np.int32) == n * (2042 + t) + n * (n - 1) // 2)]
+                    return f"tasks {bad} differ " if bad else ""
+
+                self.finish(rr, key, check)
+                return p
+
+            self.barrier()
+            p = int_plan(f"{v[0]}/int32x21")
+            self.reach(f"{v[0]}/ten_elements_per_work", p.nworks == [3, 3] and all(k == 2 for k, _, _ in p.tasks))
+            # (c) single 4 KiB launches until the next plan's two first works are
+            # the last but two entries of the ring: its four later works cross
+            # the ring's end
+            depth = rr.ring.depth
+            x = self.dev_bytes(np.full(1024, 2042 + rank, np.int32))
+            out = self.fill(4096)
+            self.barrier()
+            singles = 0
+            while rr.ring.next_available % depth != depth - 4 and singles < 2 * depth:
+                rr.all_reduce(x.data_ptr(), out.data_ptr(), 1024, I32, 0, st)
+                singles += 1
+            self.finish(rr, f"{v[0]}/singles", lambda: "" if np.all(
+                out.cpu().numpy().view(np.int32) == 2042 * n + n * (n - 1) // 2) else "result differs")
+            self.barrier()
+            p = int_plan(f"{v[0]}/int32x21_across_ring_end")
+            nexts = [w.header.workNext for _, w in p.works if not w.header.isLast]
+            self.reach(f"{v[0]}/negative_workNext", p.start % depth == depth - 4 and min(nexts) < 0 < max(nexts))
+            rr.close(self.dist.barrier)
+
+    # -- small ------------------------------------------------------------------------
+    def mode_small(self):
+        """Buckets below nChannels * nranks elements (empty chunks) and the 96-,
+        160-, 288- and 544-thread blocks of get_task_schema, in and out of place."""
+        import vnode
+
+        n, rank = self.n, self.rank
+        planned = set()
+        for v in self.variants():
+            rr = self.open(v)
+            for code in (F16, I32):
+                es = vnode.ESIZE[code]
+                for count in (1, n - 1, 7, 255) + tuple(b // es for b in NTHR_OF_BUCKET):
+                    xs = [vnode.gen(code, count, np.random.default_rng([code, count, r])) for r in range(n)]
+                    for inplace in (False, True):
+                        send = self.dev_bytes(xs[rank])
+                        recv = send if inplace else self.fill(count * es)
+                        self.barrier()
+                        rr.all_reduce(send.data_ptr(), recv.data_ptr(), count, code, 0, self.stream.cuda_stream)
+
+                        def check():
+                            k, nthr, _ = rr.last_plan
+                            why = self.same(recv.cpu().numpy(), self.oracle(code, 0, xs, rr.last_plan, rr))
+                            if k != 1 or nthr != NTHR_OF_BUCKET.get(count * es, 96) or self.calls[-1][3:] != (1, nthr):
+                                why += f"plan {rr.last_plan} launch {self.calls[-1]} "
+                            if not inplace and not np.array_equal(send.cpu().numpy(), xs[rank].view(np.uint8)):
+                                why += "source modified "
+                            return why
+
+                        self.finish(rr, f"{v[0]}/dtype{code}/n{count}/{'in' if inplace else 'out'}", check)
+                        planned.add(self.calls[-1][4])
+            rr.close(self.dist.barrier)
+        self.reach("nthr_96_160_288_544", planned == {96, 160, 288, 544})
+
+    # -- odd --------------------------------------------------------------------------
+    def mode_odd(self):
+        """Misaligned user buffers (the typed fallback) between guard bands: the
+        oracle bit for bit, the pads intact, the sources unchanged."""
+        import footprint as F
+        import vnode
+        from footprint import Guarded
+        from mccs_amd import comm as C
+        from test_gpu_footprint import extra_element
+
+        n, rank = self.n, self.rank
+        st = self.stream.cuda_stream
+
+        def plan_of(rr, nbytes):  # one task per plan: channels 0..k-1
+            k, nthr = C.task_schema(nbytes, 2)
+            return k, nthr, [rr.rings[c] for c in range(k)]
+
+        for v in self.variants():
+            rr = self.open(v)
+            for code in (F16, F32, I8):
+                es = vnode.ESIZE[code]
+                offs = [0, es, 8, 16 - es]
+                for count in (n * (16 // es) + 1, 4097):
+                    xs = [vnode.gen(code, count, np.random.default_rng([code, count, r])) for r in range(n)]
+                    plan = plan_of(rr, count * es)
+                    exp = self.oracle(code, 0, xs, plan, rr)
+                    for pattern in ("mixed", "one_rank", "inplace"):
+                        if pattern == "mixed":  # every rank differently, send and receive differently
+                            soff, roff = offs[(rank + 1) % 4], offs[(rank + 2) % 4]
+                        elif pattern == "one_rank":
+                            soff = roff = es if rank == 1 else 0
+                        else:
+                            soff = roff = offs[1 + rank % 3]
+                        send = Guarded(count * es, soff, "cuda")
+                        send.write(xs[rank])
+                        recv = send
+                        if pattern != "inplace":
+                            recv = Guarded(count * es, roff, "cuda")
+                            recv.prefill_not(exp)
+                        self.barrier()
+                        rr.all_reduce(send.ptr, recv.ptr, count, code, 0, st)
+
+                        def check():
+                            why = F.diff_message(recv.read(), exp) + recv.pads_message()
+                            if recv is not send:
+                                why += send.source_message()
+                            if rr.last_plan != plan:
+                                why += f" plan {rr.last_plan} != {plan}"
+                            return why
+
+                        self.finish(rr, f"{v[0]}/dtype{code}/n{count}/{pattern}", check)
+            # control: one element more than the buffers are guarded for
+            for code, count, off in ((F16, 4097, 0), (F32, 4097, 4)):
+                es = vnode.ESIZE[code]
+                xs = [vnode.gen(code, count + 1, np.random.default_rng([code, count, r, 1])) for r in range(n)]
+                exp = self.oracle(code, 0, xs, plan_of(rr, (count + 1) * es), rr)
+                send, recv = Guarded(xs[rank].nbytes, off, "cuda"), Guarded(count * es, off, "cuda")
+                planted, where = extra_element(exp, count, es)
+                send.write(xs[rank])
+                recv.prefill_not(exp[:count])
+                recv.poke(count * es, planted)
+                self.barrier()
+                rr.all_reduce(send.ptr, recv.ptr, count + 1, code, 0, st)
+                seen = []
+
+                def check():
+                    seen.append(recv.check().tolist())
+                    why = "" if seen[0] == where else f"control reports {seen[0][:8]}, not {where} "
+                    return why + F.diff_message(recv.read(), exp[:count]) + send.source_message()
+
+                self.finish(rr, f"{v[0]}/control/dtype{code}", check)
+                self.reach(f"{v[0]}/control_reports_extra_bytes/dtype{code}", seen[0] == where and len(where) == es)
+            rr.close(self.dist.barrier)
+
+    # -- edge -------------------------------------------------------------------------
+    def mode_edge(self):
+        """All 40 AllReduce kernels on each type's edge values (signed zeros,
+        subnormals, ties, overflow, NaNs, integer wrap): rank 0 holds x, rank 1
+        holds y; expected from the FIFO simulation under the independent functor."""
+        import types
+
+        import elem_ref as E
+        import vnode
+        from test_gpu_edge_values import expected_ring, pair_case
+
+        assert self.n == 2
+        kernels = set()
+        for v in self.variants():
+            rr = self.open(v)
+            shim = types.SimpleNamespace(nchannels=rr.nch, rings=lambda rr=rr: rr.rings)
+            for code in range(10):
+                for op in (E.SUM, E.PROD, E.MAX, E.MIN):
+                    x, y, _ = pair_case(code, op)  # asserts >= 75 % non-NaN and the required result classes
+                    inputs = [x, y]
+                    send, recv = self.dev_bytes(inputs[self.rank]), self.fill(x.nbytes)
+                    self.barrier()
+                    rr.all_reduce(send.data_ptr(), recv.data_ptr(), x.size, code, op, self.stream.cuda_stream)
+
+                    def check():
+                        planned = vnode.Planner(rr.nch, rr.rings).select(x.nbytes, x.nbytes)
+                        if tuple(planned) != tuple(rr.last_plan):
+                            return f"plan {rr.last_plan} != {planned}"
+                        exp = expected_ring(shim, inputs, code, op, v[0])[self.rank]
+                        ok, live = E.same_bits(code, vnode.from_dev(recv, code), exp)
+                        if ok and live >= 0.75:
+                            return ""
+                        bad = E.mismatches(code, vnode.from_dev(recv, code), exp)
+                        return f"{bad.size} of {exp.size} differ, first at {bad[:5].tolist()}, live {live:.2f}"
+
+                    self.finish(rr, f"{v[0]}/dtype{code}/op{op}", check)
+                    kernels.add(self.calls[-1][:3])
+            rr.close(self.dist.barrier)
+        self.reach("all_40_kernels", kernels == {(4, code, op) for code in range(10) for op in range(4)})
 
 
 def big_case(torch, dist, refdrive, orc, rank, n, dev, allgather):

@@ -687,6 +687,41 @@ def test_launch_larger_than_the_work_fifo_is_refused(fake, monkeypatch):
             c.destroy()
 
 
+def test_idle_channels_do_not_stop_the_work_fifo(fake, monkeypatch):
+    """One bucket on every channel, then small ones that take channel 0 only,
+    for many times the work FIFO's depth.  wait_work_queue moves a quiesced
+    channel's done word up to the minimum; unless the channel's expected value
+    moves with it (NCCL waitWorkFifoAvailable), the idle channel looks busy at
+    that value from the next wait on, the minimum cannot pass it, and the host
+    stops once it needs an entry one ring depth beyond it
+    ("work FIFO full and its kernel no longer running")."""
+    monkeypatch.setenv("MCCS_INLINE_WORKS", "0")
+    fake(2)
+    comms = C.init_all([0, 1], C.CommConfig(buffer_size=1 << 20, work_fifo_depth=8))
+    lib = _lib.load()
+    try:
+        _allreduce_group(comms)
+        first = [kv for k, kv in _log() if k == "launch"]
+        lanes, nch = comms[0].lanes, comms[0].nchannels
+        assert nch > 1 and first and all(kv["grid"] == f"{nch * lanes}x1" and kv["inline_works"] == "0" for kv in first)
+        _allreduce_group(comms, count=256)
+        small = [kv for k, kv in _log() if k == "launch"]
+        assert small and all(kv["grid"] == f"{lanes}x1" and kv["inline_works"] == "0" for kv in small)  # one channel
+        for c in comms:
+            c.destroy()
+        # the same sequence on the quiet fake, which acknowledges the works
+        comms = C.init_all([0, 1], C.CommConfig(buffer_size=1 << 20, work_fifo_depth=8))
+        assert lib.mccs_test_fake_quiet(1) == 0
+        _allreduce_group(comms)
+        for _ in range(5 * 8):
+            _allreduce_group(comms, count=256)
+        _allreduce_group(comms)  # and the idle channels take work again
+    finally:
+        lib.mccs_test_fake_quiet(0)
+        for c in comms:
+            c.destroy()
+
+
 def test_capture_leaves_the_eager_issue_order_alone(fake):
     """a launch captured into a graph used to overwrite the comm's
     latest-launch record (stream, event, sync owner) although a capture

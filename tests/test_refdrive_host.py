@@ -87,6 +87,23 @@ def test_work_ring_flow_control_stops_at_depth_without_acknowledgements():
     assert n * 2 <= depth + 2
 
 
+def test_idle_channel_does_not_stop_the_ring():
+    """Channel 1 works once and then idles while channel 0 takes four ring
+    depths of launches: the host must keep moving the idle channel's expected
+    value along with its done word (NCCL waitWorkFifoAvailable), or the idle
+    channel looks busy at a stale value from the second wait on."""
+    depth = 16
+    ring = refdrive.WorkRing(2, depth)
+    sim = _SimKernel(2)
+    start, acks = ring.reserve([0, 1], sim.read, sim.write, timeout_s=2)
+    sim.pending.append(([0, 1], acks, 0))
+    for i in range(4 * depth):
+        start, acks = ring.reserve([0], sim.read, sim.write, timeout_s=2)
+        sim.pending.append(([0], acks, i + 1))
+    assert ring.next_available == 2 + 4 * depth
+    assert sim.read()[1] == ring.chan_next[1]  # idle: done word and expectation agree
+
+
 def test_work_ring_counters_wrap_u32():
     ring = refdrive.WorkRing(2, 16)
     ring.next_available = ring.acked_min = 0xFFFFFFF0
@@ -97,6 +114,268 @@ def test_work_ring_counters_wrap_u32():
         start, acks = ring.reserve([0, 1], sim.read, sim.write, timeout_s=5)
         sim.pending.append(([0, 1], acks, 0))
         assert 0 <= start <= 0xFFFFFFFF and (start % 16) + 2 <= 16
+
+
+# ---- batched plans: pre_launch_schedule + upload_work, host only --------------------------
+F32, MB = 7, 1 << 18  # 1 MiB of fp32: two channels, 544 threads
+
+
+def _tasks(counts, dtype=F32):
+    """One task per count; the send pointer names the task."""
+    return [(0x10000 * (t + 1), 0x10000 * (t + 1) + 8, c, dtype) for t, c in enumerate(counts)]
+
+
+def _ring_of(p, depth):
+    """The work ring after the upload: slot -> work.  No two works of one
+    launch share a slot."""
+    ring = {}
+    for at, w in p.works:
+        assert (at & (depth - 1)) not in ring
+        ring[at & (depth - 1)] = w
+    return ring
+
+
+def _walk(p, depth):
+    """ring_kernel_body's walk (common.h:92-179): block chIdx starts at
+    workHead + chIdx and follows workHead + workNext until isLast; the pointer
+    arithmetic does not wrap, so every slot it computes must lie inside the
+    ring.  Returns per channel id the works visited, each a list of elements
+    (sendbuff, count, nWarps, bid, nChannels), and the doneAcks seen."""
+    ring, head = _ring_of(p, depth), p.start & (depth - 1)
+    out, acks, seen = {}, {}, set()
+    assert p.grid == len(p.chans) == bin(p.mask).count("1")
+    for ch_idx, c in enumerate(p.chans):
+        assert p.mask >> c & 1 and bin(p.mask & ((1 << c) - 1)).count("1") == ch_idx
+        slot, works = head + ch_idx, []
+        while True:
+            assert 0 <= slot < depth and slot not in seen, (slot, c)
+            seen.add(slot)
+            w = ring[slot]
+            assert w.header.type == 1
+            elems = []
+            for i in range(10):
+                e = w.elems[i]
+                if not e.isUsed:
+                    assert all(not w.elems[j].isUsed for j in range(i, 10))
+                    break
+                elems.append((e.sendbuff, e.count, e.nWarps, e.bid, e.nChannels))
+            works.append(elems)
+            if w.header.isLast:
+                assert w.header.inFifo
+                acks[c] = w.header.doneAcks
+                break
+            slot = head + w.header.workNext
+        out[c] = works
+    assert seen == set(ring)  # every uploaded work is visited, by exactly one channel
+    return out, acks
+
+
+def _check_plan(p, tasks, nch, depth):
+    """Every channel visits exactly the elements the plan gave it, in task
+    order; at most 10 per work; a new work exactly where nWarps changes or
+    the work before is full."""
+    visited, acks = _walk(p, depth)
+    want = {c: [] for c in range(nch)}
+    for t, (k, nthr, sel) in enumerate(p.tasks):
+        assert (k, nthr) == C.task_schema(tasks[t][2] * refdrive.ESIZE[tasks[t][3]], nch) and len(sel) == k
+        for bid, c in enumerate(sel):
+            want[c].append((tasks[t][0], tasks[t][2], nthr // 32, bid, k))
+    assert sorted(visited) == [c for c in range(nch) if want[c]] == p.chans
+    for c, works in visited.items():
+        assert [e for w in works for e in w] == want[c]
+        for i, w in enumerate(works):
+            assert 1 <= len(w) <= 10 and len({e[2] for e in w}) == 1
+            if i:
+                assert len(works[i - 1]) == 10 or works[i - 1][0][2] != w[0][2]
+    assert p.block == max(nthr for _, nthr, _ in p.tasks)
+    assert [acks[c] for c in p.chans] == p.acks
+    assert p.nworks == [len(visited[c]) for c in p.chans] and p.end == p.start + sum(p.nworks)
+    return visited
+
+
+@pytest.mark.parametrize("ntasks,nworks", [(1, 1), (10, 1), (11, 2), (21, 3)])
+@pytest.mark.parametrize("position", [0, 5, 1024 + 3])
+def test_batched_plan_walk_two_channels(ntasks, nworks, position):
+    tasks = _tasks([MB + t for t in range(ntasks)])
+    p = refdrive.build_plan(tasks, 2, position)
+    assert p.start == position and p.chans == [0, 1] and p.nworks == [nworks, nworks]
+    visited = _check_plan(p, tasks, 2, refdrive.WORK_DEPTH)
+    assert [len(w) for w in visited[0]] == [10] * (nworks - 1) + [ntasks - 10 * (nworks - 1)]
+    # first works at head + chIdx, later works behind all first works, channel by channel
+    assert sorted(at for at, _ in p.works) == list(range(position, position + 2 * nworks))
+    assert [at for at, _ in p.works] == [position] + list(range(position + 2, position + 1 + nworks)) + \
+        [position + 1] + list(range(position + 1 + nworks, position + 2 * nworks))
+
+
+MIXED = [1000 + 7919 * i for i in range(12)]  # fp32: 96- to 544-thread elements, one to five channels
+
+
+def test_batched_plan_mixed_sizes_five_channels_follow_the_load():
+    import vnode
+
+    nch = 5
+    tasks = _tasks(MIXED)
+    p = refdrive.build_plan(tasks, nch, 7)
+    _check_plan(p, tasks, nch, refdrive.WORK_DEPTH)
+    planner = vnode.Planner(nch, list(range(nch)))
+    for t, (k, nthr, sel) in enumerate(p.tasks):
+        assert (k, nthr, sel) == planner.select(4 * MIXED[t], 4 * MIXED[t]), t
+    # block id b is not channel b, and a channel's elements differ in nWarps
+    assert any(sel != list(range(k)) for k, _, sel in p.tasks)
+    assert len({nthr for _, nthr, _ in p.tasks}) > 1 and max(p.nworks) > 1
+    assert p.block == 544 and p.grid == 5
+
+
+@pytest.mark.parametrize("depth", [16, 1024])
+def test_later_works_cross_the_ring_end_with_negative_work_next(depth):
+    """The wrap test looks at the first works only (plan.rs:436), so with the
+    head two first works before the ring's end the later works continue at
+    slot 0: their workNext, relative to the head, is negative."""
+    tasks = _tasks([MB + t for t in range(21)])  # 2 first + 4 later works
+    for laps in (0, 3):
+        position = laps * depth + depth - 4
+        p = refdrive.build_plan(tasks, 2, position, depth=depth)
+        assert p.start == position and p.end == position + 6  # not moved to the ring start
+        nexts = [w.header.workNext for _, w in p.works if not w.header.isLast]
+        assert min(nexts) == -(depth - 4) and max(nexts) > 0
+        _check_plan(p, tasks, 2, depth)
+    # one slot further the FIRST works would cross: the launch moves to the ring start
+    p = refdrive.build_plan(tasks, 2, depth - 1, depth=depth)
+    assert p.start == depth and all(w.header.workNext > 0 for _, w in p.works if not w.header.isLast)
+    _check_plan(p, tasks, 2, depth)
+
+
+def test_reference_acks_of_a_multi_work_launch():
+    """plan.rs:461-470: DoneAcks = new_subsequent_start + 1 when the channel's
+    last work is written.  Channels 0 and 2 have one work, channel 1 three."""
+    nworks = [1, 3, 1]
+    assert refdrive.WorkRing.acks_for(100, nworks, True) == [104, 105, 106]
+    assert refdrive.WorkRing.acks_for(100, nworks, False) == [105, 105, 105]
+    assert refdrive.WorkRing.acks_for(100, [3, 1, 2], True) == [105, 106, 106]
+    assert refdrive.WorkRing.acks_for(100, [3, 1, 2], False) == [105, 106, 106]
+    assert refdrive.WorkRing.acks_for(100, [1, 3], True) == [103, 104]
+    assert refdrive.WorkRing.acks_for(100, [1, 3], False) == [104, 104]
+    assert refdrive.WorkRing.acks_for(100, [1, 1], True) == [103, 103]
+    assert refdrive.WorkRing.acks_for(0xFFFFFFFE, [1, 1], False) == [0, 0]
+
+
+def test_reserve_without_later_works_is_unchanged():
+    for ref in (False, True):
+        a, b = refdrive.WorkRing(4, 16, reference_acks=ref), refdrive.WorkRing(4, 16, reference_acks=ref)
+        sa, sb = _SimKernel(4), _SimKernel(4)
+        for i in range(100):
+            chans = list(range(1 + i % 4))
+            start, acks = a.reserve(chans, sa.read, sa.write, timeout_s=5)
+            start2, acks2 = b.reserve_works(chans, [1] * len(chans), sb.read, sb.write, timeout_s=5)
+            assert (start, [acks] * len(chans)) == (start2, acks2)
+            assert acks == (start + len(chans) + ref) & 0xFFFFFFFF
+            assert (a.next_available, a.chan_next, a.acked_min) == (b.next_available, b.chan_next, b.acked_min)
+            sa.pending.append((chans, acks, i))
+            sb.pending.append((chans, acks, i))
+
+
+class _SimChannels:
+    """Launches run in stream order; within the oldest one, one channel per
+    host poll loads its next work (walking workNext as the kernel does) and
+    acknowledges only when that work is its last.  `mem` is the ring: slot ->
+    id of the launch whose work the host wrote there last."""
+
+    def __init__(self, nch, depth, rng):
+        self.done, self.depth, self.rng = [0] * nch, depth, rng
+        self.mem, self.pending, self.overwritten = {}, [], []
+
+    def launch(self, lid, start, works, chans):
+        ring = {}
+        for at, w in works:
+            self.mem[at % self.depth] = lid
+            ring[at % self.depth] = w
+        head = start % self.depth
+        self.pending.append({"id": lid, "head": head, "ring": ring, "at": {c: head + i for i, c in enumerate(chans)}})
+
+    def read(self):
+        if self.pending:
+            la = self.pending[0]
+            c = sorted(la["at"])[self.rng.integers(len(la["at"]))]
+            slot = la["at"][c]
+            if self.mem[slot] != la["id"]:  # the host reused the slot before this channel read it
+                self.overwritten.append((la["id"], slot, slot == la["head"]))
+            w = la["ring"][slot]
+            if w.header.isLast:
+                self.done[c] = w.header.doneAcks
+                del la["at"][c]
+                if not la["at"]:
+                    self.pending.pop(0)
+            else:
+                la["at"][c] = la["head"] + w.header.workNext
+        return list(self.done)
+
+    def write(self, c, v):
+        self.done[c] = v
+
+
+def _random_launches(depth, nch, reference_acks, seed, launches):
+    import numpy as np
+
+    rng = np.random.default_rng(seed)
+    ring = refdrive.WorkRing(nch, depth, reference_acks=reference_acks)
+    sim = _SimChannels(nch, depth, rng)
+    task = [(0x1000, 0x2000, 1, F32)]
+    crossed = multi = 0
+    for lid in range(launches):
+        k = int(rng.integers(1, nch + 1))
+        chans = sorted(rng.choice(nch, k, replace=False).tolist())
+        nworks = [int(rng.integers(1, 4)) if rng.random() < 0.5 else 1 for _ in chans]
+        queues = [[] for _ in range(nch)]
+        for c, w in zip(chans, nworks):
+            queues[c] = [[(0, 3, 0, 1)] for _ in range(w)]
+        start, acks = ring.reserve_works(chans, nworks, sim.read, sim.write, timeout_s=5)
+        assert start % depth + k <= depth  # the first works are contiguous
+        works, chans2, nworks2, acks2 = refdrive.layout_works(task, queues, start, depth, reference_acks)
+        assert (chans2, nworks2, acks2) == (chans, nworks, acks)
+        crossed += any(w.header.workNext < 0 for _, w in works if not w.header.isLast)
+        multi += sum(nworks) > k
+        sim.launch(lid, start, works, chans)
+    return sim.overwritten, crossed, multi
+
+
+@pytest.mark.parametrize("depth,nch", [(16, 3), (16, 5), (64, 6)])
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_multi_work_launches_never_reuse_an_unread_slot(depth, nch, seed):
+    """With the exact acknowledgement (the slot after a chained channel's last
+    work, the launch's end for a single work; written when the channel loads
+    its LAST work) the host, always as far ahead as the
+    flow control lets it, never rewrites a slot before its channel read it."""
+    overwritten, crossed, multi = _random_launches(depth, nch, False, seed, 60 * depth)
+    assert not overwritten
+    assert crossed > 0 and multi > 10  # later works crossed the ring's end on the way
+
+
+def test_reference_acks_with_multi_work_launches_free_only_the_next_head_early():
+    """The reference arithmetic is one past the launch only for a single-work
+    channel behind which no later works follow; the slot it frees early is
+    the head of the next launch, and no other."""
+    hits = []
+    for seed in (1, 2, 3):
+        overwritten, crossed, multi = _random_launches(16, 4, True, seed, 60 * 16)
+        assert crossed > 0 and multi > 10
+        hits += overwritten
+    assert hits and all(is_head for _, _, is_head in hits)
+
+
+def test_all_gather_plan_uses_total_bytes_of_every_rank():
+    """task.rs:95-102: the schema of an AllGather comes from nbytes * n; the
+    element count is the rank's own nbytes (all_gather.h:16)."""
+    n, nbytes = 3, 30000
+    assert C.task_schema(nbytes, 2)[0] == 1 and C.task_schema(nbytes * n, 2) == (2, 544)
+    p = refdrive.build_plan([(0x7000, 0x9000, nbytes, 0)], 2, 11, func=refdrive.FUNC_ALLGATHER, nranks=n)
+    assert p.tasks == [(2, 544, [0, 1])] and (p.grid, p.block, p.mask, p.start, p.end) == (2, 544, 3, 11, 13)
+    visited, _ = _walk(p, refdrive.WORK_DEPTH)
+    assert visited == {0: [[(0x7000, nbytes, 17, 0, 2)]], 1: [[(0x7000, nbytes, 17, 1, 2)]]}
+    assert [w.elems[0].recvbuff for _, w in p.works] == [0x9000, 0x9000]
+    # a small one: one channel, the thread count of the total
+    p = refdrive.build_plan([(0x7000, 0x9000, 4000, 0)], 2, 0, func=refdrive.FUNC_ALLGATHER, nranks=n)
+    assert p.tasks == [(1, C.task_schema(12000, 2)[1], [0])] and p.tasks[0][1] != C.task_schema(4000, 2)[1]
+    assert p.works[0][1].elems[0].count == 4000 and p.works[0][1].elems[0].nChannels == 1
 
 
 @pytest.mark.parametrize("n", [2, 4, 8])
