@@ -221,6 +221,35 @@ mccsResult_t mccsAllReduce(const void *sendbuff, void *recvbuff, size_t count, i
 /* libmccs::all_gather: sendbytes per rank; recvbuff holds nranks*sendbytes. */
 mccsResult_t mccsAllGather(const void *sendbuff, void *recvbuff, size_t sendbytes, mccsComm_t comm,
                            hipStream_t stream);
+/* Ring ReduceScatter.  Not in the reference: it declares the function
+ * (mccsFuncReduceScatter = 3, src/collectives/include/devcomm.h:14 and
+ * src/mccs/src/proxy/task.rs:12) but stops at unimplemented!() in
+ * CollTask::total_bytes (task.rs:95-102) and ships no kernel for it.
+ * sendbuff holds nranks * recvcount elements of dtype, block D at element
+ * D * recvcount; rank r receives in recvbuff (recvcount elements) the
+ * reduction over all ranks of block r.  dtype: any mccsDevDataType_t; op:
+ * mccsDevSum / Prod / Max / Min.  For block D on a channel the value is
+ * acc = x[s1], then acc = fn(x[sk], acc) for k = 2..n, each hop rounded in
+ * dtype, where s1..sn are the successors of D along that channel's ring and
+ * sn = D (the operand order of the AllReduce ring).  Which channel an element
+ * belongs to follows the ring walk.
+ * Stream-ordered, returns after launch.  As for mccsAllReduce: a
+ * communicator's collectives run in issue order whatever stream each is issued
+ * on; every launch takes the communicator's launch guard; several
+ * ReduceScatters of one comm in one group are batched into one launch (mixing
+ * functions, dtypes or ops on one comm in a group is refused with
+ * mccsInvalidUsage at mccsGroupEnd); ranks sharing a GPU run as one fused
+ * launch; the call may be captured into a HIP graph; the watchdog and
+ * mccsCommAbort end a stuck kernel.  Always the ring (mccsCommLastAlgo reports
+ * MCCS_ALGO_RING), whatever the size: the direct / LL variants do not take it.
+ * In place means recvbuff == sendbuff + rank * recvcount (in elements) and is
+ * supported; no other overlap of the two buffers is.  Out of place, sendbuff
+ * is never written.  Nothing outside [recvbuff, recvbuff + recvcount) is
+ * written.  recvcount == 0 succeeds and launches nothing; an unknown dtype or
+ * op and null buffers are refused with mccsInvalidArgument; nranks == 1 is a
+ * local copy. */
+mccsResult_t mccsReduceScatter(const void *sendbuff, void *recvbuff, size_t recvcount, int dtype, int op,
+                               mccsComm_t comm, hipStream_t stream);
 /* Group calls (ProxyCommand::GroupCall): collectives issued between Start and
  * End are planned together and launched at End (one launch per device). */
 mccsResult_t mccsGroupStart(void);
@@ -343,6 +372,12 @@ mccsResult_t mccsStreamWaitShared(hipStream_t stream, void *event);
 mccsResult_t mccs_host_ring_allreduce(int nranks, const void *const *sendbufs, void *const *recvbufs, size_t count,
                                       int dtype, int op, int nchannels, int nthreads_ref, int buff_size,
                                       const int *rings);
+/* The ring ReduceScatter schedule (mccsReduceScatter) and FIFO protocol on
+ * host threads over host memory: sendbufs[r] holds nranks * recvcount
+ * elements, recvbufs[r] recvcount; in place as for mccsReduceScatter. */
+mccsResult_t mccs_host_ring_reduce_scatter(int nranks, const void *const *sendbufs, void *const *recvbufs,
+                                           size_t recvcount, int dtype, int op, int nchannels, int nthreads_ref,
+                                           int buff_size, const int *rings);
 /* Default ring orders for an n-rank node (edge-disjoint Hamiltonian cycles,
  * both directions); writes up to max_channels x nranks ints, returns count. */
 int mccs_default_rings(int nranks, int nch_req, int *out, int max_channels);

@@ -104,6 +104,7 @@ SIGNATURES: dict[str, tuple] = {
     "mccsCommConnect": (_c_int, [_c_void_p, _c_void_p]),
     "mccsAllReduce": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_int, _c_void_p, _c_void_p]),
     "mccsAllGather": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_void_p]),
+    "mccsReduceScatter": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_int, _c_void_p, _c_void_p]),
     "mccsGroupStart": (_c_int, []),
     "mccsGroupEnd": (_c_int, []),
     "mccsCommSync": (_c_int, [_c_void_p]),
@@ -138,6 +139,9 @@ SIGNATURES: dict[str, tuple] = {
     "mccs_task_schema": (None, [_c_size_t, _c_int, _P(_c_int), _P(_c_int)]),
     "mccs_direct_defaults": (None, [_c_int, _P(_c_int), _P(_c_int)]),
     "mccs_host_ring_allreduce": (
+        _c_int, [_c_int, _P(_c_void_p), _P(_c_void_p), _c_size_t, _c_int, _c_int, _c_int, _c_int, _c_int,
+                 _P(_c_int)]),
+    "mccs_host_ring_reduce_scatter": (
         _c_int, [_c_int, _P(_c_void_p), _P(_c_void_p), _c_size_t, _c_int, _c_int, _c_int, _c_int, _c_int,
                  _P(_c_int)]),
 }

@@ -8,6 +8,8 @@ Mirrors the reference application API (src/libmccs/src/lib.rs:19-27):
   all_reduce(comm, send, recv, size, dtype,     all_reduce(comm, send, recv, size, dtype,
              op, stream) -> Result<(), Error>              op, stream)  (raises MccsError)
   all_gather(comm, send, recv, size, stream)    all_gather(comm, send, recv, size, stream)
+  (none: ReduceScatter is declared but          reduce_scatter(comm, send, recv, recv_count, dtype,
+   unimplemented, task.rs:95-102)                              op, stream)
   AllReduceDataType {Float16, Int32}            AllReduceDataType (+ Float32: the one API delta,
                                                 SURVEY §8(b); + the other kernel dtypes)
   AllReduceOpType {Sum, Prod, ...}              AllReduceOpType
@@ -189,6 +191,10 @@ class Communicator:
     def all_gather(self, send_buf, recv_buf, size: int, stream=None) -> None:
         all_gather(self, send_buf, recv_buf, size, stream)
 
+    def reduce_scatter(self, send_buf, recv_buf, recv_count: int, data_type=AllReduceDataType.Float32,
+                       op_type=AllReduceOpType.Sum, stream=None) -> None:
+        reduce_scatter(self, send_buf, recv_buf, recv_count, data_type, op_type, stream)
+
     def sync(self) -> None:
         """Waits for the comm's launches; raises on a device-side timeout/abort."""
         _lib.check(_sig().mccsCommSync(self._h), "mccsCommSync")
@@ -276,6 +282,16 @@ def all_gather(comm: Communicator, send_buf, recv_buf, size: int, stream=None) -
     _lib.check(rc, "mccsAllGather")
 
 
+def reduce_scatter(comm: Communicator, send_buf, recv_buf, recv_count: int, data_type=AllReduceDataType.Float32,
+                   op_type=AllReduceOpType.Sum, stream=None) -> None:
+    """mccsReduceScatter: send holds nranks * recv_count elements (block D at
+    element D * recv_count); recv gets recv_count elements, the reduction of
+    this rank's block over all ranks.  Always the ring; stream-ordered."""
+    rc = _sig().mccsReduceScatter(_ptr(send_buf), _ptr(recv_buf), int(recv_count), int(data_type), int(op_type),
+                                  comm._h, _stream(stream))
+    _lib.check(rc, "mccsReduceScatter")
+
+
 @contextlib.contextmanager
 def group():
     """ProxyCommand::GroupCall: collectives inside are launched together at exit."""
@@ -311,6 +327,24 @@ def host_ring_allreduce(sendbufs, recvbufs, count: int, data_type, op_type=AllRe
     _lib.check(rc, "mccs_host_ring_allreduce")
 
 
+def host_ring_reduce_scatter(sendbufs, recvbufs, recv_count: int, data_type, op_type=AllReduceOpType.Sum,
+                             channels: int = 1, nthreads: int = 96, buffer_size: int = 1 << 22, rings=None) -> None:
+    """The ring ReduceScatter schedule on host threads over host memory (numpy
+    arrays or raw host pointers; no GPU): sendbufs[r] holds nranks * recv_count
+    elements, recvbufs[r] recv_count."""
+    n = len(sendbufs)
+    arr = ctypes.c_void_p * max(1, n)
+    sp = arr(*[x.ctypes.data if hasattr(x, "ctypes") else int(x) for x in sendbufs])
+    rp = arr(*[x.ctypes.data if hasattr(x, "ctypes") else int(x) for x in recvbufs])
+    ro = None
+    if rings is not None:
+        flat = [int(v) for r in rings for v in r]
+        ro = (_ci * len(flat))(*flat)
+    rc = _sig().mccs_host_ring_reduce_scatter(n, sp, rp, int(recv_count), int(data_type), int(op_type), channels,
+                                              nthreads, buffer_size, ro)
+    _lib.check(rc, "mccs_host_ring_reduce_scatter")
+
+
 def ring_profile(device: int = 0, reset: bool = True) -> dict:
     """Per-slice timing of the ring kernels on `device` (MCCS_RING_PROFILE=1
     set before communicator init): slices, mean µs waiting for peer flags,
@@ -343,7 +377,7 @@ def task_schema(total_bytes: int, channels: int) -> tuple[int, int]:
 
 
 __all__ = ["AllReduceDataType", "AllReduceOpType", "CommConfig", "Communicator", "init_all",
-           "init_communicator_rank", "all_reduce", "all_gather", "group", "default_rings", "task_schema",
+           "init_communicator_rank", "all_reduce", "all_gather", "reduce_scatter", "group", "default_rings", "task_schema",
            "direct_defaults", "ll_default",
-           "host_ring_allreduce", "ring_profile",
+           "host_ring_allreduce", "host_ring_reduce_scatter", "ring_profile",
            "RedOp", "DataType"]

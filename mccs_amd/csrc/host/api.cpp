@@ -199,15 +199,19 @@ static mccsResult_t launch_single(Comm* c, int func, int dtype, int op, const vo
   if (c->failed) return reject(mccsRemoteError, "the communicator failed earlier (watchdog or abort): destroy it");
   if (count == 0) return mccsSuccess;
   if (!send || !recv) return reject(mccsInvalidArgument, "null send or recv buffer");
-  if (func == mccsFuncAllReduce && (dtype < 0 || dtype >= mccsNumTypes || op < 0 || op > mccsDevMin))
+  if ((func == mccsFuncAllReduce || func == mccsFuncReduceScatter) &&
+      (dtype < 0 || dtype >= mccsNumTypes || op < 0 || op > mccsDevMin))
     return reject(mccsInvalidArgument, "unknown dtype or reduction op");
+  const char* const name = func == mccsFuncAllGather       ? "mccsAllGather"
+                           : func == mccsFuncReduceScatter ? "mccsReduceScatter"
+                                                           : "mccsAllReduce";
   if (std::find(g_group.comms.begin(), g_group.comms.end(), c) == g_group.comms.end()) {
     g_group.comms.push_back(c);
     g_group.streams.push_back(stream);
   }
   mccsResult_t er;
   {
-    StepScope st(func == mccsFuncAllGather ? "mccsAllGather" : "mccsAllReduce");
+    StepScope st(name);
     er = plan_enqueue(c, func, dtype, op, send, recv, count);
   }
   if (er != mccsSuccess) {
@@ -216,7 +220,7 @@ static mccsResult_t launch_single(Comm* c, int func, int dtype, int op, const vo
     return er;
   }
   if (g_group.depth == 0) {
-    StepScope st(func == mccsFuncAllGather ? "mccsAllGather launch" : "mccsAllReduce launch");
+    StepScope st(std::string(name) + " launch");
     mccsResult_t r = plan_launch_group(g_group.comms, g_group.streams);
     group_discard();
     return r;
@@ -587,6 +591,11 @@ extern "C" mccsResult_t mccsAllReduce(const void* sendbuff, void* recvbuff, size
 extern "C" mccsResult_t mccsAllGather(const void* sendbuff, void* recvbuff, size_t sendbytes, mccsComm_t comm,
                                       hipStream_t stream) {
   return launch_single((Comm*)comm, mccsFuncAllGather, mccsInt8, mccsDevSum, sendbuff, recvbuff, sendbytes, stream);
+}
+
+extern "C" mccsResult_t mccsReduceScatter(const void* sendbuff, void* recvbuff, size_t recvcount, int dtype, int op,
+                                          mccsComm_t comm, hipStream_t stream) {
+  return launch_single((Comm*)comm, mccsFuncReduceScatter, dtype, op, sendbuff, recvbuff, recvcount, stream);
 }
 
 extern "C" mccsResult_t mccsGroupStart(void) {

@@ -11,6 +11,9 @@
 // own parked worker, so a 1 KiB AllReduce costs no thread creation.  It exists so the FIFO
 // protocol and schedule can be exercised end to end without a GPU; it is not
 // a fallback for the device path (nothing on the device path calls it).
+// mccs_host_ring_reduce_scatter runs the ring ReduceScatter schedule
+// (ring_kernel.h; not in the reference) through the same primitive, so the
+// device walk has a second implementation that runs without a GPU.
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -164,7 +167,7 @@ struct HostConn {  // one directed FIFO (rank -> next) of one channel
 };
 
 struct Ctx {
-  int n, nch, dt, op, nthreads_ref, buff_size;
+  int func, n, nch, dt, op, nthreads_ref, buff_size;
   size_t es, count;
   const void* const* send;
   void* const* recv;
@@ -174,35 +177,47 @@ struct Ctx {
   double timeout_s;
 };
 
-// one (rank, channel) thread executing runRing
-void run_rank_channel(Ctx* c, int rank, int ch) {
-  const int n = c->n;
-  int ring[64];  // n <= 64 (mccs_host_ring_allreduce)
-  for (int i = 0; i < n; ++i) ring[i] = c->rings ? c->rings[ch * n + i] : i;
-  int pos = 0, pos0 = 0;
-  for (int i = 0; i < n; ++i) {
-    if (ring[i] == rank) pos = i;
-    if (ring[i] == 0) pos0 = i;
-  }
-  const int next = ring[(pos + 1) % n], prev = ring[(pos + n - 1) % n];
-  const int ringIx = (pos - pos0 + n) % n;
-  HostConn& out = (*c->conns)[ch * n + rank];
-  HostConn& in = (*c->conns)[ch * n + prev];
-  (void)next;
-  const int64_t stepSize = c->buff_size / MCCS_BUFFER_SLOTS / (int64_t)c->es;
-  const int64_t chunkSize = (int64_t)(int)(stepSize * ALLREDUCE_CHUNKSTEPS);
-  const int64_t size = (int64_t)c->count;
-  const int64_t loopSize = (int64_t)c->nch * n * chunkSize;
-  int64_t gran = (int64_t)(c->nthreads_ref - WARP_SIZE) * 8 / (int64_t)c->es;
-  if (gran < 1) gran = 1;
-  const char* input = (const char*)c->send[rank];
-  char* output = (char*)c->recv[rank];
+// One (rank, channel) task: its place on the channel's ring, its two
+// connectors and the FIFO primitive every schedule is written in.
+struct RankChannel {
+  Ctx* c;
+  int n, rank, ch;
+  int ring[64];  // n <= 64 (checked by the entry points)
+  int pos, ringIx;
+  HostConn* out;
+  HostConn* in;
+  int64_t stepSize;
+  const char* input;
+  char* output;
   uint64_t rstep = 0, sstep = 0;
-  thread_local std::vector<char> tmp_store;  // this worker's staging slice, kept across calls
-  if (tmp_store.size() < (size_t)(2 * stepSize * c->es)) tmp_store.resize((size_t)(2 * stepSize * c->es));
-  char* const tmp = tmp_store.data();
-  const auto t0 = std::chrono::steady_clock::now();
-  auto wait_geq = [&](std::atomic<uint64_t>& f, uint64_t target) {
+  char* tmp;
+  std::chrono::steady_clock::time_point t0;
+
+  RankChannel(Ctx* ctx, int rank_, int ch_) : c(ctx), n(ctx->n), rank(rank_), ch(ch_) {
+    for (int i = 0; i < n; ++i) ring[i] = c->rings ? c->rings[ch * n + i] : i;
+    int pos0 = 0;
+    pos = 0;
+    for (int i = 0; i < n; ++i) {
+      if (ring[i] == rank) pos = i;
+      if (ring[i] == 0) pos0 = i;
+    }
+    const int prev = ring[(pos + n - 1) % n];
+    ringIx = (pos - pos0 + n) % n;
+    out = &(*c->conns)[ch * n + rank];
+    in = &(*c->conns)[ch * n + prev];
+    stepSize = c->buff_size / MCCS_BUFFER_SLOTS / (int64_t)c->es;
+    input = (const char*)c->send[rank];
+    output = (char*)c->recv[rank];
+    thread_local std::vector<char> tmp_store;  // this worker's staging slice, kept across calls
+    if (tmp_store.size() < (size_t)(2 * stepSize * c->es)) tmp_store.resize((size_t)(2 * stepSize * c->es));
+    tmp = tmp_store.data();
+    t0 = std::chrono::steady_clock::now();
+  }
+
+  // ring.userRanks: the ring order starting at this rank
+  int user_rank(int i) const { return ring[(pos + i) % n]; }
+
+  bool wait_geq(std::atomic<uint64_t>& f, uint64_t target) {
     // the peer is a running thread: spin (pause) before giving up the core
     for (int spin = 0; spin < 4096; ++spin) {
       if (f.load(std::memory_order_acquire) >= target) return true;
@@ -217,9 +232,10 @@ void run_rank_channel(Ctx* c, int rank, int ch) {
       std::this_thread::yield();
     }
     return true;
-  };
+  }
+
   // genericOp: RECV/SEND/SRC(input)/DST(output) flags, two slices per call
-  auto op = [&](bool RECV, bool SEND, bool SRC, bool DST, int64_t srcIx, int64_t dstIx, int64_t nelem) {
+  bool op(bool RECV, bool SEND, bool SRC, bool DST, int64_t srcIx, int64_t dstIx, int64_t nelem) {
     if (nelem < 0) nelem = 0;
     int64_t sliceSize = stepSize * ALLREDUCE_SLICESTEPS;
     const int64_t s = (nelem + 32 - 1) / 32 * 16;
@@ -229,11 +245,11 @@ void run_rank_channel(Ctx* c, int rank, int ch) {
       int64_t real = nelem - offset;
       real = real < sliceSize ? real : sliceSize;
       if (real < 0) real = 0;
-      if (RECV && !wait_geq(in.tail, rstep + 2)) return false;
-      if (SEND && !wait_geq(out.head, sstep + 2 > 8 ? sstep + 2 - 8 : 0)) return false;
+      if (RECV && !wait_geq(in->tail, rstep + 2)) return false;
+      if (SEND && !wait_geq(out->head, sstep + 2 > 8 ? sstep + 2 - 8 : 0)) return false;
       const size_t bytes = (size_t)real * c->es;
-      const char* rslot = in.data.get() + (rstep % 8) * stepSize * c->es;
-      char* sslot = out.data.get() + (sstep % 8) * stepSize * c->es;
+      const char* rslot = in->data.get() + (rstep % 8) * stepSize * c->es;
+      char* sslot = out->data.get() + (sstep % 8) * stepSize * c->es;
       if (bytes) {
         // vals = srcs[0]; vals = fn(vals, srcs[1]) with srcs = [input?, recv?]
         if (SRC && RECV) apply(c->dt, c->op, tmp, input + (srcIx + offset) * c->es, rslot, (size_t)real);
@@ -246,15 +262,26 @@ void run_rank_channel(Ctx* c, int rank, int ch) {
       // remaining (empty) slices with this one: the same step counts as a
       // post per slice, one cross-thread hand-off instead of two
       const int64_t adv = offset + sliceSize >= nelem ? 2 * (2 - slice) : 2;
-      if (SEND) out.tail.store(sstep + adv, std::memory_order_release);
-      if (RECV) in.head.store(rstep + adv, std::memory_order_release);
+      if (SEND) out->tail.store(sstep + adv, std::memory_order_release);
+      if (RECV) in->head.store(rstep + adv, std::memory_order_release);
       if (RECV) rstep += adv;
       if (SEND) sstep += adv;
       if (adv > 2) break;
       offset += sliceSize;
     }
     return true;
-  };
+  }
+};
+
+// runRing of AllReduce (all_reduce.h:10-87)
+void walk_allreduce(RankChannel& k) {
+  const Ctx* c = k.c;
+  const int n = k.n, ch = k.ch, ringIx = k.ringIx;
+  const int64_t chunkSize = (int64_t)(int)(k.stepSize * ALLREDUCE_CHUNKSTEPS);
+  const int64_t size = (int64_t)c->count;
+  const int64_t loopSize = (int64_t)c->nch * n * chunkSize;
+  int64_t gran = (int64_t)(c->nthreads_ref - WARP_SIZE) * 8 / (int64_t)c->es;
+  if (gran < 1) gran = 1;
   auto mod = [&](int r) { return r >= n ? r - n : r; };
   for (int64_t g = 0; g < size; g += loopSize) {
     int64_t rcs = (size - g + (int64_t)c->nch * n - 1) / ((int64_t)c->nch * n);
@@ -263,20 +290,52 @@ void run_rank_channel(Ctx* c, int rank, int ch) {
     auto off = [&](int chunk) { return g + (int64_t)ch * n * rcs + (int64_t)chunk * rcs; };
     auto ne = [&](int64_t o) { return rcs < size - o ? rcs : size - o; };
     int chunk = mod(ringIx + n - 1);
-    if (!op(false, true, true, false, off(chunk), 0, ne(off(chunk)))) return;
+    if (!k.op(false, true, true, false, off(chunk), 0, ne(off(chunk)))) return;
     for (int j = 2; j < n; ++j) {
       chunk = mod(ringIx + n - j);
-      if (!op(true, true, true, false, off(chunk), 0, ne(off(chunk)))) return;
+      if (!k.op(true, true, true, false, off(chunk), 0, ne(off(chunk)))) return;
     }
     chunk = ringIx;
-    if (!op(true, true, true, true, off(chunk), off(chunk), ne(off(chunk)))) return;
+    if (!k.op(true, true, true, true, off(chunk), off(chunk), ne(off(chunk)))) return;
     for (int j = 1; j < n - 1; ++j) {
       chunk = mod(ringIx + n - j);
-      if (!op(true, true, false, true, 0, off(chunk), ne(off(chunk)))) return;
+      if (!k.op(true, true, false, true, 0, off(chunk), ne(off(chunk)))) return;
     }
     chunk = mod(ringIx + 1);
-    if (!op(true, false, false, true, 0, off(chunk), ne(off(chunk)))) return;
+    if (!k.op(true, false, false, true, 0, off(chunk), ne(off(chunk)))) return;
   }
+}
+
+// Ring ReduceScatter (ring_kernel.h): count = elements per
+// block; call j of a loop works on block userRanks[n-1-j], the last one
+// (recvReduceCopy) on the rank's own block, written at the chunk's offset.
+void walk_reduce_scatter(RankChannel& k) {
+  const Ctx* c = k.c;
+  const int n = k.n;
+  const int64_t chunkSize = (int64_t)(int)(k.stepSize * ALLREDUCE_CHUNKSTEPS);
+  const int64_t size = (int64_t)c->count;
+  const int64_t loopSize = (int64_t)c->nch * chunkSize;
+  int64_t gran = (int64_t)(c->nthreads_ref - WARP_SIZE) * 8 / (int64_t)c->es;
+  if (gran < 1) gran = 1;
+  for (int64_t g = 0; g < size; g += loopSize) {
+    int64_t rcs = (size - g + c->nch - 1) / c->nch;
+    rcs = chunkSize < rcs ? chunkSize : rcs;
+    rcs = (int64_t)(int)((rcs + gran - 1) / gran * gran);
+    const int64_t chunkOffset = g + (int64_t)(int)(k.ch * rcs);
+    const int64_t nelem = rcs < size - chunkOffset ? rcs : size - chunkOffset;  // <= 0: empty calls
+    auto src = [&](int j) { return chunkOffset + (int64_t)k.user_rank(n - 1 - j) * size; };
+    if (!k.op(false, true, true, false, src(0), 0, nelem)) return;
+    for (int j = 1; j < n - 1; ++j)
+      if (!k.op(true, true, true, false, src(j), 0, nelem)) return;
+    if (!k.op(true, false, true, true, src(n - 1), chunkOffset, nelem)) return;
+  }
+}
+
+// one (rank, channel) thread
+void run_rank_channel(Ctx* c, int rank, int ch) {
+  RankChannel k(c, rank, ch);
+  if (c->func == mccsFuncReduceScatter) walk_reduce_scatter(k);
+  else walk_allreduce(k);
 }
 
 // Parked worker threads, one per concurrent (rank, channel) task: every task
@@ -375,9 +434,9 @@ class HostRingPool {
 
 }  // namespace
 
-extern "C" mccsResult_t mccs_host_ring_allreduce(int nranks, const void* const* sendbufs, void* const* recvbufs,
-                                                 size_t count, int dtype, int op, int nchannels, int nthreads_ref,
-                                                 int buff_size, const int* rings) {
+static mccsResult_t host_ring_run(int func, int nranks, const void* const* sendbufs, void* const* recvbufs,
+                                  size_t count, int dtype, int op, int nchannels, int nthreads_ref, int buff_size,
+                                  const int* rings) {
   if (nranks < 1 || nranks > 64 || !sendbufs || !recvbufs || dtype < 0 || dtype >= mccsNumTypes || op < 0 ||
       op > mccsDevMin || nchannels < 1 || nchannels > MCCS_MAX_NCHANNELS || nthreads_ref <= WARP_SIZE ||
       buff_size < 8192 || buff_size % 8192)
@@ -388,9 +447,10 @@ extern "C" mccsResult_t mccs_host_ring_allreduce(int nranks, const void* const* 
     return mccsSuccess;
   }
   HostRingPool& pool = HostRingPool::get();
-  std::lock_guard<std::mutex> call(pool.call_mu);  // one host-ring AllReduce at a time
+  std::lock_guard<std::mutex> call(pool.call_mu);  // one host-ring collective at a time
   std::vector<HostConn>& conns = pool.fifos((size_t)nchannels * nranks, (size_t)buff_size);
   Ctx c;
+  c.func = func;
   c.n = nranks;
   c.nch = nchannels;
   c.dt = dtype;
@@ -406,4 +466,18 @@ extern "C" mccsResult_t mccs_host_ring_allreduce(int nranks, const void* const* 
   c.timeout_s = 60.0;
   pool.run(&c, nranks * nchannels);
   return c.failed.load() ? mccsTimeout : mccsSuccess;
+}
+
+extern "C" mccsResult_t mccs_host_ring_allreduce(int nranks, const void* const* sendbufs, void* const* recvbufs,
+                                                 size_t count, int dtype, int op, int nchannels, int nthreads_ref,
+                                                 int buff_size, const int* rings) {
+  return host_ring_run(mccsFuncAllReduce, nranks, sendbufs, recvbufs, count, dtype, op, nchannels, nthreads_ref,
+                       buff_size, rings);
+}
+
+extern "C" mccsResult_t mccs_host_ring_reduce_scatter(int nranks, const void* const* sendbufs, void* const* recvbufs,
+                                                      size_t recvcount, int dtype, int op, int nchannels,
+                                                      int nthreads_ref, int buff_size, const int* rings) {
+  return host_ring_run(mccsFuncReduceScatter, nranks, sendbufs, recvbufs, recvcount, dtype, op, nchannels,
+                       nthreads_ref, buff_size, rings);
 }

@@ -79,7 +79,11 @@ static void enqueue_elem(ChannelSchedule& s, const WorkElemHost& e, int func_ind
 
 static mccsResult_t ring_enqueue(Comm* c, int func, int dtype, int op, const void* send, void* recv, size_t count) {
   const size_t esize = (size_t)elem_bytes(dtype);
-  const size_t total = func == mccsFuncAllGather ? count * c->nranks : count * esize;  // task.rs:95-102
+  // task.rs:95-102.  ReduceScatter (not in the reference: task.rs stops at unimplemented!()) counts
+  // like AllGather, the bytes that enter the ring: count is elements per block
+  const size_t total = func == mccsFuncAllGather       ? count * c->nranks
+                       : func == mccsFuncReduceScatter ? count * esize * c->nranks
+                                                       : count * esize;
   int nch = 0, nthr = 0;
   task_schema(total, c->nch, &nch, &nthr);
   int chans[MCCS_MAX_NCHANNELS];
@@ -139,7 +143,8 @@ mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send
   const bool twoshot = func == mccsFuncAllReduce && c->layout.direct_slot > 0 && bytes <= (size_t)c->cfg.direct_bytes;
   const bool ll = ll_fits(c, bytes);
   // (the LL one-shot makes no remote atomics: it runs without peer atomics,
-  // the count-based variants need them)
+  // the count-based variants need them).  A ReduceScatter always takes the
+  // ring: the direct variants are AllReduce / AllGather only.
   if (!c->plan_pending && (func == mccsFuncAllReduce || func == mccsFuncAllGather) &&
       ((c->direct_ok && (oneshot || twoshot)) || ll)) {
     c->plan_direct = true;
@@ -208,7 +213,7 @@ static mccsResult_t wait_work_queue(Comm* c, uint32_t target) {
 }
 
 struct LaunchDesc {
-  const void* fn = nullptr;
+  const void* fn = nullptr;  // reference-named single-rank kernel (none for ReduceScatter); launches use multi_fn
   const void* multi_fn = nullptr;
   uint64_t mask = 0;
   int nch_used = 0;
@@ -304,7 +309,7 @@ static mccsResult_t upload_work_graph(Comm* c, LaunchDesc* ld, hipGraph_t graph)
   ld->multi_fn = ring_multi_kernel_ptr(c->plan_func, c->plan_dtype, c->plan_op);
   for (auto& s : c->sched) s.reset();
   c->plan_pending = false;
-  return (ld->fn && ld->multi_fn) ? mccsSuccess : mccsInvalidArgument;
+  return ld->multi_fn ? mccsSuccess : mccsInvalidArgument;
 }
 
 // A launch whose ranks' used channels each hold one work carries the works in
@@ -342,7 +347,7 @@ static mccsResult_t upload_work_inline(Comm* c, LaunchDesc* ld, mccsMultiLaunchA
   ld->multi_fn = ring_multi_kernel_ptr(c->plan_func, c->plan_dtype, c->plan_op);
   for (auto& s : c->sched) s.reset();
   c->plan_pending = false;
-  return (ld->fn && ld->multi_fn) ? mccsSuccess : mccsInvalidArgument;
+  return ld->multi_fn ? mccsSuccess : mccsInvalidArgument;
 }
 
 static mccsResult_t upload_work(Comm* c, LaunchDesc* ld) {
@@ -412,7 +417,7 @@ static mccsResult_t upload_work(Comm* c, LaunchDesc* ld) {
   ld->multi_fn = ring_multi_kernel_ptr(c->plan_func, c->plan_dtype, c->plan_op);
   for (auto& s : c->sched) s.reset();
   c->plan_pending = false;
-  return (ld->fn && ld->multi_fn) ? mccsSuccess : mccsInvalidArgument;
+  return ld->multi_fn ? mccsSuccess : mccsInvalidArgument;
 }
 
 // Blocks of the fused multi-rank kernels the device holds at once, minimised
@@ -434,11 +439,14 @@ int coresident_ring_blocks(int block, int device) {
   int ncu = 0;
   if (rt().CuCount(&ncu, device) != hipSuccess) return 0;
   int best = 1 << 30;
-  const void* fns[1 + mccsNumTypes * 4];
+  const void* fns[1 + 2 * mccsNumTypes * 4];
   int nf = 0;
   fns[nf++] = ring_multi_kernel_ptr(mccsFuncAllGather, mccsInt8, 0);
   for (int dt = 0; dt < mccsNumTypes; ++dt)
-    for (int op = 0; op < 4; ++op) fns[nf++] = ring_multi_kernel_ptr(mccsFuncAllReduce, dt, op);
+    for (int op = 0; op < 4; ++op) {
+      fns[nf++] = ring_multi_kernel_ptr(mccsFuncAllReduce, dt, op);
+      fns[nf++] = ring_multi_kernel_ptr(mccsFuncReduceScatter, dt, op);
+    }
   for (int i = 0; i < nf; ++i) {
     int per_cu = 0;
     if (!fns[i] || rt().BlocksPerCu(&per_cu, fns[i], block) != hipSuccess) return 0;

@@ -1,7 +1,8 @@
 // ring.hip — AllGather ring kernel, kernel tables and device-wide helpers of
 // the ring path.  The device engine is ring_kernel.h; the forty AllReduce
 // kernels live in ring_ar_{sum,prod,max,min}.hip (one translation unit per
-// reduction op, compiled in parallel).
+// reduction op, compiled in parallel), the forty ReduceScatter kernels in
+// ring_rs_{sum,prod,max,min}.hip.
 #include "ring_kernel.h"
 
 namespace mccs {
@@ -28,6 +29,14 @@ const void* ring_ar_kernel_Sum(int dtype, bool multi);
 const void* ring_ar_kernel_Prod(int dtype, bool multi);
 const void* ring_ar_kernel_Max(int dtype, bool multi);
 const void* ring_ar_kernel_Min(int dtype, bool multi);
+const void* ring_rs_kernel_Sum(int dtype);
+const void* ring_rs_kernel_Prod(int dtype);
+const void* ring_rs_kernel_Max(int dtype);
+const void* ring_rs_kernel_Min(int dtype);
+hipError_t ring_tu_rs_sum_read_profile(unsigned long long* out, bool reset);
+hipError_t ring_tu_rs_prod_read_profile(unsigned long long* out, bool reset);
+hipError_t ring_tu_rs_max_read_profile(unsigned long long* out, bool reset);
+hipError_t ring_tu_rs_min_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_ar_sum_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_ar_prod_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_ar_max_read_profile(unsigned long long* out, bool reset);
@@ -49,6 +58,18 @@ static const void* ar_kernel(int dtype, int op, bool multi) {
   return nullptr;
 }
 
+// ReduceScatter has multi-rank kernels only (no reference-named entry points)
+static const void* rs_kernel(int dtype, int op) {
+  if (dtype < 0 || dtype >= mccsNumTypes) return nullptr;
+  switch (op) {
+    case OpSum: return ring_rs_kernel_Sum(dtype);
+    case OpProd: return ring_rs_kernel_Prod(dtype);
+    case OpMax: return ring_rs_kernel_Max(dtype);
+    case OpMin: return ring_rs_kernel_Min(dtype);
+  }
+  return nullptr;
+}
+
 const void* ring_kernel_ptr(int func, int dtype, int op) {
   if (func == mccsFuncAllGather) return (const void*)&mccsKernel_AllGather_RING_SIMPLE_Sum_int8_t;
   if (func != mccsFuncAllReduce) return nullptr;
@@ -57,6 +78,7 @@ const void* ring_kernel_ptr(int func, int dtype, int op) {
 
 const void* ring_multi_kernel_ptr(int func, int dtype, int op) {
   if (func == mccsFuncAllGather) return (const void*)&ring_multi_kernel<mccsFuncAllGather, mccsInt8, OpSum>;
+  if (func == mccsFuncReduceScatter) return rs_kernel(dtype, op);
   if (func != mccsFuncAllReduce) return nullptr;
   return ar_kernel(dtype, op, true);
 }
@@ -86,7 +108,8 @@ hipError_t ring_read_profile(unsigned long long* out, bool reset) {
   for (int i = 0; i < MCCS_PROF_N; ++i) out[i] = 0;
   hipError_t (*const readers[])(unsigned long long*, bool) = {
       ring_tu_ag_read_profile, ring_tu_ar_sum_read_profile, ring_tu_ar_prod_read_profile,
-      ring_tu_ar_max_read_profile, ring_tu_ar_min_read_profile};
+      ring_tu_ar_max_read_profile, ring_tu_ar_min_read_profile, ring_tu_rs_sum_read_profile,
+      ring_tu_rs_prod_read_profile, ring_tu_rs_max_read_profile, ring_tu_rs_min_read_profile};
   for (auto rd : readers) {
     hipError_t e = rd(out, reset);
     if (e != hipSuccess) return e;

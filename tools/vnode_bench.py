@@ -30,7 +30,12 @@ def main():
     ap.add_argument("--profile", action="store_true", help="per-slice wait/stream timing (MCCS_RING_PROFILE)")
     ap.add_argument("--graph", action="store_true", help="also time the same calls captured in one HIP graph")
     ap.add_argument("--allgather", action="store_true", help="time AllGather (size = bytes per rank) instead")
+    ap.add_argument("--reduce-scatter", action="store_true",
+                    help="time ReduceScatter (size = bytes per rank of input; each rank receives size / n) instead")
     args = ap.parse_args()
+    if args.allgather and args.reduce_scatter:
+        ap.error("--allgather and --reduce-scatter are exclusive")
+    coll = "allgather" if args.allgather else "reduce_scatter" if args.reduce_scatter else "allreduce"
     if args.profile:
         os.environ["MCCS_RING_PROFILE"] = "1"
     for n in args.n:
@@ -42,11 +47,14 @@ def main():
             for kib in (args.sizes_kib or [m << 10 for m in args.sizes_mib]):
                 cnt = (kib << 10) // 4
                 xs = [torch.randn(cnt, device="cuda") for _ in range(n)]
-                ys = [torch.empty(n * cnt if args.allgather else cnt, device="cuda") for _ in xs]
+                ys = [torch.empty(n * cnt if args.allgather else cnt // n if args.reduce_scatter else cnt,
+                                  device="cuda") for _ in xs]
 
                 def call(r, st=None):
                     if args.allgather:
                         C.all_gather(comms[r], xs[r], ys[r], cnt * 4, stream=st)
+                    elif args.reduce_scatter:  # the first n * (cnt // n) elements of the input
+                        C.reduce_scatter(comms[r], xs[r], ys[r], cnt // n, C.AllReduceDataType.Float32, stream=st)
                     else:
                         C.all_reduce(comms[r], xs[r], ys[r], cnt, C.AllReduceDataType.Float32, stream=st)
 
@@ -86,7 +94,7 @@ def main():
                     torch.cuda.synchronize()
                     graph_ms = (time.perf_counter() - t0) / args.iters * 1e3
                     del g
-                print(json.dumps({"coll": "allgather" if args.allgather else "allreduce", "n": n, "lanes": comms[0].lanes, "channels": comms[0].nchannels,
+                print(json.dumps({"coll": coll, "n": n, "lanes": comms[0].lanes, "channels": comms[0].nchannels,
                                   "block": comms[0].block_threads, "bridge": args.bridge, "KiB": kib, "ms": round(dt * 1e3, 4),
                                   "algbw_GBps": round((kib << 10) / dt / 1e9, 2), "slice_profile": prof,
                                   "graph_ms": round(graph_ms, 4) if graph_ms else None,
