@@ -132,6 +132,108 @@ def seq_stream(comm, rank, world, orc, vnode, nops=40, streams=False):
     return out
 
 
+def rs_seq_stream(comm, rank, world, orc, vnode, nops=40, streams=False):
+    """tests/test_gpu_reduce_scatter_fuzz.py's sequence (ReduceScatters among
+    AllReduces, AllGathers and groups; same list on every rank) on this
+    rank's communicator, as seq_stream above.  A rank alone in its process
+    launches the multi-rank kernel for a ReduceScatter; last_algo() after
+    each one is recorded and reported."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    from mccs_amd import comm as C
+    import test_gpu_reduce_scatter_fuzz as F
+
+    seq = F.rs_sequence(np.random.default_rng(F.IPC_BASE + world), nops)
+    rng = np.random.default_rng(77 + rank)
+    srng = np.random.default_rng(500 + rank)
+    pool = [torch.cuda.current_stream(), torch.cuda.Stream(), torch.cuda.Stream()]
+
+    def stream():
+        if not streams:
+            return None
+        st = pool[int(srng.integers(0, 3))]
+        st.wait_stream(torch.cuda.current_stream())  # the inputs were copied on the current stream
+        return st
+
+    checks, algos, rs_algos = [], set(), set()
+    for i, o in enumerate(seq):
+        batch = []
+        for call in F.resolve(o, world):
+            x = F.call_input(call, world, rng)
+            xs = [None] * world
+            dist.all_gather_object(xs, x)
+            kind, cnt = call["kind"], call["count"]
+            es = 1 if kind == "ag" else vnode.ESIZE[call["code"]]
+            send = vnode.to_dev(x)
+            if not call["inplace"]:
+                recv = out = vnode.to_dev(np.zeros((world if kind == "ag" else 1) * cnt * es, np.uint8))
+                lo, hi = 0, out.numel()
+            elif kind == "rs":
+                recv, out, lo, hi = send.data_ptr() + rank * cnt * es, send, rank * cnt * es, (rank + 1) * cnt * es
+            else:
+                recv, out, lo, hi = send, send, 0, send.numel()
+            batch.append((call, xs, send, recv, out, lo, hi))
+        st = stream()
+        with C.group():
+            for call, xs, send, recv, out, lo, hi in batch:
+                if call["kind"] == "ag":
+                    C.all_gather(comm, send, recv, call["count"], st)
+                elif call["kind"] in ("rs", "rsgroup"):
+                    C.reduce_scatter(comm, send, recv, call["count"], call["code"], call["op"], st)
+                else:
+                    C.all_reduce(comm, send, recv, call["count"], call["code"], call["op"], st)
+        if o["kind"] == "ar":
+            algos.add(comm.last_algo())
+        elif o["kind"] in ("rs", "rsgroup"):
+            rs_algos.add(comm.last_algo())
+        for k, (call, xs, send, recv, out, lo, hi) in enumerate(batch):
+            checks.append((f"{i}.{k}/{call['kind']}/code{call['code']}/op{call['op']}/n{call['count']}", call, xs, send,
+                           out, lo, hi))
+    torch.cuda.synchronize()
+    comm.sync()
+    res = {}
+    for what, call, xs, send, out, lo, hi in checks:
+        exp = F.call_expected(orc, call, xs, comm.nchannels, comm.rings())[rank]
+        res[f"rsseq/{what}"] = out.cpu().numpy()[lo:hi].tobytes() == exp.tobytes()
+    res["rsseq/algos:" + ",".join(sorted(a for a in algos if a))] = True
+    res["rsseq/rs_algos:" + ",".join(sorted(str(a) for a in rs_algos))] = rs_algos == {"ring"}
+    return res
+
+
+def rs_checks(comm, rank, world, orc, vnode, mode):
+    """Two ReduceScatters of a rank that is alone in its process (the
+    multi-rank kernel launched for one rank, over IPC-mapped arenas): fp16 Sum
+    of 30011 elements per block and int64 Max of 4099, against tests/rs_ref.py."""
+    import numpy as np
+    import torch.distributed as dist
+
+    from mccs_amd import comm as C
+    import rs_ref
+
+    res = {}
+    for name, code, op, cnt in (("f16sum", 6, 0, 30011), ("i64max", 4, 2, 4099)):
+        rng = np.random.default_rng(cnt * 17 + rank)
+        x = vnode.gen(code, world * cnt, rng)
+        if code == 4:  # full-range values: the high words matter to Max
+            x = rng.integers(-(1 << 62), 1 << 62, world * cnt, dtype=np.int64)
+        xs = [None] * world
+        dist.all_gather_object(xs, x)
+        send = vnode.to_dev(x)
+        recv = vnode.to_dev(np.zeros(cnt, vnode.NPDT[code]))
+        try:
+            C.reduce_scatter(comm, send, recv, cnt, code, op)
+            comm.sync()
+            exp = rs_ref.expected_planned(orc, xs, code, op, comm)[rank]
+            ok = vnode.from_dev(recv, code).tobytes() == exp.tobytes() and comm.last_algo() == "ring"
+        except Exception as e:  # noqa: BLE001
+            print(f"[rank {rank}] {mode} rs {name}: {e}", flush=True)
+            ok = False
+        res[f"{mode}/rs/{name}/n{cnt}"] = ok
+    return res
+
+
 def _streams():
     """Two streams on different hardware queues: HIP maps a process's streams
     onto a few queues (GPU_MAX_HW_QUEUES, 4 here) and runs one queue's
@@ -239,6 +341,9 @@ def main():
                  # tests/test_gpu_sequence_fuzz.py's random sequence at the defaults
                  "seq": (C.FIFO_UNCACHED, C.LOCALITY_RECEIVER),
                  "seqs": (C.FIFO_UNCACHED, C.LOCALITY_RECEIVER),
+                 # tests/test_gpu_reduce_scatter_fuzz.py's sequence (ReduceScatters among the others)
+                 "rsseq": (C.FIFO_UNCACHED, C.LOCALITY_RECEIVER),
+                 "rsseqs": (C.FIFO_UNCACHED, C.LOCALITY_RECEIVER),
                  # a graph replay beside an eager launch of the same comm (launch guard)
                  "guard": (C.FIFO_UNCACHED, C.LOCALITY_RECEIVER)}
     direct_kw = {"direct": dict(direct_bytes=8 << 20, oneshot_bytes=-1, ll_bytes=-1),
@@ -257,8 +362,10 @@ def main():
         kw.setdefault("lanes", lanes)
         comm = C.init_communicator_rank(rank, world, dev, exchange,
                                         C.CommConfig(fifo_memory=fifo, locality=loc, timeout_ms=20000, **kw))
-        if mode in ("ddp", "seq", "seqs", "guard"):
-            if mode == "guard":
+        if mode in ("ddp", "seq", "seqs", "rsseq", "rsseqs", "guard"):
+            if mode in ("rsseq", "rsseqs"):
+                results.update(rs_seq_stream(comm, rank, world, orc, vnode, streams=mode == "rsseqs"))
+            elif mode == "guard":
                 results.update(guard_overlap(comm, rank, world, orc, vnode))
             elif mode == "ddp":
                 results.update(ddp_stream(comm, rank, world, orc, vnode))
@@ -327,6 +434,7 @@ def main():
                 exp = orc.ring_allreduce(7, 0, xs_all[i], nchannels=nch, nthreads=nthr, ring_orders=rings)
                 ok = ok and bool(np.array_equal(vnode.from_dev(recvs[i], 7).view(np.uint8), exp.view(np.uint8)))
             results[f"{mode}/back_to_back_x{k}"] = ok
+        results.update(rs_checks(comm, rank, world, orc, vnode, mode))
         if torch.cuda.device_count() < world:  # co-located processes: lanes shrunk to half the ring slots
             # auto lanes (api.cpp make_comm) capped at half of MI355X's 256 one-per-CU ring slots
             auto = (128 if world == 2 else 64) // comm.nchannels

@@ -13,6 +13,10 @@ get_task_schema.
   * block D's piece on channel bid is folded along that channel's ring:
     acc = x[s1], acc = fn(x[sk], acc) for k = 2..n, s1..sn the successors of
     D on the ring and sn = D (the operand order of oracle ring_visit).
+
+`orc` in fold / expected / expected_planned is anything with
+`.apply(code, op, x, acc)`: the oracle module, or ELEM_REF below, which
+evaluates the same schedule under the independent tests/elem_ref.py.
 """
 from __future__ import annotations
 
@@ -84,3 +88,79 @@ def rank_order(orc, inputs, code, op):
     n = len(inputs)
     cnt = inputs[0].size // n
     return [fold(orc, code, op, [inputs[r][d * cnt:(d + 1) * cnt] for r in range(n)]) for d in range(n)]
+
+
+class ElemRef:
+    """Stands in for the oracle module in fold / expected / expected_planned:
+    `.apply` is the independent reference of tests/elem_ref.py, on raw storage
+    arrays (bf16 as uint16 bits), so the same schedule can be evaluated without
+    the oracle's functor."""
+
+    @staticmethod
+    def apply(code, op, x, acc):
+        import elem_ref as E
+
+        return E.ref_op(code, op, x, acc)
+
+
+ELEM_REF = ElemRef()
+
+
+def fold_classes(code, op, parts, tie_budget=64):
+    """(fold result, union of elem_ref.result_classes over every step) in this
+    module's operand order, acc = fn(parts[k], acc): elem_ref.fold_classes
+    folds fn(acc, s), which picks the other zero in Max / Min of +0 and -0."""
+    import elem_ref as E
+
+    acc = np.ascontiguousarray(parts[0]).view(E.NPDT[code])
+    got = set()
+    for x in parts[1:]:
+        nxt = E.ref_op(code, op, x, acc)
+        got |= E.result_classes(code, op, x, acc, nxt, tie_budget=tie_budget)
+        acc = nxt
+    return acc, got
+
+
+# ---- edge-value inputs (tests/test_gpu_reduce_scatter_values.py, tests/test_reduce_scatter_cases.py) ----
+_edge_cache = {}
+BF16_RANDOM = 1001  # odd, as elem_ref.N_RANDOM
+
+
+def edge_inputs(n, code, op):
+    """Per-rank ReduceScatter inputs made of elem_ref's edge values.
+
+    n = 2: rank 0 holds x and rank 1 holds y of edge_pairs(code, seed=d) in
+    block d.  n > 2: block d is edge_sources(code, n, op, seed=d), rank r
+    holding source (r - d - 1) % n, so that on the identity ring block d's
+    fold visits the sources 0, 1, .., n-1 in that order.  bf16, whose Sum and
+    Prod reference works in exact rationals element by element, gets a third
+    of the random tail per block (n blocks of it cost what the AllReduce
+    suite's single set does); designed columns and edge values stay whole.
+
+    Returned read-only and checked once for vacuity on the identity ring's
+    fold: every block's expected value is at least 75 % non-NaN, and the
+    per-step classes contain elem_ref.required_classes(code, op)."""
+    import elem_ref as E
+
+    key = (n, code, op)
+    if key in _edge_cache:
+        return _edge_cache[key]
+    if n == 2:
+        blocks = [E.edge_pairs(code, seed=d) for d in range(n)]  # blocks[d][r]
+    else:
+        nrandom = BF16_RANDOM if code == 9 else E.N_RANDOM
+        srcs = [E.edge_sources(code, n, op, seed=d, nrandom=nrandom) for d in range(n)]
+        blocks = [[srcs[d][(r - d - 1) % n] for r in range(n)] for d in range(n)]
+    inputs = [np.concatenate([blocks[d][r] for d in range(n)]) for r in range(n)]
+    cnt = inputs[0].size // n
+    assert all(x.size == n * cnt for x in inputs)
+    for d in range(n):
+        parts = [inputs[(d + k) % n][d * cnt:(d + 1) * cnt] for k in range(1, n + 1)]
+        ref, classes = fold_classes(code, op, parts, tie_budget=4000 if n == 2 else 64)
+        _, live = E.same_bits(code, ref, ref)
+        assert live >= 0.75, (n, code, op, d, live)
+        assert classes >= E.required_classes(code, op), (n, code, op, d, classes)
+    for x in inputs:
+        x.setflags(write=False)
+    _edge_cache[key] = inputs
+    return inputs

@@ -40,3 +40,9 @@ def test_multi_process_ring_matches_oracle(world, modes):
     res = json.loads(lines[-1])
     assert res["all_ok"], res
     assert res["world"] == world
+    # every mode also ran two ReduceScatters (the multi-rank kernel launched by a
+    # process that owns one rank), checked per rank against tests/rs_ref.py
+    rs = {k: v for k, v in res["fifo_modes"].items() if "/rs/" in k}
+    assert set(rs) == {f"{m}/rs/{c}" for m in modes.split(",") for c in ("f16sum/n30011", "i64max/n4099")}, rs
+    assert all(rs.values()), rs
+    print(f"{world} processes, ReduceScatter per FIFO mode:", rs)

@@ -125,6 +125,29 @@ def test_mixing_functions_in_a_group_is_refused_at_group_end(fake):
             c.destroy()
 
 
+@pytest.mark.parametrize("second", [(F16, SUM), (F32, 2)], ids=["dtype", "op"])
+def test_mixing_dtypes_or_ops_in_a_group_is_refused_at_group_end(fake, second):
+    """Several ReduceScatters of one communicator in a group must share dtype
+    and op (tests/test_gpu_reduce_scatter_fuzz.py's rsgroup keeps to that)."""
+    fake(2)
+    comms = C.init_all([0, 1], C.CommConfig(buffer_size=1 << 20))
+    lib = _lib.load()
+    try:
+        _log()
+        assert lib.mccsGroupStart() == 0
+        for r, c in enumerate(comms):
+            assert lib.mccsReduceScatter(_send(r), _recv(r), 1024, F32, SUM, c._h, 0) == 0
+        assert lib.mccsReduceScatter(_send(0) + 0x100000, _recv(0) + 0x100000, 1024, second[0], second[1],
+                                     comms[0]._h, 0) == INVALID_USAGE
+        assert lib.mccsGroupEnd() == INVALID_USAGE
+        assert not any(k == "launch" for k, _ in _log())
+        _reduce_scatter_group(comms, 1024)  # the comms stay usable
+        assert sum(1 for k, _ in _log() if k == "launch") == 2
+    finally:
+        for c in comms:
+            c.destroy()
+
+
 def test_refusals_and_empty_calls(fake):
     fake(2)
     comms = C.init_all([0, 1], C.CommConfig(buffer_size=1 << 20))
