@@ -389,6 +389,17 @@ void mccs_direct_defaults(int nranks, int *oneshot_bytes, int *direct_bytes);
 int mccs_ll_default(int nranks);
 /* get_task_schema (plan.rs:602-635): channels and threads for total_bytes. */
 void mccs_task_schema(size_t total_bytes, int nch_cfg, int *nch, int *nthreads);
+/* The chunk walk of one work element, as every kernel and host path cuts it:
+ * func = mccsFuncAllReduce (count = the buffer's elements), mccsFuncAllGather
+ * (elem_bytes = 1, count = bytes per rank) or mccsFuncReduceScatter (count =
+ * elements per block); width = 64 (the ring's arithmetic) or 32 (the direct
+ * kernels'; count < 2^31).  Writes the first max_rows rows of four values
+ * {gridOffset, realChunkSize, chunk offset, nelem}, one row per loop and part
+ * (AllReduce: part = bid * nranks + ring chunk; otherwise part = bid), nelem
+ * 0 for a part past the end.  Returns the walk's row count, -1 for invalid
+ * arguments. */
+long long mccs_ring_walk(int func, int nranks, int nchannels, int elem_bytes, int nthreads_ref, int buff_size,
+                         size_t count, int width, long long *rows, long long max_rows);
 
 /* Library identification. */
 const char *mccs_hip_version(void);

@@ -138,6 +138,8 @@ SIGNATURES: dict[str, tuple] = {
     "mccs_default_rings": (_c_int, [_c_int, _c_int, _P(_c_int), _c_int]),
     "mccs_task_schema": (None, [_c_size_t, _c_int, _P(_c_int), _P(_c_int)]),
     "mccs_direct_defaults": (None, [_c_int, _P(_c_int), _P(_c_int)]),
+    "mccs_ring_walk": (
+        ctypes.c_longlong, [_c_int] * 6 + [_c_size_t, _c_int, _P(ctypes.c_longlong), ctypes.c_longlong]),
     "mccs_host_ring_allreduce": (
         _c_int, [_c_int, _P(_c_void_p), _P(_c_void_p), _c_size_t, _c_int, _c_int, _c_int, _c_int, _c_int,
                  _P(_c_int)]),

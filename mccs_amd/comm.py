@@ -376,8 +376,27 @@ def task_schema(total_bytes: int, channels: int) -> tuple[int, int]:
     return a.value, b.value
 
 
+FUNC_ALLGATHER, FUNC_REDUCE_SCATTER, FUNC_ALLREDUCE = 2, 3, 4  # mccsDevFunc_t (include/mccs_devcomm.h)
+
+
+def ring_walk(func: int, nranks: int, channels: int, elem_bytes: int, nthreads: int, buffer_size: int, count: int,
+              width: int = 64) -> list[tuple[int, int, int, int]]:
+    """The chunk walk of one work element as the kernels and host paths cut it
+    (csrc/ring_walk.h; host-only): one (gridOffset, realChunkSize, offset,
+    nelem) per loop and part, in 64-bit or 32-bit arithmetic."""
+    args = (int(func), int(nranks), int(channels), int(elem_bytes), int(nthreads), int(buffer_size), int(count),
+            int(width))
+    n = _sig().mccs_ring_walk(*args, None, 0)
+    if n < 0:
+        raise ValueError(f"mccs_ring_walk{args}: invalid argument")
+    rows = (ctypes.c_longlong * (4 * max(1, n)))()
+    assert _sig().mccs_ring_walk(*args, rows, n) == n
+    vals = rows[:4 * n]
+    return list(zip(vals[0::4], vals[1::4], vals[2::4], vals[3::4]))
+
+
 __all__ = ["AllReduceDataType", "AllReduceOpType", "CommConfig", "Communicator", "init_all",
            "init_communicator_rank", "all_reduce", "all_gather", "reduce_scatter", "group", "default_rings", "task_schema",
-           "direct_defaults", "ll_default",
+           "direct_defaults", "ll_default", "ring_walk",
            "host_ring_allreduce", "host_ring_reduce_scatter", "ring_profile",
            "RedOp", "DataType"]

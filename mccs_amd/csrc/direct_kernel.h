@@ -8,7 +8,8 @@
 // keeps from the reference is everything that decides a result bit for bit:
 // the ring's chunk walk (all_reduce.h:28-42: chunkSize, loopSize,
 // realChunkSize rounding, chunk k of channel bid at gridOffset +
-// (bid*n + k)*realChunkSize), chunk k's owner (the rank at ring index k of
+// (bid*n + k)*realChunkSize; the functions of ring_walk.h that the ring
+// kernels call, here in 32 bits), chunk k's owner (the rank at ring index k of
 // channel bid's ring) and its summation order (acc = x[idx k+1];
 // acc = fn(x[idx k+j], acc) for j = 2..n, rounded in T at every step,
 // all_reduce.h:46-70 + prims_simple.h:174-177), so the output equals the
@@ -74,11 +75,11 @@ __device__ unsigned long long g_dtrace[MCCS_MULTI_MAX_RANKS][kDtEvents];
 #define MCCS_DTRACE(ev) ((void)0)
 #endif
 
-// The walk in 32-bit arithmetic: a direct bucket holds < 2^31 elements
-// (direct_bytes <= 1 GiB), and 64-bit divisions are long software sequences
-// that a per-chunk loop run by every thread cannot afford.
-struct DirectWalk {
-  uint32_t size, chunkSize, loopSize, gran;
+// The AllReduce walk (ring_walk.h) in 32-bit arithmetic: a direct bucket holds
+// < 2^31 elements (direct_bytes <= 1 GiB), and 64-bit divisions are long
+// software sequences that a per-chunk loop run by every thread cannot afford.
+// tests/test_ring_walk.py holds the 32-bit walk to the 64-bit one up to that size.
+struct DirectWalk : RingWalk<uint32_t> {
   uint32_t n, nch;
 };
 
@@ -88,14 +89,9 @@ __device__ __forceinline__ DirectWalk direct_walk(const mccsDirectArgs& a) {
   DirectWalk w;
   w.n = a.nranks;
   w.nch = a.nch;
-  w.size = (uint32_t)a.count;
-  // all_reduce.h:17-21 with the ring kernel's arithmetic (ring_kernel.h run_elem)
-  const uint32_t stepSize = (uint32_t)((int)a.buff_size / MCCS_BUFFER_SLOTS / (int)sizeof(T));
-  w.chunkSize = stepSize * ALLREDUCE_CHUNKSTEPS;
-  const uint64_t loop = (uint64_t)w.nch * w.n * w.chunkSize;
-  w.loopSize = loop > 0x7fffffffu ? 0x7fffffffu : (uint32_t)loop;  // >= size: one loop
-  w.gran = ((a.nthr_ref - WARP_SIZE) * 8) / (uint32_t)sizeof(T);
-  if (w.gran < 1) w.gran = 1;
+  ring_walk<uint32_t>(w, mccsFuncAllReduce, (int)a.nranks, (int)a.nch, (int)sizeof(T), (int)a.nthr_ref,
+                      (int)a.buff_size, (uint32_t)a.count);
+  walk_guard<uint32_t>(w);
   return w;
 }
 
@@ -112,16 +108,14 @@ __device__ __forceinline__ void direct_pieces(const DirectWalk& w, const uint8_t
   uint32_t base = 0;  // (pieces of selected chunks before this one) mod G
   const uint32_t parts = w.nch * w.n;
   for (uint32_t g = 0; g < w.size; g += w.loopSize) {
-    uint32_t rcs = (w.size - g + parts - 1) / parts;  // realChunkSize, all_reduce.h:30-36
-    rcs = w.chunkSize < rcs ? w.chunkSize : rcs;
-    rcs = (rcs + w.gran - 1) / w.gran * w.gran;
+    const uint32_t rcs = real_chunk_size<uint32_t>(w, g, parts);
     const uint32_t np_full = (rcs + pc - 1) / pc;
     for (uint32_t c = 0, bid = 0, k = 0; c < parts; ++c, k = k + 1 == w.n ? 0 : k + 1, bid += k == 0) {
-      const uint32_t off = g + c * rcs;
+      const uint32_t off = allreduce_chunk_offset(g, c, rcs);
       if (off >= w.size) return;  // every later chunk of the walk is empty
       const uint32_t owner = idx2rank[bid][k];
       if (!want(owner)) continue;
-      const uint32_t ne = rcs < w.size - off ? rcs : w.size - off;
+      const uint32_t ne = chunk_nelem(w.size, off, rcs);
       const uint32_t np = ne == rcs ? np_full : (ne + pc - 1) / pc;
       for (uint32_t j = bx >= base ? bx - base : bx + G - base; j < np; j += G) {
         const uint32_t s = j * pc;
@@ -638,10 +632,7 @@ __device__ __forceinline__ void direct_ll_body(const mccsDirectArgs& a) {
     if (!ag) {
       const uint32_t e = wd * EPW;
       const uint32_t g = e / w.loopSize * w.loopSize;
-      uint32_t rcs = (w.size - g + parts - 1) / parts;  // realChunkSize, all_reduce.h:30-36
-      rcs = w.chunkSize < rcs ? w.chunkSize : rcs;
-      rcs = (rcs + w.gran - 1) / w.gran * w.gran;
-      const uint32_t c = (e - g) / rcs;
+      const uint32_t c = (e - g) / real_chunk_size<uint32_t>(w, g, parts);  // allreduce_chunk_offset's part holding e
       bid = c / n;
       k = c - bid * n;
     }

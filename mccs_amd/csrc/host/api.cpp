@@ -16,6 +16,7 @@
 
 #include "comm.h"
 #include "dtypes.h"
+#include "ring_walk.h"
 
 namespace mccs {
 void task_schema(size_t total_bytes, int nch_cfg, int* nch_out, int* nthreads_out);
@@ -750,6 +751,43 @@ extern "C" void mccs_direct_defaults(int nranks, int* oneshot_bytes, int* direct
 
 extern "C" void mccs_task_schema(size_t total_bytes, int nch_cfg, int* nch, int* nthreads) {
   task_schema(total_bytes, nch_cfg, nch, nthreads);
+}
+
+// The chunk walk of one work element as every kernel and host path takes it
+// (ring_walk.h), one row {gridOffset, realChunkSize, chunk offset, nelem} per
+// loop and part; nelem is 0 for a part past the end of the buffer.
+template <typename I>
+static long long ring_walk_rows(int func, int nranks, int nch, int esize, int nthr, int buff_size, size_t count,
+                                long long* rows, long long max_rows) {
+  RingWalk<I> w;
+  ring_walk<I>(w, func, nranks, nch, esize, nthr, buff_size, (I)count);
+  walk_guard(w);
+  const I parts = walk_parts<I>(func, nch, nranks);
+  long long n = 0;
+  for (I g = 0; g < w.size; g += w.loopSize) {
+    const I rcs = real_chunk_size(w, g, parts);
+    for (I c = 0; c < parts; ++c, ++n) {
+      const I off = func == mccsFuncAllReduce ? allreduce_chunk_offset(g, c, rcs) : block_chunk_offset(g, c, rcs);
+      if (n >= max_rows) continue;
+      const long long row[4] = {(long long)g, (long long)rcs, (long long)off,
+                                off < w.size ? (long long)chunk_nelem(w.size, off, rcs) : 0};
+      std::memcpy(rows + 4 * n, row, sizeof(row));
+    }
+  }
+  return n;
+}
+
+extern "C" long long mccs_ring_walk(int func, int nranks, int nchannels, int elem_bytes, int nthreads_ref,
+                                    int buff_size, size_t count, int width, long long* rows, long long max_rows) {
+  if ((func != mccsFuncAllReduce && func != mccsFuncAllGather && func != mccsFuncReduceScatter) || nranks < 1 ||
+      nchannels < 1 || nchannels > MCCS_MAX_NCHANNELS || elem_bytes < 1 || nthreads_ref <= WARP_SIZE ||
+      buff_size < 8192 || buff_size % 8192 || (width != 32 && width != 64) || (max_rows > 0 && !rows) ||
+      (width == 32 && count > 0x7fffffffu))
+    return -1;
+  return width == 32 ? ring_walk_rows<uint32_t>(func, nranks, nchannels, elem_bytes, nthreads_ref, buff_size, count,
+                                                rows, max_rows)
+                     : ring_walk_rows<int64_t>(func, nranks, nchannels, elem_bytes, nthreads_ref, buff_size, count,
+                                               rows, max_rows);
 }
 
 // Ring profile counters of `device` (MCCS_RING_PROFILE=1 at communicator

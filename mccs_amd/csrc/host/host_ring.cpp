@@ -25,10 +25,14 @@
 #include <thread>
 #include <vector>
 
+#include "dtypes.h"
 #include "mccs_devcomm.h"
 #include "mccs_hip.h"
+#include "ring_walk.h"
 
 namespace {
+
+using mccs::RingWalk;
 
 float h2f(uint16_t h) {
   const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, exp = (h >> 10) & 0x1f, man = h & 0x3ffu;
@@ -149,13 +153,6 @@ void apply(int dt, int op, void* out, const void* x, const void* y, size_t n) {
 #undef INT_CASE
 }
 
-size_t esize(int dt) {
-  return (dt == mccsInt8 || dt == mccsUint8) ? 1
-         : (dt == mccsFloat16 || dt == mccsBfloat16) ? 2
-         : (dt == mccsInt32 || dt == mccsUint32 || dt == mccsFloat32) ? 4
-         : 8;
-}
-
 struct HostConn {  // one directed FIFO (rank -> next) of one channel
   // uninitialised: only the slots a call touches are ever faulted in (a
   // zero-filled 4 MiB FIFO per connector cost ms per 1 KiB call)
@@ -186,6 +183,8 @@ struct RankChannel {
   int pos, ringIx;
   HostConn* out;
   HostConn* in;
+  RingWalk<int64_t> w;  // the element's geometry (ring_walk.h)
+  int64_t parts;        // chunks per loop
   int64_t stepSize;
   const char* input;
   char* output;
@@ -205,7 +204,10 @@ struct RankChannel {
     ringIx = (pos - pos0 + n) % n;
     out = &(*c->conns)[ch * n + rank];
     in = &(*c->conns)[ch * n + prev];
-    stepSize = c->buff_size / MCCS_BUFFER_SLOTS / (int64_t)c->es;
+    mccs::ring_walk<int64_t>(w, c->func, n, c->nch, (int)c->es, c->nthreads_ref, c->buff_size, (int64_t)c->count);
+    mccs::walk_guard(w);
+    parts = mccs::walk_parts<int64_t>(c->func, c->nch, n);
+    stepSize = w.stepSize;
     input = (const char*)c->send[rank];
     output = (char*)c->recv[rank];
     thread_local std::vector<char> tmp_store;  // this worker's staging slice, kept across calls
@@ -237,9 +239,8 @@ struct RankChannel {
   // genericOp: RECV/SEND/SRC(input)/DST(output) flags, two slices per call
   bool op(bool RECV, bool SEND, bool SRC, bool DST, int64_t srcIx, int64_t dstIx, int64_t nelem) {
     if (nelem < 0) nelem = 0;
-    int64_t sliceSize = stepSize * ALLREDUCE_SLICESTEPS;
-    const int64_t s = (nelem + 32 - 1) / 32 * 16;
-    sliceSize = s > sliceSize / 32 ? s : sliceSize / 32;
+    const int64_t sliceSize =
+        mccs::slice_size(nelem, stepSize, ALLREDUCE_SLICESTEPS, ALLREDUCE_CHUNKSTEPS / ALLREDUCE_SLICESTEPS);
     int64_t offset = 0;
     for (int slice = 0; slice < 2; ++slice) {
       int64_t real = nelem - offset;
@@ -275,34 +276,16 @@ struct RankChannel {
 
 // runRing of AllReduce (all_reduce.h:10-87)
 void walk_allreduce(RankChannel& k) {
-  const Ctx* c = k.c;
-  const int n = k.n, ch = k.ch, ringIx = k.ringIx;
-  const int64_t chunkSize = (int64_t)(int)(k.stepSize * ALLREDUCE_CHUNKSTEPS);
-  const int64_t size = (int64_t)c->count;
-  const int64_t loopSize = (int64_t)c->nch * n * chunkSize;
-  int64_t gran = (int64_t)(c->nthreads_ref - WARP_SIZE) * 8 / (int64_t)c->es;
-  if (gran < 1) gran = 1;
-  auto mod = [&](int r) { return r >= n ? r - n : r; };
-  for (int64_t g = 0; g < size; g += loopSize) {
-    int64_t rcs = (size - g + (int64_t)c->nch * n - 1) / ((int64_t)c->nch * n);
-    rcs = chunkSize < rcs ? chunkSize : rcs;
-    rcs = (int64_t)(int)((rcs + gran - 1) / gran * gran);
-    auto off = [&](int chunk) { return g + (int64_t)ch * n * rcs + (int64_t)chunk * rcs; };
-    auto ne = [&](int64_t o) { return rcs < size - o ? rcs : size - o; };
-    int chunk = mod(ringIx + n - 1);
-    if (!k.op(false, true, true, false, off(chunk), 0, ne(off(chunk)))) return;
-    for (int j = 2; j < n; ++j) {
-      chunk = mod(ringIx + n - j);
-      if (!k.op(true, true, true, false, off(chunk), 0, ne(off(chunk)))) return;
+  const RingWalk<int64_t>& w = k.w;
+  const int n = k.n;
+  for (int64_t g = 0; g < w.size; g += w.loopSize) {
+    const int64_t rcs = mccs::real_chunk_size(w, g, k.parts);
+    // call j: send, n-2 x recvReduceSend, recvReduceCopySend, n-2 x recvCopySend, recv
+    for (int j = 0; j < 2 * n - 1; ++j) {
+      const int64_t c = (int64_t)k.ch * n + mccs::allreduce_call_chunk(k.ringIx, n, j);
+      const int64_t off = mccs::allreduce_chunk_offset(g, c, rcs);
+      if (!k.op(j > 0, j < 2 * n - 2, j <= n - 1, j >= n - 1, off, off, mccs::chunk_nelem(w.size, off, rcs))) return;
     }
-    chunk = ringIx;
-    if (!k.op(true, true, true, true, off(chunk), off(chunk), ne(off(chunk)))) return;
-    for (int j = 1; j < n - 1; ++j) {
-      chunk = mod(ringIx + n - j);
-      if (!k.op(true, true, false, true, 0, off(chunk), ne(off(chunk)))) return;
-    }
-    chunk = mod(ringIx + 1);
-    if (!k.op(true, false, false, true, 0, off(chunk), ne(off(chunk)))) return;
   }
 }
 
@@ -310,19 +293,13 @@ void walk_allreduce(RankChannel& k) {
 // block; call j of a loop works on block userRanks[n-1-j], the last one
 // (recvReduceCopy) on the rank's own block, written at the chunk's offset.
 void walk_reduce_scatter(RankChannel& k) {
-  const Ctx* c = k.c;
+  const RingWalk<int64_t>& w = k.w;
   const int n = k.n;
-  const int64_t chunkSize = (int64_t)(int)(k.stepSize * ALLREDUCE_CHUNKSTEPS);
-  const int64_t size = (int64_t)c->count;
-  const int64_t loopSize = (int64_t)c->nch * chunkSize;
-  int64_t gran = (int64_t)(c->nthreads_ref - WARP_SIZE) * 8 / (int64_t)c->es;
-  if (gran < 1) gran = 1;
-  for (int64_t g = 0; g < size; g += loopSize) {
-    int64_t rcs = (size - g + c->nch - 1) / c->nch;
-    rcs = chunkSize < rcs ? chunkSize : rcs;
-    rcs = (int64_t)(int)((rcs + gran - 1) / gran * gran);
-    const int64_t chunkOffset = g + (int64_t)(int)(k.ch * rcs);
-    const int64_t nelem = rcs < size - chunkOffset ? rcs : size - chunkOffset;  // <= 0: empty calls
+  const int64_t size = w.size;
+  for (int64_t g = 0; g < size; g += w.loopSize) {
+    const int64_t rcs = mccs::real_chunk_size(w, g, k.parts);
+    const int64_t chunkOffset = mccs::block_chunk_offset(g, (int64_t)k.ch, rcs);
+    const int64_t nelem = mccs::chunk_nelem(size, chunkOffset, rcs);  // <= 0: empty calls
     auto src = [&](int j) { return chunkOffset + (int64_t)k.user_rank(n - 1 - j) * size; };
     if (!k.op(false, true, true, false, src(0), 0, nelem)) return;
     for (int j = 1; j < n - 1; ++j)
@@ -441,7 +418,7 @@ static mccsResult_t host_ring_run(int func, int nranks, const void* const* sendb
       op > mccsDevMin || nchannels < 1 || nchannels > MCCS_MAX_NCHANNELS || nthreads_ref <= WARP_SIZE ||
       buff_size < 8192 || buff_size % 8192)
     return mccsInvalidArgument;
-  const size_t es = esize(dtype);
+  const size_t es = (size_t)mccs::elem_bytes(dtype);
   if (nranks == 1) {
     if (recvbufs[0] != sendbufs[0]) std::memmove(recvbufs[0], sendbufs[0], count * es);
     return mccsSuccess;

@@ -26,6 +26,7 @@
 
 #include "comm.h"
 #include "dtypes.h"
+#include "ring_walk.h"
 
 namespace mccs {
 
@@ -546,18 +547,19 @@ static mccsResult_t build_direct(std::vector<Comm*>& comms, const std::vector<in
     const int pos0 = (int)(std::find(ring.begin(), ring.end(), 0) - ring.begin());
     for (int k = 0; k < n; ++k) da->idx2rank[bid][k] = (uint8_t)ring[(pos0 + k) % n];
   }
-  // elements each rank owns: the ring walk (all_reduce.h:28-42), chunk k of
-  // channel bid owned by the rank at ring index k (AllGather: unused)
+  // elements each rank owns: the walk the kernel takes (ring_walk.h, in the
+  // kernel's 32 bits), chunk k of channel bid owned by the rank at ring index
+  // k (AllGather: unused)
   if (!gather) {
-    const int64_t size = (int64_t)da->count, parts = (int64_t)da->nch * n;
-    const int64_t chunk = (int64_t)((int)da->buff_size / MCCS_BUFFER_SLOTS / (int)esize) * ALLREDUCE_CHUNKSTEPS;
-    const int64_t gran = std::max<int64_t>(1, (int64_t)(nthr - WARP_SIZE) * 8 / (int64_t)esize);
-    for (int64_t g = 0; g < size; g += parts * chunk) {
-      int64_t rcs = std::min(chunk, (size - g + parts - 1) / parts);
-      rcs = (rcs + gran - 1) / gran * gran;
-      for (int64_t c = 0; c < parts; ++c) {
-        const int64_t off = g + c * rcs;
-        if (off < size) da->owned[da->idx2rank[c / n][c % n]] += (uint64_t)std::min(rcs, size - off);
+    RingWalk<uint32_t> w;
+    ring_walk<uint32_t>(w, mccsFuncAllReduce, n, nsel, (int)esize, nthr, (int)da->buff_size, (uint32_t)da->count);
+    walk_guard(w);
+    const uint32_t parts = walk_parts<uint32_t>(mccsFuncAllReduce, nsel, n);
+    for (uint32_t g = 0; g < w.size; g += w.loopSize) {
+      const uint32_t rcs = real_chunk_size(w, g, parts);
+      for (uint32_t c = 0; c < parts; ++c) {
+        const uint32_t off = allreduce_chunk_offset(g, c, rcs);
+        if (off < w.size) da->owned[da->idx2rank[c / n][c % n]] += chunk_nelem(w.size, off, rcs);
       }
     }
   }

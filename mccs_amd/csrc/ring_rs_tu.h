@@ -10,17 +10,11 @@
   case DT:                             \
     return (const void*)&ring_multi_kernel<mccsFuncReduceScatter, DT, OPV>;
 
-#define MCCS_RS_TYPES(X, OPN, OPV)                                                                  \
-  X(OPN, OPV, int8_t, mccsInt8) X(OPN, OPV, uint8_t, mccsUint8) X(OPN, OPV, int32_t, mccsInt32)    \
-  X(OPN, OPV, uint32_t, mccsUint32) X(OPN, OPV, int64_t, mccsInt64) X(OPN, OPV, uint64_t, mccsUint64) \
-  X(OPN, OPV, half, mccsFloat16) X(OPN, OPV, float, mccsFloat32) X(OPN, OPV, double, mccsFloat64)  \
-  X(OPN, OPV, bfloat16, mccsBfloat16)
-
 // Defines mccs::ring_rs_kernel_<OPN>(dtype), which instantiates the kernels.
 #define MCCS_RS_TU(OPN, OPV)                                     \
   namespace mccs {                                               \
   const void* ring_rs_kernel_##OPN(int dtype) {                  \
-    switch (dtype) { MCCS_RS_TYPES(MCCS_RS_CASE, OPN, OPV) }     \
+    switch (dtype) { MCCS_RING_TYPES(MCCS_RS_CASE, OPN, OPV) }   \
     return nullptr;                                              \
   }                                                              \
   }

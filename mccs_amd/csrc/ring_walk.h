@@ -1,0 +1,133 @@
+// ring_walk.h — the ring chunk walk, stated once.
+//
+// Every path that produces an AllReduce, AllGather or ReduceScatter result
+// cuts the buffer into the same chunks: the ring kernels (ring_kernel.h), the
+// direct and LL kernels (direct_kernel.h), the planner's owned[] counts
+// (host/plan.cpp build_direct) and the host-thread ring (host/host_ring.cpp).
+// They all take the arithmetic from here, so "the ring's result, bit for bit"
+// cannot drift between them.  mccs_ring_walk (host/api.cpp) prints the walk
+// for tests/test_ring_walk.py, which holds it to the Python models.
+//
+// I is the integer type of the walk: int64_t for the ring and the host
+// paths, uint32_t for the direct kernels (direct_kernel.h says why).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mccs_devcomm.h"
+
+namespace mccs {
+
+template <typename I>
+__host__ __device__ __forceinline__ I div_up(I a, I b) {
+  return (a + b - 1) / b;
+}
+template <typename I>
+__host__ __device__ __forceinline__ I round_up(I a, I b) {
+  return div_up(a, b) * b;
+}
+
+// Geometry of one work element, in elements of `esize` bytes.  The number of
+// parts (chunks) per loop is not kept: walk_parts gives it.
+template <typename I>
+struct RingWalk {
+  I size;       // AllReduce: the buffer; AllGather / ReduceScatter: one rank's block
+  I stepSize;   // one FIFO step
+  I chunkSize;  // the largest chunk
+  I loopSize;   // what one loop of all channels covers
+  I gran;       // realChunkSize is a multiple of this
+};
+
+// Chunks per loop: AllReduce cuts a loop into a chunk per channel and rank,
+// the block collectives into one per channel.
+template <typename I>
+__host__ __device__ __forceinline__ I walk_parts(int func, I nChannels, int nranks) {
+  return func == mccsFuncAllReduce ? nChannels * nranks : nChannels;
+}
+
+// all_reduce.h:17-21,30 / all_gather.h:16-20,30.  func is mccsFuncAllReduce,
+// mccsFuncAllGather (esize = 1: the int8 kernel counts bytes) or
+// mccsFuncReduceScatter (a block split over the channels like AllGather's, in
+// AllReduce's element granule).  nthreads_ref is the
+// reference's thread count (nWarps * WARP_SIZE), buff_size the FIFO's bytes.
+// The reference holds chunkSize in an int: the (int) here and the ones in
+// real_chunk_size / block_chunk_offset are its truncations.
+// Fills w in place (the ring kernel's lives in LDS); walk_guard completes it.
+template <typename I>
+__host__ __device__ __forceinline__ void ring_walk(RingWalk<I>& w, int func, int nranks, int nChannels, int esize,
+                                                   int nthreads_ref, int buff_size, I size) {
+  static_assert(ALLGATHER_CHUNKSTEPS == ALLREDUCE_CHUNKSTEPS, "one chunkSize for the three functions");
+  w.stepSize = (I)(buff_size / MCCS_BUFFER_SLOTS / esize);
+  w.size = size;
+  w.chunkSize = (I)(int)(w.stepSize * ALLREDUCE_CHUNKSTEPS);
+  if constexpr (sizeof(I) == 4) {
+    // 32 bits hold a bucket of < 2^31 elements, not every loopSize: one at or
+    // above the bucket's size means a single loop whatever its value
+    const uint64_t loop = walk_parts(func, (uint64_t)nChannels, nranks) * w.chunkSize;
+    w.loopSize = loop > 0x7fffffffu ? 0x7fffffffu : (I)loop;
+  } else {
+    w.loopSize = walk_parts(func, (I)nChannels, nranks) * w.chunkSize;
+  }
+  w.gran = (I)(nthreads_ref - WARP_SIZE) * 8 / (I)esize;
+}
+
+// A work element of fewer than two reference warps, which no host path sends,
+// has no granule: 1 keeps the walk's divisions defined.  Apart from ring_walk
+// because the ring kernel applies it after the rest of its schedule: next to
+// the store of gran the compiler folds the two into a select, which moved
+// registers and spills in most ring kernels (tools/kernel_resources.py --diff).
+template <typename I>
+__host__ __device__ __forceinline__ void walk_guard(RingWalk<I>& w) {
+  if (w.gran < 1) w.gran = 1;
+}
+
+// realChunkSize of the loop at gridOffset (all_reduce.h:31-36, all_gather.h:
+// 31-35): what is left over the loop's parts, at most chunkSize, rounded up
+// to the granule.
+template <typename I>
+__host__ __device__ __forceinline__ I real_chunk_size(const RingWalk<I>& w, I gridOffset, I parts) {
+  I rcs = div_up(w.size - gridOffset, parts);
+  rcs = w.chunkSize < rcs ? w.chunkSize : rcs;
+  return (I)(int)round_up(rcs, w.gran);
+}
+
+// AllReduce: chunk `chunk` (a ring index) of channel bid is part bid * nranks
+// + chunk of the loop (all_reduce.h:38-42); the second form takes the part.
+template <typename I>
+__host__ __device__ __forceinline__ I allreduce_chunk_offset(I gridOffset, I bid, int nranks, int chunk, I rcs) {
+  return gridOffset + bid * nranks * rcs + (I)chunk * rcs;
+}
+template <typename I>
+__host__ __device__ __forceinline__ I allreduce_chunk_offset(I gridOffset, I part, I rcs) {
+  return gridOffset + part * rcs;
+}
+// AllGather / ReduceScatter: channel bid's chunk of the block (all_gather.h:36).
+template <typename I>
+__host__ __device__ __forceinline__ I block_chunk_offset(I gridOffset, I bid, I rcs) {
+  return gridOffset + (I)(int)(bid * rcs);
+}
+// Elements of the chunk at `off` (all_reduce.h:42, all_gather.h:37).  Signed
+// I: <= 0 past the end, an empty call that still takes and posts its steps.
+template <typename I>
+__host__ __device__ __forceinline__ I chunk_nelem(I size, I off, I rcs) {
+  return rcs < size - off ? rcs : size - off;
+}
+
+// AllReduce: the chunk primitive call j = 0 .. 2n-2 of a loop works on, for
+// the rank at ring index ringIx (all_reduce.h:46-84: send ringIx+n-1, the
+// reduce calls down to ringIx, the copy calls from ringIx+n-1 down to ringIx+1).
+__host__ __device__ __forceinline__ int allreduce_call_chunk(int ringIx, int n, int j) {
+  const int chunk = j <= n - 1 ? ringIx + n - 1 - j : ringIx + 2 * n - 1 - j;
+  return chunk >= n ? chunk - n : chunk;
+}
+
+// Slice size of a primitive call of nelem elements (prims_simple.h:156-157):
+// sps steps per slice, spc slices per call.
+template <typename I>
+__host__ __device__ __forceinline__ I slice_size(I nelem, I stepSize, int sps, int spc) {
+  const I sliceSize = (nelem + 16 * (I)spc - 1) / (16 * (I)spc) * 16;
+  const I span = stepSize * sps;
+  return sliceSize > span / 32 ? sliceSize : span / 32;
+}
+
+}  // namespace mccs
