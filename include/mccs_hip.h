@@ -250,6 +250,49 @@ mccsResult_t mccsAllGather(const void *sendbuff, void *recvbuff, size_t sendbyte
  * local copy. */
 mccsResult_t mccsReduceScatter(const void *sendbuff, void *recvbuff, size_t recvcount, int dtype, int op,
                                mccsComm_t comm, hipStream_t stream);
+/* Ring Broadcast and Reduce, the two rooted collectives.  Not in the
+ * reference: it declares the functions (mccsFuncBoadcast = 0, sic, and
+ * mccsFuncReduce = 1, src/collectives/include/devcomm.h:11-12) and carries
+ * mccsDevWorkElem.root, but ships no kernel for either.
+ * mccsBroadcast is byte-typed like mccsAllGather: every rank's
+ * recvbuff[0, nbytes) becomes the root's sendbuff[0, nbytes).  sendbuff is
+ * read on the root only; elsewhere it may be NULL and is never dereferenced.
+ * In place on the root means recvbuff == sendbuff; out of place the root's
+ * recvbuff is written too and its sendbuff is never written.
+ * mccsReduce: dtype any mccsDevDataType_t, op mccsDevSum / Prod / Max / Min.
+ * The root's recvbuff[0, count) receives the reduction over all ranks of
+ * sendbuff[0, count); recvbuff is neither read nor written on the other ranks
+ * and may be NULL there.  In place on the root, recvbuff == sendbuff, is
+ * supported; no other overlap is.  On a channel the value is acc = x[s1], then
+ * acc = fn(x[sk], acc) for k = 2..n, each hop rounded in dtype, where s1..sn
+ * are the successors of root along that channel's ring and sn = root: the
+ * operand order mccsReduceScatter has for block `root`, and the AllReduce
+ * ring's.  Which channel an element belongs to follows the ring walk of the
+ * whole buffer cut like a block.
+ * Both are a chain along each channel's ring, from the root (Broadcast) or to
+ * it (Reduce); the connection between the chain's two ends carries nothing, so
+ * after a rooted call the communicator's connections stand at different FIFO
+ * steps (each connection's two ends still agree).
+ * Otherwise as for mccsReduceScatter: stream-ordered, returns after launch; a
+ * communicator's collectives run in issue order whatever stream each is issued
+ * on; every launch takes the communicator's launch guard; several calls of one
+ * function, dtype and op on one comm in one group are batched into one launch,
+ * and their roots may differ (the root is per work element); mixing functions,
+ * dtypes or ops on one comm in a group is refused with mccsInvalidUsage at
+ * mccsGroupEnd; ranks sharing a GPU run as one fused launch; the call may be
+ * captured into a HIP graph; the watchdog and mccsCommAbort end a stuck
+ * kernel.  Always the ring (mccsCommLastAlgo reports MCCS_ALGO_RING), whatever
+ * the size.  nbytes / count == 0 succeeds and launches nothing; a root outside
+ * [0, nranks) is refused with mccsInvalidArgument (mccsGetLastErrorString names
+ * it), as are an unknown dtype or op and a NULL buffer where the rank's role
+ * uses it; nranks == 1 is a local copy.  Every rank must name the same root:
+ * ranks that disagree stall until the watchdog (mccsTimeout from
+ * mccsCommSync); this is not detected earlier.  Nothing outside
+ * [recvbuff, recvbuff + size) is written on any rank. */
+mccsResult_t mccsBroadcast(const void *sendbuff, void *recvbuff, size_t nbytes, int root, mccsComm_t comm,
+                           hipStream_t stream);
+mccsResult_t mccsReduce(const void *sendbuff, void *recvbuff, size_t count, int dtype, int op, int root,
+                        mccsComm_t comm, hipStream_t stream);
 /* Group calls (ProxyCommand::GroupCall): collectives issued between Start and
  * End are planned together and launched at End (one launch per device). */
 mccsResult_t mccsGroupStart(void);
@@ -378,6 +421,15 @@ mccsResult_t mccs_host_ring_allreduce(int nranks, const void *const *sendbufs, v
 mccsResult_t mccs_host_ring_reduce_scatter(int nranks, const void *const *sendbufs, void *const *recvbufs,
                                            size_t recvcount, int dtype, int op, int nchannels, int nthreads_ref,
                                            int buff_size, const int *rings);
+/* The ring Broadcast and Reduce schedules (mccsBroadcast, mccsReduce) and the
+ * FIFO protocol on host threads over host memory.  Buffers as for the device
+ * calls: sendbufs[r] of a Broadcast may be NULL for r != root, recvbufs[r] of
+ * a Reduce for r != root. */
+mccsResult_t mccs_host_ring_broadcast(int nranks, const void *const *sendbufs, void *const *recvbufs, size_t nbytes,
+                                      int root, int nchannels, int nthreads_ref, int buff_size, const int *rings);
+mccsResult_t mccs_host_ring_reduce(int nranks, const void *const *sendbufs, void *const *recvbufs, size_t count,
+                                   int dtype, int op, int root, int nchannels, int nthreads_ref, int buff_size,
+                                   const int *rings);
 /* Default ring orders for an n-rank node (edge-disjoint Hamiltonian cycles,
  * both directions); writes up to max_channels x nranks ints, returns count. */
 int mccs_default_rings(int nranks, int nch_req, int *out, int max_channels);

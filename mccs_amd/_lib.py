@@ -105,6 +105,8 @@ SIGNATURES: dict[str, tuple] = {
     "mccsAllReduce": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_int, _c_void_p, _c_void_p]),
     "mccsAllGather": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_void_p]),
     "mccsReduceScatter": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_int, _c_void_p, _c_void_p]),
+    "mccsBroadcast": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_void_p, _c_void_p]),
+    "mccsReduce": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),
     "mccsGroupStart": (_c_int, []),
     "mccsGroupEnd": (_c_int, []),
     "mccsCommSync": (_c_int, [_c_void_p]),
@@ -145,6 +147,11 @@ SIGNATURES: dict[str, tuple] = {
                  _P(_c_int)]),
     "mccs_host_ring_reduce_scatter": (
         _c_int, [_c_int, _P(_c_void_p), _P(_c_void_p), _c_size_t, _c_int, _c_int, _c_int, _c_int, _c_int,
+                 _P(_c_int)]),
+    "mccs_host_ring_broadcast": (
+        _c_int, [_c_int, _P(_c_void_p), _P(_c_void_p), _c_size_t, _c_int, _c_int, _c_int, _c_int, _P(_c_int)]),
+    "mccs_host_ring_reduce": (
+        _c_int, [_c_int, _P(_c_void_p), _P(_c_void_p), _c_size_t, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
                  _P(_c_int)]),
 }
 

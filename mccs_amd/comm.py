@@ -10,6 +10,8 @@ Mirrors the reference application API (src/libmccs/src/lib.rs:19-27):
   all_gather(comm, send, recv, size, stream)    all_gather(comm, send, recv, size, stream)
   (none: ReduceScatter is declared but          reduce_scatter(comm, send, recv, recv_count, dtype,
    unimplemented, task.rs:95-102)                              op, stream)
+  (none: Broadcast and Reduce are declared,     broadcast(comm, send, recv, nbytes, root, stream)
+   devcomm.h:11-12, and have no kernel)         reduce(comm, send, recv, count, dtype, op, root, stream)
   AllReduceDataType {Float16, Int32}            AllReduceDataType (+ Float32: the one API delta,
                                                 SURVEY §8(b); + the other kernel dtypes)
   AllReduceOpType {Sum, Prod, ...}              AllReduceOpType
@@ -113,6 +115,8 @@ def _sig():
 
 
 def _ptr(x) -> int:
+    if x is None:  # the buffer a rooted collective's role does not use
+        return 0
     return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
 
 
@@ -194,6 +198,13 @@ class Communicator:
     def reduce_scatter(self, send_buf, recv_buf, recv_count: int, data_type=AllReduceDataType.Float32,
                        op_type=AllReduceOpType.Sum, stream=None) -> None:
         reduce_scatter(self, send_buf, recv_buf, recv_count, data_type, op_type, stream)
+
+    def broadcast(self, send_buf, recv_buf, nbytes: int, root: int, stream=None) -> None:
+        broadcast(self, send_buf, recv_buf, nbytes, root, stream)
+
+    def reduce(self, send_buf, recv_buf, count: int, data_type=AllReduceDataType.Float32,
+               op_type=AllReduceOpType.Sum, root: int = 0, stream=None) -> None:
+        reduce(self, send_buf, recv_buf, count, data_type, op_type, root, stream)
 
     def sync(self) -> None:
         """Waits for the comm's launches; raises on a device-side timeout/abort."""
@@ -292,6 +303,24 @@ def reduce_scatter(comm: Communicator, send_buf, recv_buf, recv_count: int, data
     _lib.check(rc, "mccsReduceScatter")
 
 
+def broadcast(comm: Communicator, send_buf, recv_buf, nbytes: int, root: int, stream=None) -> None:
+    """mccsBroadcast: every rank's recv[0, nbytes) becomes the root's
+    send[0, nbytes).  send is read on the root only (None elsewhere); in place
+    on the root is recv == send.  Always the ring; stream-ordered."""
+    rc = _sig().mccsBroadcast(_ptr(send_buf), _ptr(recv_buf), int(nbytes), int(root), comm._h, _stream(stream))
+    _lib.check(rc, "mccsBroadcast")
+
+
+def reduce(comm: Communicator, send_buf, recv_buf, count: int, data_type=AllReduceDataType.Float32,
+           op_type=AllReduceOpType.Sum, root: int = 0, stream=None) -> None:
+    """mccsReduce: the root's recv[0, count) gets the reduction of every rank's
+    send[0, count).  recv is used on the root only (None elsewhere); in place on
+    the root is recv == send.  Always the ring; stream-ordered."""
+    rc = _sig().mccsReduce(_ptr(send_buf), _ptr(recv_buf), int(count), int(data_type), int(op_type), int(root),
+                           comm._h, _stream(stream))
+    _lib.check(rc, "mccsReduce")
+
+
 @contextlib.contextmanager
 def group():
     """ProxyCommand::GroupCall: collectives inside are launched together at exit."""
@@ -345,6 +374,37 @@ def host_ring_reduce_scatter(sendbufs, recvbufs, recv_count: int, data_type, op_
     _lib.check(rc, "mccs_host_ring_reduce_scatter")
 
 
+def _host_ptrs(bufs):
+    arr = ctypes.c_void_p * max(1, len(bufs))
+    return arr(*[None if x is None else x.ctypes.data if hasattr(x, "ctypes") else int(x) for x in bufs])
+
+
+def host_ring_broadcast(sendbufs, recvbufs, nbytes: int, root: int, channels: int = 1, nthreads: int = 96,
+                        buffer_size: int = 1 << 22, rings=None) -> None:
+    """The ring Broadcast schedule on host threads over host memory (numpy
+    arrays or raw host pointers; no GPU).  sendbufs[r] may be None for r != root."""
+    ro = None
+    if rings is not None:
+        flat = [int(v) for r in rings for v in r]
+        ro = (_ci * len(flat))(*flat)
+    rc = _sig().mccs_host_ring_broadcast(len(sendbufs), _host_ptrs(sendbufs), _host_ptrs(recvbufs), int(nbytes),
+                                         int(root), channels, nthreads, buffer_size, ro)
+    _lib.check(rc, "mccs_host_ring_broadcast")
+
+
+def host_ring_reduce(sendbufs, recvbufs, count: int, data_type, op_type=AllReduceOpType.Sum, root: int = 0,
+                     channels: int = 1, nthreads: int = 96, buffer_size: int = 1 << 22, rings=None) -> None:
+    """The ring Reduce schedule on host threads over host memory (numpy arrays
+    or raw host pointers; no GPU).  recvbufs[r] may be None for r != root."""
+    ro = None
+    if rings is not None:
+        flat = [int(v) for r in rings for v in r]
+        ro = (_ci * len(flat))(*flat)
+    rc = _sig().mccs_host_ring_reduce(len(sendbufs), _host_ptrs(sendbufs), _host_ptrs(recvbufs), int(count),
+                                      int(data_type), int(op_type), int(root), channels, nthreads, buffer_size, ro)
+    _lib.check(rc, "mccs_host_ring_reduce")
+
+
 def ring_profile(device: int = 0, reset: bool = True) -> dict:
     """Per-slice timing of the ring kernels on `device` (MCCS_RING_PROFILE=1
     set before communicator init): slices, mean µs waiting for peer flags,
@@ -376,7 +436,8 @@ def task_schema(total_bytes: int, channels: int) -> tuple[int, int]:
     return a.value, b.value
 
 
-FUNC_ALLGATHER, FUNC_REDUCE_SCATTER, FUNC_ALLREDUCE = 2, 3, 4  # mccsDevFunc_t (include/mccs_devcomm.h)
+# mccsDevFunc_t (include/mccs_devcomm.h)
+FUNC_BROADCAST, FUNC_REDUCE, FUNC_ALLGATHER, FUNC_REDUCE_SCATTER, FUNC_ALLREDUCE = 0, 1, 2, 3, 4
 
 
 def ring_walk(func: int, nranks: int, channels: int, elem_bytes: int, nthreads: int, buffer_size: int, count: int,
@@ -396,7 +457,9 @@ def ring_walk(func: int, nranks: int, channels: int, elem_bytes: int, nthreads: 
 
 
 __all__ = ["AllReduceDataType", "AllReduceOpType", "CommConfig", "Communicator", "init_all",
-           "init_communicator_rank", "all_reduce", "all_gather", "reduce_scatter", "group", "default_rings", "task_schema",
+           "init_communicator_rank", "all_reduce", "all_gather", "reduce_scatter", "broadcast", "reduce",
+           "group", "default_rings", "task_schema",
            "direct_defaults", "ll_default", "ring_walk",
-           "host_ring_allreduce", "host_ring_reduce_scatter", "ring_profile",
+           "host_ring_allreduce", "host_ring_reduce_scatter", "host_ring_broadcast", "host_ring_reduce", "ring_profile",
+           "FUNC_BROADCAST", "FUNC_REDUCE", "FUNC_ALLGATHER", "FUNC_REDUCE_SCATTER", "FUNC_ALLREDUCE",
            "RedOp", "DataType"]

@@ -186,7 +186,7 @@ static mccsResult_t enable_peer(int a, int b) {
 }
 
 static mccsResult_t launch_single(Comm* c, int func, int dtype, int op, const void* send, void* recv, size_t count,
-                                  hipStream_t stream) {
+                                  hipStream_t stream, int root = 0) {
   // inside a group the diagnosis of a rejected call must survive to GroupEnd
   // (the group was cleared at GroupStart)
   if (g_group.depth == 0) err_clear();
@@ -199,12 +199,24 @@ static mccsResult_t launch_single(Comm* c, int func, int dtype, int op, const vo
   if (!c || !c->connected) return reject(mccsInvalidUsage, "the communicator is not connected");
   if (c->failed) return reject(mccsRemoteError, "the communicator failed earlier (watchdog or abort): destroy it");
   if (count == 0) return mccsSuccess;
-  if (!send || !recv) return reject(mccsInvalidArgument, "null send or recv buffer");
-  if ((func == mccsFuncAllReduce || func == mccsFuncReduceScatter) &&
+  const bool rooted = func == mccsFuncBoadcast || func == mccsFuncReduce;
+  if (rooted && (root < 0 || root >= c->nranks)) {
+    char why[96];
+    std::snprintf(why, sizeof(why), "root %d outside 0..%d", root, c->nranks - 1);
+    return reject(mccsInvalidArgument, why);
+  }
+  // a rooted call's buffers are needed where the rank's role uses them:
+  // Broadcast reads sendbuff on the root only, Reduce writes recvbuff there only
+  const bool need_send = func != mccsFuncBoadcast || c->rank == root;
+  const bool need_recv = func != mccsFuncReduce || c->rank == root;
+  if ((need_send && !send) || (need_recv && !recv)) return reject(mccsInvalidArgument, "null send or recv buffer");
+  if ((func == mccsFuncAllReduce || func == mccsFuncReduceScatter || func == mccsFuncReduce) &&
       (dtype < 0 || dtype >= mccsNumTypes || op < 0 || op > mccsDevMin))
     return reject(mccsInvalidArgument, "unknown dtype or reduction op");
   const char* const name = func == mccsFuncAllGather       ? "mccsAllGather"
                            : func == mccsFuncReduceScatter ? "mccsReduceScatter"
+                           : func == mccsFuncBoadcast      ? "mccsBroadcast"
+                           : func == mccsFuncReduce        ? "mccsReduce"
                                                            : "mccsAllReduce";
   if (std::find(g_group.comms.begin(), g_group.comms.end(), c) == g_group.comms.end()) {
     g_group.comms.push_back(c);
@@ -213,7 +225,7 @@ static mccsResult_t launch_single(Comm* c, int func, int dtype, int op, const vo
   mccsResult_t er;
   {
     StepScope st(name);
-    er = plan_enqueue(c, func, dtype, op, send, recv, count);
+    er = plan_enqueue(c, func, dtype, op, send, recv, count, rooted ? root : 0);
   }
   if (er != mccsSuccess) {
     if (g_group.depth == 0) group_discard();
@@ -597,6 +609,16 @@ extern "C" mccsResult_t mccsAllGather(const void* sendbuff, void* recvbuff, size
 extern "C" mccsResult_t mccsReduceScatter(const void* sendbuff, void* recvbuff, size_t recvcount, int dtype, int op,
                                           mccsComm_t comm, hipStream_t stream) {
   return launch_single((Comm*)comm, mccsFuncReduceScatter, dtype, op, sendbuff, recvbuff, recvcount, stream);
+}
+
+extern "C" mccsResult_t mccsBroadcast(const void* sendbuff, void* recvbuff, size_t nbytes, int root, mccsComm_t comm,
+                                      hipStream_t stream) {
+  return launch_single((Comm*)comm, mccsFuncBoadcast, mccsInt8, mccsDevSum, sendbuff, recvbuff, nbytes, stream, root);
+}
+
+extern "C" mccsResult_t mccsReduce(const void* sendbuff, void* recvbuff, size_t count, int dtype, int op, int root,
+                                   mccsComm_t comm, hipStream_t stream) {
+  return launch_single((Comm*)comm, mccsFuncReduce, dtype, op, sendbuff, recvbuff, count, stream, root);
 }
 
 extern "C" mccsResult_t mccsGroupStart(void) {

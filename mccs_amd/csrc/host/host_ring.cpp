@@ -13,7 +13,9 @@
 // a fallback for the device path (nothing on the device path calls it).
 // mccs_host_ring_reduce_scatter runs the ring ReduceScatter schedule
 // (ring_kernel.h; not in the reference) through the same primitive, so the
-// device walk has a second implementation that runs without a GPU.
+// device walk has a second implementation that runs without a GPU;
+// mccs_host_ring_broadcast / mccs_host_ring_reduce do the same for the rooted
+// chains.
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -164,7 +166,7 @@ struct HostConn {  // one directed FIFO (rank -> next) of one channel
 };
 
 struct Ctx {
-  int func, n, nch, dt, op, nthreads_ref, buff_size;
+  int func, n, nch, dt, op, nthreads_ref, buff_size, root;
   size_t es, count;
   const void* const* send;
   void* const* recv;
@@ -308,10 +310,38 @@ void walk_reduce_scatter(RankChannel& k) {
   }
 }
 
+// Ring Broadcast and Reduce (ring_kernel.h): the whole buffer
+// cut like a block, one call per loop whose kind is the rank's role on the
+// chain: d is the root's distance ahead of the rank along the ring.
+void walk_rooted(RankChannel& k) {
+  const RingWalk<int64_t>& w = k.w;
+  const int n = k.n;
+  int d = 0;
+  while (d < n - 1 && k.user_rank(d) != k.c->root) ++d;
+  bool RECV, SEND, SRC, DST;
+  if (k.c->func == mccsFuncBoadcast) {
+    RECV = d != 0;               // root: send / copySend
+    SEND = d != 1;               // the rank whose next is the root: recv
+    SRC = d == 0;
+    DST = d != 0 || k.input != k.output;
+  } else {
+    RECV = d != n - 1;           // first after the root: send
+    SEND = d != 0;               // root: recvReduceCopy
+    SRC = true;
+    DST = d == 0;
+  }
+  for (int64_t g = 0; g < w.size; g += w.loopSize) {
+    const int64_t rcs = mccs::real_chunk_size(w, g, k.parts);
+    const int64_t off = mccs::block_chunk_offset(g, (int64_t)k.ch, rcs);
+    if (!k.op(RECV, SEND, SRC, DST, off, off, mccs::chunk_nelem(w.size, off, rcs))) return;
+  }
+}
+
 // one (rank, channel) thread
 void run_rank_channel(Ctx* c, int rank, int ch) {
   RankChannel k(c, rank, ch);
   if (c->func == mccsFuncReduceScatter) walk_reduce_scatter(k);
+  else if (c->func == mccsFuncBoadcast || c->func == mccsFuncReduce) walk_rooted(k);
   else walk_allreduce(k);
 }
 
@@ -413,7 +443,8 @@ class HostRingPool {
 
 static mccsResult_t host_ring_run(int func, int nranks, const void* const* sendbufs, void* const* recvbufs,
                                   size_t count, int dtype, int op, int nchannels, int nthreads_ref, int buff_size,
-                                  const int* rings) {
+                                  const int* rings, int root = 0) {
+  if (root < 0 || root >= nranks) return mccsInvalidArgument;
   if (nranks < 1 || nranks > 64 || !sendbufs || !recvbufs || dtype < 0 || dtype >= mccsNumTypes || op < 0 ||
       op > mccsDevMin || nchannels < 1 || nchannels > MCCS_MAX_NCHANNELS || nthreads_ref <= WARP_SIZE ||
       buff_size < 8192 || buff_size % 8192)
@@ -439,6 +470,7 @@ static mccsResult_t host_ring_run(int func, int nranks, const void* const* sendb
   c.send = sendbufs;
   c.recv = recvbufs;
   c.rings = rings;
+  c.root = root;
   c.conns = &conns;
   c.timeout_s = 60.0;
   pool.run(&c, nranks * nchannels);
@@ -457,4 +489,18 @@ extern "C" mccsResult_t mccs_host_ring_reduce_scatter(int nranks, const void* co
                                                       int nthreads_ref, int buff_size, const int* rings) {
   return host_ring_run(mccsFuncReduceScatter, nranks, sendbufs, recvbufs, recvcount, dtype, op, nchannels,
                        nthreads_ref, buff_size, rings);
+}
+
+extern "C" mccsResult_t mccs_host_ring_broadcast(int nranks, const void* const* sendbufs, void* const* recvbufs,
+                                                 size_t nbytes, int root, int nchannels, int nthreads_ref,
+                                                 int buff_size, const int* rings) {
+  return host_ring_run(mccsFuncBoadcast, nranks, sendbufs, recvbufs, nbytes, mccsInt8, mccsDevSum, nchannels,
+                       nthreads_ref, buff_size, rings, root);
+}
+
+extern "C" mccsResult_t mccs_host_ring_reduce(int nranks, const void* const* sendbufs, void* const* recvbufs,
+                                              size_t count, int dtype, int op, int root, int nchannels,
+                                              int nthreads_ref, int buff_size, const int* rings) {
+  return host_ring_run(mccsFuncReduce, nranks, sendbufs, recvbufs, count, dtype, op, nchannels, nthreads_ref,
+                       buff_size, rings, root);
 }

@@ -78,10 +78,12 @@ static void enqueue_elem(ChannelSchedule& s, const WorkElemHost& e, int func_ind
   w.func = func_index;
 }
 
-static mccsResult_t ring_enqueue(Comm* c, int func, int dtype, int op, const void* send, void* recv, size_t count) {
+static mccsResult_t ring_enqueue(Comm* c, int func, int dtype, int op, const void* send, void* recv, size_t count,
+                                 int root = 0) {
   const size_t esize = (size_t)elem_bytes(dtype);
   // task.rs:95-102.  ReduceScatter (not in the reference: task.rs stops at unimplemented!()) counts
-  // like AllGather, the bytes that enter the ring: count is elements per block
+  // like AllGather, the bytes that enter the ring: count is elements per block.  Broadcast (the int8
+  // kernel: count is bytes) and Reduce count the buffer's bytes, like AllReduce
   const size_t total = func == mccsFuncAllGather       ? count * c->nranks
                        : func == mccsFuncReduceScatter ? count * esize * c->nranks
                                                        : count * esize;
@@ -97,6 +99,7 @@ static mccsResult_t ring_enqueue(Comm* c, int func, int dtype, int op, const voi
     e.count = count;
     e.bid = (uint8_t)bid;
     e.nChannels = (uint8_t)nsel;
+    e.root = (uint32_t)root;
     enqueue_elem(c->sched[chans[bid]], e, /*funcIndex, unused (plan.rs:585)*/ 0,
                  func == mccsFuncAllGather ? 1 : esize);
   }
@@ -129,7 +132,8 @@ static bool ll_fits(const Comm* c, size_t bytes) {
          bytes <= (size_t)c->cfg.ll_bytes && 2 * ((bytes + 7) & ~(size_t)7) <= c->layout.ll_slot;
 }
 
-mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send, void* recv, size_t count) {
+mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send, void* recv, size_t count,
+                          int root) {
   if (c->plan_pending && (c->plan_func != func || c->plan_dtype != dtype || c->plan_op != op))
     // pre_launch_schedule batches same func/dtype/op only (plan.rs:122-141)
     MCCS_FAIL(mccsInvalidUsage, "a group mixes collectives of different function / dtype / op on one communicator");
@@ -144,8 +148,9 @@ mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send
   const bool twoshot = func == mccsFuncAllReduce && c->layout.direct_slot > 0 && bytes <= (size_t)c->cfg.direct_bytes;
   const bool ll = ll_fits(c, bytes);
   // (the LL one-shot makes no remote atomics: it runs without peer atomics,
-  // the count-based variants need them).  A ReduceScatter always takes the
-  // ring: the direct variants are AllReduce / AllGather only.
+  // the count-based variants need them).  A ReduceScatter, Broadcast or
+  // Reduce always takes the ring: the direct variants are AllReduce /
+  // AllGather only.
   if (!c->plan_pending && (func == mccsFuncAllReduce || func == mccsFuncAllGather) &&
       ((c->direct_ok && (oneshot || twoshot)) || ll)) {
     c->plan_direct = true;
@@ -158,7 +163,7 @@ mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send
     c->plan_op = op;
     return mccsSuccess;
   }
-  return ring_enqueue(c, func, dtype, op, send, recv, count);
+  return ring_enqueue(c, func, dtype, op, send, recv, count, root);
 }
 
 static mccsDevWork to_dev_work(const HostWork& elems, bool in_fifo, bool is_last, uint32_t u) {
@@ -171,7 +176,7 @@ static mccsDevWork to_dev_work(const HostWork& elems, bool in_fifo, bool is_last
     d.sendbuff = elems[i].send;
     d.recvbuff = elems[i].recv;
     d.count = elems[i].count;
-    d.root = 0;
+    d.root = elems[i].root;
     d.bid = elems[i].bid;
     d.nChannels = elems[i].nChannels;
     d.redOpArg = 0;
@@ -440,13 +445,15 @@ int coresident_ring_blocks(int block, int device) {
   int ncu = 0;
   if (rt().CuCount(&ncu, device) != hipSuccess) return 0;
   int best = 1 << 30;
-  const void* fns[1 + 2 * mccsNumTypes * 4];
+  const void* fns[2 + 3 * mccsNumTypes * 4];
   int nf = 0;
   fns[nf++] = ring_multi_kernel_ptr(mccsFuncAllGather, mccsInt8, 0);
+  fns[nf++] = ring_multi_kernel_ptr(mccsFuncBoadcast, mccsInt8, 0);
   for (int dt = 0; dt < mccsNumTypes; ++dt)
     for (int op = 0; op < 4; ++op) {
       fns[nf++] = ring_multi_kernel_ptr(mccsFuncAllReduce, dt, op);
       fns[nf++] = ring_multi_kernel_ptr(mccsFuncReduceScatter, dt, op);
+      fns[nf++] = ring_multi_kernel_ptr(mccsFuncReduce, dt, op);
     }
   for (int i = 0; i < nf; ++i) {
     int per_cu = 0;

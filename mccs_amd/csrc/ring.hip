@@ -2,7 +2,8 @@
 // the ring path.  The device engine is ring_kernel.h; the forty AllReduce
 // kernels live in ring_ar_{sum,prod,max,min}.hip (one translation unit per
 // reduction op, compiled in parallel), the forty ReduceScatter kernels in
-// ring_rs_{sum,prod,max,min}.hip.
+// ring_rs_{sum,prod,max,min}.hip, the forty Reduce kernels in
+// ring_rd_{sum,prod,max,min}.hip and the Broadcast kernel in ring_bc.hip.
 #include "ring_kernel.h"
 
 namespace mccs {
@@ -33,6 +34,16 @@ const void* ring_rs_kernel_Sum(int dtype);
 const void* ring_rs_kernel_Prod(int dtype);
 const void* ring_rs_kernel_Max(int dtype);
 const void* ring_rs_kernel_Min(int dtype);
+const void* ring_rd_kernel_Sum(int dtype);
+const void* ring_rd_kernel_Prod(int dtype);
+const void* ring_rd_kernel_Max(int dtype);
+const void* ring_rd_kernel_Min(int dtype);
+const void* ring_bc_kernel();
+hipError_t ring_tu_rd_sum_read_profile(unsigned long long* out, bool reset);
+hipError_t ring_tu_rd_prod_read_profile(unsigned long long* out, bool reset);
+hipError_t ring_tu_rd_max_read_profile(unsigned long long* out, bool reset);
+hipError_t ring_tu_rd_min_read_profile(unsigned long long* out, bool reset);
+hipError_t ring_tu_bc_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_rs_sum_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_rs_prod_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_rs_max_read_profile(unsigned long long* out, bool reset);
@@ -70,6 +81,18 @@ static const void* rs_kernel(int dtype, int op) {
   return nullptr;
 }
 
+// Reduce and Broadcast likewise
+static const void* rd_kernel(int dtype, int op) {
+  if (dtype < 0 || dtype >= mccsNumTypes) return nullptr;
+  switch (op) {
+    case OpSum: return ring_rd_kernel_Sum(dtype);
+    case OpProd: return ring_rd_kernel_Prod(dtype);
+    case OpMax: return ring_rd_kernel_Max(dtype);
+    case OpMin: return ring_rd_kernel_Min(dtype);
+  }
+  return nullptr;
+}
+
 const void* ring_kernel_ptr(int func, int dtype, int op) {
   if (func == mccsFuncAllGather) return (const void*)&mccsKernel_AllGather_RING_SIMPLE_Sum_int8_t;
   if (func != mccsFuncAllReduce) return nullptr;
@@ -79,6 +102,8 @@ const void* ring_kernel_ptr(int func, int dtype, int op) {
 const void* ring_multi_kernel_ptr(int func, int dtype, int op) {
   if (func == mccsFuncAllGather) return (const void*)&ring_multi_kernel<mccsFuncAllGather, mccsInt8, OpSum>;
   if (func == mccsFuncReduceScatter) return rs_kernel(dtype, op);
+  if (func == mccsFuncReduce) return rd_kernel(dtype, op);
+  if (func == mccsFuncBoadcast) return ring_bc_kernel();
   if (func != mccsFuncAllReduce) return nullptr;
   return ar_kernel(dtype, op, true);
 }
@@ -109,7 +134,9 @@ hipError_t ring_read_profile(unsigned long long* out, bool reset) {
   hipError_t (*const readers[])(unsigned long long*, bool) = {
       ring_tu_ag_read_profile, ring_tu_ar_sum_read_profile, ring_tu_ar_prod_read_profile,
       ring_tu_ar_max_read_profile, ring_tu_ar_min_read_profile, ring_tu_rs_sum_read_profile,
-      ring_tu_rs_prod_read_profile, ring_tu_rs_max_read_profile, ring_tu_rs_min_read_profile};
+      ring_tu_rs_prod_read_profile, ring_tu_rs_max_read_profile, ring_tu_rs_min_read_profile,
+      ring_tu_rd_sum_read_profile, ring_tu_rd_prod_read_profile, ring_tu_rd_max_read_profile,
+      ring_tu_rd_min_read_profile, ring_tu_bc_read_profile};
   for (auto rd : readers) {
     hipError_t e = rd(out, reset);
     if (e != hipSuccess) return e;

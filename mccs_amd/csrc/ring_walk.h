@@ -31,7 +31,7 @@ __host__ __device__ __forceinline__ I round_up(I a, I b) {
 // parts (chunks) per loop is not kept: walk_parts gives it.
 template <typename I>
 struct RingWalk {
-  I size;       // AllReduce: the buffer; AllGather / ReduceScatter: one rank's block
+  I size;       // AllReduce, Broadcast, Reduce: the buffer; AllGather / ReduceScatter: one rank's block
   I stepSize;   // one FIFO step
   I chunkSize;  // the largest chunk
   I loopSize;   // what one loop of all channels covers
@@ -48,7 +48,9 @@ __host__ __device__ __forceinline__ I walk_parts(int func, I nChannels, int nran
 // all_reduce.h:17-21,30 / all_gather.h:16-20,30.  func is mccsFuncAllReduce,
 // mccsFuncAllGather (esize = 1: the int8 kernel counts bytes) or
 // mccsFuncReduceScatter (a block split over the channels like AllGather's, in
-// AllReduce's element granule).  nthreads_ref is the
+// AllReduce's element granule).  mccsFuncBoadcast and
+// mccsFuncReduce cut the whole buffer (size) as a block is cut: Broadcast as
+// AllGather does (esize = 1), Reduce as ReduceScatter does.  nthreads_ref is the
 // reference's thread count (nWarps * WARP_SIZE), buff_size the FIFO's bytes.
 // The reference holds chunkSize in an int: the (int) here and the ones in
 // real_chunk_size / block_chunk_offset are its truncations.
