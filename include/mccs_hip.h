@@ -82,7 +82,11 @@ mccsResult_t mccs_hip_reduce_tune_grid(int blocks);
 
 /* Host stub of the reference-named kernel mccsKernel_<Func>_RING_SIMPLE_<Op>_<T>
  * (collectives.h:43-49) for hipLaunchKernel: the value plan.rs:142-166 stores
- * in KernelPlan.kernel_fn.  func: mccsFuncAllReduce | mccsFuncAllGather. */
+ * in KernelPlan.kernel_fn.  func: mccsFuncAllReduce | mccsFuncAllGather.
+ * op: for AllReduce any mccsDevRedOp_t; the mccsDevPreMulSum / mccsDevSumPostDiv
+ * kernels (mccs_kernels_avg.h) take their scalar from each work element's
+ * redOpArg, as the reference's do.  NULL for SumPostDiv on a floating dtype
+ * (no such kernel), which mccs_hip_launch_coll refuses likewise. */
 const void *mccs_hip_coll_kernel(int func, int dtype, int op);
 /* plan.rs:638-669 launch_plan: hipLaunchKernel(fn, grid, block, {comm,
  * channelMask, workHead}, 0, stream).  grid = #channels * lanes; block =
@@ -293,6 +297,69 @@ mccsResult_t mccsBroadcast(const void *sendbuff, void *recvbuff, size_t nbytes, 
                            hipStream_t stream);
 mccsResult_t mccsReduce(const void *sendbuff, void *recvbuff, size_t count, int dtype, int op, int root,
                         mccsComm_t comm, hipStream_t stream);
+/* PreMulSum, SumPostDiv and the average: the three reducing ring collectives
+ * with an op argument.  The reference declares both ops (mccsDevPreMulSum = 4,
+ * mccsDevSumPostDiv = 5, collectives.h:28-32; DECL2(AllReduce, PreMulSum /
+ * SumPostDiv), collectives.h:101-102; AllReduceOpType, command.rs:40-41; the
+ * functors FuncPreMulSum / FuncSumPostDiv, reduce_kernel.h:478-697) and carries
+ * the scalar in mccsDevWorkElem.redOpArg; the semantics below are those
+ * functors'.
+ * op: any of the six mccsDevRedOp_t.  With mccsDevSum / Prod / Max / Min op_arg
+ * must be 0 and the call is exactly the plain one (which keeps refusing ops 4
+ * and 5).
+ * mccsDevPreMulSum, every dtype: op_arg holds the scalar s, an element of
+ * dtype, in its low sizeof(T) bytes (*(T*)&op_arg; the bits above must be
+ * zero).  Every rank's own input element x is replaced by pre(x) = x * s,
+ * rounded ONCE in dtype (integers: modulo 2^w; half / bfloat16: the exact
+ * product rounded once to the type), before its first use; the reduction then
+ * is Sum.  The product and the sum are two roundings, never one fused
+ * multiply-add.
+ * mccsDevSumPostDiv, the six integer dtypes only: n = (int)op_arg, 1 <= n <=
+ * INT32_MAX.  The reduction is Sum, wrapping in dtype; the finished sum goes
+ * through post(x) = T(x / n), C division truncating toward zero after the
+ * usual promotions (n converts to unsigned for uint32 / uint64).
+ * With the operand order of the plain calls the value is acc = pre(x[s1]),
+ * then acc = pre(x[sk]) + acc for k = 2..n, result = post(acc).  So a
+ * PreMulSum collective equals, bit for bit, the Sum collective over inputs
+ * pre-scaled elementwise, and a SumPostDiv collective equals post applied
+ * elementwise to the Sum collective's output.  pre is applied where a call
+ * reads the user input, post on the call that finishes the reduction
+ * (AllReduce's recvReduceCopySend, the closing recvReduceCopy of ReduceScatter
+ * and of Reduce's root), whose posted value goes to every destination: the
+ * FIFO never carries a pre-less input or a posted partial.  nranks == 1:
+ * recvbuff = post(pre(sendbuff)), in place too.
+ * Otherwise as the plain calls (buffers, in place, counts, roots, groups:
+ * several calls of one function, dtype and op on one comm in one group are
+ * batched into one launch and may differ in op_arg, which is per work element
+ * like the root; mixing ops, e.g. Sum and PreMulSum, is refused with
+ * mccsInvalidUsage at mccsGroupEnd; fused launches of ranks sharing a GPU,
+ * graph capture -- the scalar lives in the captured work list --, the launch
+ * guard, the watchdog and mccsCommAbort).  PreMulSum and SumPostDiv always take
+ * the ring (mccsCommLastAlgo reports MCCS_ALGO_RING), whatever the size and the
+ * direct / one-shot / LL thresholds: those kernels know neither step.
+ * Refused with mccsInvalidArgument (mccsGetLastErrorString names the problem):
+ * a nonzero op_arg with Sum / Prod / Max / Min, PreMulSum bits above the element
+ * width, SumPostDiv on a floating dtype or with op_arg outside 1..INT32_MAX. */
+mccsResult_t mccsAllReduceOpArg(const void *sendbuff, void *recvbuff, size_t count, int dtype, int op,
+                                uint64_t op_arg, mccsComm_t comm, hipStream_t stream);
+mccsResult_t mccsReduceScatterOpArg(const void *sendbuff, void *recvbuff, size_t recvcount, int dtype, int op,
+                                    uint64_t op_arg, mccsComm_t comm, hipStream_t stream);
+mccsResult_t mccsReduceOpArg(const void *sendbuff, void *recvbuff, size_t count, int dtype, int op, uint64_t op_arg,
+                             int root, mccsComm_t comm, hipStream_t stream);
+/* The average over nranks as (op, op_arg) for the calls above (host only).
+ * Floating dtypes: mccsDevPreMulSum with s = 1/nranks (double: 1.0 / n; float:
+ * 1.0f / (float)n; half / bfloat16: that binary32 value rounded to nearest even
+ * once to the type).  Integer dtypes: mccsDevSumPostDiv with n = nranks (NCCL's
+ * mapping). */
+mccsResult_t mccsAvgOp(int dtype, int nranks, int *op, uint64_t *op_arg);
+/* Encodes v as a PreMulSum scalar of dtype (host only).  double: v as is;
+ * float: (float)v; half / bfloat16: (float)v rounded to nearest even to the
+ * type -- two roundings, so a v within half a binary32 ulp of a 16-bit tie may
+ * land one ulp from the directly rounded value; pass a v the type holds exactly
+ * where that matters.  Integer dtypes: v must be integral and in the type's
+ * range (else mccsInvalidArgument); negative values are two's complement in the
+ * element's width. */
+mccsResult_t mccsRedOpArgFromDouble(int dtype, double v, uint64_t *op_arg);
 /* Group calls (ProxyCommand::GroupCall): collectives issued between Start and
  * End are planned together and launched at End (one launch per device). */
 mccsResult_t mccsGroupStart(void);
@@ -430,6 +497,19 @@ mccsResult_t mccs_host_ring_broadcast(int nranks, const void *const *sendbufs, v
 mccsResult_t mccs_host_ring_reduce(int nranks, const void *const *sendbufs, void *const *recvbufs, size_t count,
                                    int dtype, int op, int root, int nchannels, int nthreads_ref, int buff_size,
                                    const int *rings);
+/* The three reducing schedules with an op argument (mccsAllReduceOpArg,
+ * mccsReduceScatterOpArg, mccsReduceOpArg): all six ops, the same argument
+ * rules, pre and post applied where the kernels apply them and rounded as they
+ * round.  The three functions above keep refusing ops 4 and 5. */
+mccsResult_t mccs_host_ring_allreduce_oparg(int nranks, const void *const *sendbufs, void *const *recvbufs,
+                                            size_t count, int dtype, int op, int nchannels, int nthreads_ref,
+                                            int buff_size, const int *rings, uint64_t op_arg);
+mccsResult_t mccs_host_ring_reduce_scatter_oparg(int nranks, const void *const *sendbufs, void *const *recvbufs,
+                                                 size_t recvcount, int dtype, int op, int nchannels,
+                                                 int nthreads_ref, int buff_size, const int *rings, uint64_t op_arg);
+mccsResult_t mccs_host_ring_reduce_oparg(int nranks, const void *const *sendbufs, void *const *recvbufs, size_t count,
+                                         int dtype, int op, int root, int nchannels, int nthreads_ref, int buff_size,
+                                         const int *rings, uint64_t op_arg);
 /* Default ring orders for an n-rank node (edge-disjoint Hamiltonian cycles,
  * both directions); writes up to max_channels x nranks ints, returns count. */
 int mccs_default_rings(int nranks, int nch_req, int *out, int max_channels);

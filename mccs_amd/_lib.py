@@ -107,6 +107,14 @@ SIGNATURES: dict[str, tuple] = {
     "mccsReduceScatter": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_int, _c_void_p, _c_void_p]),
     "mccsBroadcast": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_void_p, _c_void_p]),
     "mccsReduce": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),
+    "mccsAllReduceOpArg": (
+        _c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_int, ctypes.c_uint64, _c_void_p, _c_void_p]),
+    "mccsReduceScatterOpArg": (
+        _c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_int, ctypes.c_uint64, _c_void_p, _c_void_p]),
+    "mccsReduceOpArg": (
+        _c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_int, ctypes.c_uint64, _c_int, _c_void_p, _c_void_p]),
+    "mccsAvgOp": (_c_int, [_c_int, _c_int, _P(_c_int), _P(ctypes.c_uint64)]),
+    "mccsRedOpArgFromDouble": (_c_int, [_c_int, ctypes.c_double, _P(ctypes.c_uint64)]),
     "mccsGroupStart": (_c_int, []),
     "mccsGroupEnd": (_c_int, []),
     "mccsCommSync": (_c_int, [_c_void_p]),
@@ -153,6 +161,15 @@ SIGNATURES: dict[str, tuple] = {
     "mccs_host_ring_reduce": (
         _c_int, [_c_int, _P(_c_void_p), _P(_c_void_p), _c_size_t, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
                  _P(_c_int)]),
+    "mccs_host_ring_allreduce_oparg": (
+        _c_int, [_c_int, _P(_c_void_p), _P(_c_void_p), _c_size_t, _c_int, _c_int, _c_int, _c_int, _c_int,
+                 _P(_c_int), ctypes.c_uint64]),
+    "mccs_host_ring_reduce_scatter_oparg": (
+        _c_int, [_c_int, _P(_c_void_p), _P(_c_void_p), _c_size_t, _c_int, _c_int, _c_int, _c_int, _c_int,
+                 _P(_c_int), ctypes.c_uint64]),
+    "mccs_host_ring_reduce_oparg": (
+        _c_int, [_c_int, _P(_c_void_p), _P(_c_void_p), _c_size_t, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
+                 _P(_c_int), ctypes.c_uint64]),
 }
 
 # Symbols appended after round 4: an older build (an A/B library under abvar/,

@@ -80,6 +80,7 @@ def _compile(src: str, hdr_mtime: float, verbose: bool) -> str:
 REF_OPS = ("Sum", "Prod", "Max", "Min")
 REF_TYPES = ("int8_t", "uint8_t", "int32_t", "uint32_t", "int64_t", "uint64_t", "half", "float", "double",
              "bfloat16")
+REF_INT_TYPES = REF_TYPES[:6]
 
 
 def kernel_names() -> list[str]:
@@ -87,6 +88,9 @@ def kernel_names() -> list[str]:
     out = ["mccsKernel_AllGather_RING_SIMPLE_Sum_int8_t"]
     for op in REF_OPS:
         out += [f"mccsKernel_AllReduce_RING_SIMPLE_{op}_{t}" for t in REF_TYPES]
+    # collectives.h:101-102 (include/mccs_kernels_avg.h); SumPostDiv has the integer types only
+    out += [f"mccsKernel_AllReduce_RING_SIMPLE_PreMulSum_{t}" for t in REF_TYPES]
+    out += [f"mccsKernel_AllReduce_RING_SIMPLE_SumPostDiv_{t}" for t in REF_INT_TYPES]
     return out
 
 

@@ -52,8 +52,11 @@ class AllReduceDataType(enum.IntEnum):
 
 
 class AllReduceOpType(enum.IntEnum):
-    """command.rs:33-42 (PreMulSum/SumPostDiv are declared there but no kernel
-    exists for them in the reference either: gen_rules.sh:15)."""
+    """command.rs:33-42.  PreMulSum and SumPostDiv take an argument (`op_arg=`
+    of all_reduce / reduce_scatter / reduce: the scalar in the element type's
+    bits, red_op_arg(); the divisor): the ring kernels implement both
+    (PreMulSum for every dtype, SumPostDiv for the integer ones).  avg_op()
+    maps the average onto them."""
 
     Sum = 0
     Prod = 1
@@ -118,6 +121,11 @@ def _ptr(x) -> int:
     if x is None:  # the buffer a rooted collective's role does not use
         return 0
     return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
+
+
+def _u64(x) -> int:
+    """An op argument as the C-ABI's uint64_t (a negative Python int is taken in two's complement)."""
+    return int(x) & 0xFFFFFFFFFFFFFFFF
 
 
 def _stream(s) -> int:
@@ -189,22 +197,33 @@ class Communicator:
         return p.value
 
     def all_reduce(self, send_buf, recv_buf, size: int, data_type=AllReduceDataType.Float32,
-                   op_type=AllReduceOpType.Sum, stream=None) -> None:
-        all_reduce(self, send_buf, recv_buf, size, data_type, op_type, stream)
+                   op_type=AllReduceOpType.Sum, stream=None, op_arg: int | None = None) -> None:
+        all_reduce(self, send_buf, recv_buf, size, data_type, op_type, stream, op_arg=op_arg)
 
     def all_gather(self, send_buf, recv_buf, size: int, stream=None) -> None:
         all_gather(self, send_buf, recv_buf, size, stream)
 
     def reduce_scatter(self, send_buf, recv_buf, recv_count: int, data_type=AllReduceDataType.Float32,
-                       op_type=AllReduceOpType.Sum, stream=None) -> None:
-        reduce_scatter(self, send_buf, recv_buf, recv_count, data_type, op_type, stream)
+                       op_type=AllReduceOpType.Sum, stream=None, op_arg: int | None = None) -> None:
+        reduce_scatter(self, send_buf, recv_buf, recv_count, data_type, op_type, stream, op_arg=op_arg)
 
     def broadcast(self, send_buf, recv_buf, nbytes: int, root: int, stream=None) -> None:
         broadcast(self, send_buf, recv_buf, nbytes, root, stream)
 
     def reduce(self, send_buf, recv_buf, count: int, data_type=AllReduceDataType.Float32,
-               op_type=AllReduceOpType.Sum, root: int = 0, stream=None) -> None:
-        reduce(self, send_buf, recv_buf, count, data_type, op_type, root, stream)
+               op_type=AllReduceOpType.Sum, root: int = 0, stream=None, op_arg: int | None = None) -> None:
+        reduce(self, send_buf, recv_buf, count, data_type, op_type, root, stream, op_arg=op_arg)
+
+    def all_reduce_avg(self, send_buf, recv_buf, size: int, data_type=AllReduceDataType.Float32, stream=None) -> None:
+        all_reduce_avg(self, send_buf, recv_buf, size, data_type, stream)
+
+    def reduce_scatter_avg(self, send_buf, recv_buf, recv_count: int, data_type=AllReduceDataType.Float32,
+                           stream=None) -> None:
+        reduce_scatter_avg(self, send_buf, recv_buf, recv_count, data_type, stream)
+
+    def reduce_avg(self, send_buf, recv_buf, count: int, data_type=AllReduceDataType.Float32, root: int = 0,
+                   stream=None) -> None:
+        reduce_avg(self, send_buf, recv_buf, count, data_type, root, stream)
 
     def sync(self) -> None:
         """Waits for the comm's launches; raises on a device-side timeout/abort."""
@@ -280,11 +299,20 @@ def init_communicator_rank(rank: int, nranks: int, device: int, exchange, config
 
 
 def all_reduce(comm: Communicator, send_buf, recv_buf, size: int, data_type=AllReduceDataType.Float32,
-               op_type=AllReduceOpType.Sum, stream=None) -> None:
-    """libmccs::all_reduce (collectives.rs:75-138): stream-ordered, returns after launch."""
-    rc = _sig().mccsAllReduce(_ptr(send_buf), _ptr(recv_buf), int(size), int(data_type), int(op_type),
-                              comm._h, _stream(stream))
-    _lib.check(rc, "mccsAllReduce")
+               op_type=AllReduceOpType.Sum, stream=None, op_arg: int | None = None) -> None:
+    """libmccs::all_reduce (collectives.rs:75-138): stream-ordered, returns after launch.
+    op_arg=None is mccsAllReduce (Sum / Prod / Max / Min); a value goes to
+    mccsAllReduceOpArg, which also takes PreMulSum (op_arg: the scalar's bits,
+    red_op_arg()) and SumPostDiv (op_arg: the divisor) and always runs those
+    two on the ring."""
+    if op_arg is None:
+        rc = _sig().mccsAllReduce(_ptr(send_buf), _ptr(recv_buf), int(size), int(data_type), int(op_type),
+                                  comm._h, _stream(stream))
+        _lib.check(rc, "mccsAllReduce")
+        return
+    rc = _sig().mccsAllReduceOpArg(_ptr(send_buf), _ptr(recv_buf), int(size), int(data_type), int(op_type),
+                                   _u64(op_arg), comm._h, _stream(stream))
+    _lib.check(rc, "mccsAllReduceOpArg")
 
 
 def all_gather(comm: Communicator, send_buf, recv_buf, size: int, stream=None) -> None:
@@ -294,13 +322,19 @@ def all_gather(comm: Communicator, send_buf, recv_buf, size: int, stream=None) -
 
 
 def reduce_scatter(comm: Communicator, send_buf, recv_buf, recv_count: int, data_type=AllReduceDataType.Float32,
-                   op_type=AllReduceOpType.Sum, stream=None) -> None:
+                   op_type=AllReduceOpType.Sum, stream=None, op_arg: int | None = None) -> None:
     """mccsReduceScatter: send holds nranks * recv_count elements (block D at
     element D * recv_count); recv gets recv_count elements, the reduction of
-    this rank's block over all ranks.  Always the ring; stream-ordered."""
-    rc = _sig().mccsReduceScatter(_ptr(send_buf), _ptr(recv_buf), int(recv_count), int(data_type), int(op_type),
-                                  comm._h, _stream(stream))
-    _lib.check(rc, "mccsReduceScatter")
+    this rank's block over all ranks.  Always the ring; stream-ordered.
+    op_arg as for all_reduce (mccsReduceScatterOpArg)."""
+    if op_arg is None:
+        rc = _sig().mccsReduceScatter(_ptr(send_buf), _ptr(recv_buf), int(recv_count), int(data_type),
+                                      int(op_type), comm._h, _stream(stream))
+        _lib.check(rc, "mccsReduceScatter")
+        return
+    rc = _sig().mccsReduceScatterOpArg(_ptr(send_buf), _ptr(recv_buf), int(recv_count), int(data_type),
+                                       int(op_type), _u64(op_arg), comm._h, _stream(stream))
+    _lib.check(rc, "mccsReduceScatterOpArg")
 
 
 def broadcast(comm: Communicator, send_buf, recv_buf, nbytes: int, root: int, stream=None) -> None:
@@ -312,13 +346,57 @@ def broadcast(comm: Communicator, send_buf, recv_buf, nbytes: int, root: int, st
 
 
 def reduce(comm: Communicator, send_buf, recv_buf, count: int, data_type=AllReduceDataType.Float32,
-           op_type=AllReduceOpType.Sum, root: int = 0, stream=None) -> None:
+           op_type=AllReduceOpType.Sum, root: int = 0, stream=None, op_arg: int | None = None) -> None:
     """mccsReduce: the root's recv[0, count) gets the reduction of every rank's
     send[0, count).  recv is used on the root only (None elsewhere); in place on
-    the root is recv == send.  Always the ring; stream-ordered."""
-    rc = _sig().mccsReduce(_ptr(send_buf), _ptr(recv_buf), int(count), int(data_type), int(op_type), int(root),
-                           comm._h, _stream(stream))
-    _lib.check(rc, "mccsReduce")
+    the root is recv == send.  Always the ring; stream-ordered.  op_arg as for
+    all_reduce (mccsReduceOpArg)."""
+    if op_arg is None:
+        rc = _sig().mccsReduce(_ptr(send_buf), _ptr(recv_buf), int(count), int(data_type), int(op_type), int(root),
+                               comm._h, _stream(stream))
+        _lib.check(rc, "mccsReduce")
+        return
+    rc = _sig().mccsReduceOpArg(_ptr(send_buf), _ptr(recv_buf), int(count), int(data_type), int(op_type),
+                                _u64(op_arg), int(root), comm._h, _stream(stream))
+    _lib.check(rc, "mccsReduceOpArg")
+
+
+def avg_op(data_type, nranks: int) -> tuple[AllReduceOpType, int]:
+    """mccsAvgOp: the (op, op_arg) that averages over nranks.  Floating types:
+    PreMulSum with 1/nranks in the type's bits; integer types: SumPostDiv with
+    nranks (truncating division of the finished sum).  Host-only."""
+    op, arg = _ci(), ctypes.c_uint64()
+    _lib.check(_sig().mccsAvgOp(int(data_type), int(nranks), ctypes.byref(op), ctypes.byref(arg)), "mccsAvgOp")
+    return AllReduceOpType(op.value), int(arg.value)
+
+
+def red_op_arg(data_type, value) -> int:
+    """mccsRedOpArgFromDouble: `value` as a PreMulSum scalar of data_type (its
+    bits in the low bytes).  float16 / bfloat16 round through binary32; an
+    integer type needs an integral value in range.  Host-only."""
+    arg = ctypes.c_uint64()
+    _lib.check(_sig().mccsRedOpArgFromDouble(int(data_type), float(value), ctypes.byref(arg)),
+               "mccsRedOpArgFromDouble")
+    return int(arg.value)
+
+
+def all_reduce_avg(comm: Communicator, send_buf, recv_buf, size: int, data_type=AllReduceDataType.Float32,
+                   stream=None) -> None:
+    """The average over the communicator's ranks (avg_op) as one AllReduce."""
+    op, arg = avg_op(data_type, comm.nranks)
+    all_reduce(comm, send_buf, recv_buf, size, data_type, op, stream, op_arg=arg)
+
+
+def reduce_scatter_avg(comm: Communicator, send_buf, recv_buf, recv_count: int,
+                       data_type=AllReduceDataType.Float32, stream=None) -> None:
+    op, arg = avg_op(data_type, comm.nranks)
+    reduce_scatter(comm, send_buf, recv_buf, recv_count, data_type, op, stream, op_arg=arg)
+
+
+def reduce_avg(comm: Communicator, send_buf, recv_buf, count: int, data_type=AllReduceDataType.Float32,
+               root: int = 0, stream=None) -> None:
+    op, arg = avg_op(data_type, comm.nranks)
+    reduce(comm, send_buf, recv_buf, count, data_type, op, root, stream, op_arg=arg)
 
 
 @contextlib.contextmanager
@@ -340,7 +418,8 @@ def default_rings(nranks: int, channels: int = 0) -> list[list[int]]:
 
 
 def host_ring_allreduce(sendbufs, recvbufs, count: int, data_type, op_type=AllReduceOpType.Sum,
-                        channels: int = 1, nthreads: int = 96, buffer_size: int = 1 << 22, rings=None) -> None:
+                        channels: int = 1, nthreads: int = 96, buffer_size: int = 1 << 22, rings=None,
+                        op_arg: int | None = None) -> None:
     """BASELINE configs[0]: the ring protocol on host threads over host memory
     (numpy arrays or raw host pointers; no GPU)."""
     n = len(sendbufs)
@@ -351,13 +430,19 @@ def host_ring_allreduce(sendbufs, recvbufs, count: int, data_type, op_type=AllRe
     if rings is not None:
         flat = [int(v) for r in rings for v in r]
         ro = (_ci * len(flat))(*flat)
+    if op_arg is not None:  # all six ops (mccs_host_ring_allreduce_oparg)
+        rc = _sig().mccs_host_ring_allreduce_oparg(n, sp, rp, int(count), int(data_type), int(op_type), channels,
+                                                   nthreads, buffer_size, ro, _u64(op_arg))
+        _lib.check(rc, "mccs_host_ring_allreduce_oparg")
+        return
     rc = _sig().mccs_host_ring_allreduce(n, sp, rp, int(count), int(data_type), int(op_type), channels, nthreads,
                                          buffer_size, ro)
     _lib.check(rc, "mccs_host_ring_allreduce")
 
 
 def host_ring_reduce_scatter(sendbufs, recvbufs, recv_count: int, data_type, op_type=AllReduceOpType.Sum,
-                             channels: int = 1, nthreads: int = 96, buffer_size: int = 1 << 22, rings=None) -> None:
+                             channels: int = 1, nthreads: int = 96, buffer_size: int = 1 << 22, rings=None,
+                             op_arg: int | None = None) -> None:
     """The ring ReduceScatter schedule on host threads over host memory (numpy
     arrays or raw host pointers; no GPU): sendbufs[r] holds nranks * recv_count
     elements, recvbufs[r] recv_count."""
@@ -369,6 +454,11 @@ def host_ring_reduce_scatter(sendbufs, recvbufs, recv_count: int, data_type, op_
     if rings is not None:
         flat = [int(v) for r in rings for v in r]
         ro = (_ci * len(flat))(*flat)
+    if op_arg is not None:
+        rc = _sig().mccs_host_ring_reduce_scatter_oparg(n, sp, rp, int(recv_count), int(data_type), int(op_type),
+                                                        channels, nthreads, buffer_size, ro, _u64(op_arg))
+        _lib.check(rc, "mccs_host_ring_reduce_scatter_oparg")
+        return
     rc = _sig().mccs_host_ring_reduce_scatter(n, sp, rp, int(recv_count), int(data_type), int(op_type), channels,
                                               nthreads, buffer_size, ro)
     _lib.check(rc, "mccs_host_ring_reduce_scatter")
@@ -393,13 +483,20 @@ def host_ring_broadcast(sendbufs, recvbufs, nbytes: int, root: int, channels: in
 
 
 def host_ring_reduce(sendbufs, recvbufs, count: int, data_type, op_type=AllReduceOpType.Sum, root: int = 0,
-                     channels: int = 1, nthreads: int = 96, buffer_size: int = 1 << 22, rings=None) -> None:
+                     channels: int = 1, nthreads: int = 96, buffer_size: int = 1 << 22, rings=None,
+                     op_arg: int | None = None) -> None:
     """The ring Reduce schedule on host threads over host memory (numpy arrays
     or raw host pointers; no GPU).  recvbufs[r] may be None for r != root."""
     ro = None
     if rings is not None:
         flat = [int(v) for r in rings for v in r]
         ro = (_ci * len(flat))(*flat)
+    if op_arg is not None:
+        rc = _sig().mccs_host_ring_reduce_oparg(len(sendbufs), _host_ptrs(sendbufs), _host_ptrs(recvbufs), int(count),
+                                                int(data_type), int(op_type), int(root), channels, nthreads,
+                                                buffer_size, ro, _u64(op_arg))
+        _lib.check(rc, "mccs_host_ring_reduce_oparg")
+        return
     rc = _sig().mccs_host_ring_reduce(len(sendbufs), _host_ptrs(sendbufs), _host_ptrs(recvbufs), int(count),
                                       int(data_type), int(op_type), int(root), channels, nthreads, buffer_size, ro)
     _lib.check(rc, "mccs_host_ring_reduce")
@@ -458,6 +555,7 @@ def ring_walk(func: int, nranks: int, channels: int, elem_bytes: int, nthreads: 
 
 __all__ = ["AllReduceDataType", "AllReduceOpType", "CommConfig", "Communicator", "init_all",
            "init_communicator_rank", "all_reduce", "all_gather", "reduce_scatter", "broadcast", "reduce",
+           "avg_op", "red_op_arg", "all_reduce_avg", "reduce_scatter_avg", "reduce_avg",
            "group", "default_rings", "task_schema",
            "direct_defaults", "ll_default", "ring_walk",
            "host_ring_allreduce", "host_ring_reduce_scatter", "host_ring_broadcast", "host_ring_reduce", "ring_profile",

@@ -14,6 +14,10 @@
 // acc = fn(x[idx k+j], acc) for j = 2..n, rounded in T at every step,
 // all_reduce.h:46-70 + prims_simple.h:174-177), so the output equals the
 // ring's (and the oracle's) for the same channels and rings.
+// Sum / Prod / Max / Min only: these kernels know neither PreMulSum's step on
+// the input nor SumPostDiv's on the finished value (dtypes.h pre_op / post_op),
+// so the planner sends those two ops to the ring at every size (plan.cpp
+// plan_enqueue); teaching the direct variants the two steps is left for later.
 //
 // One launch per device (blockIdx.y = rank slot when ranks share a GPU), G
 // workgroups per rank of MCCS_DIRECT_THREADS threads.  Each phase cuts the

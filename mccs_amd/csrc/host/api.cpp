@@ -9,6 +9,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -16,6 +17,7 @@
 
 #include "comm.h"
 #include "dtypes.h"
+#include "half_bits.h"
 #include "ring_walk.h"
 
 namespace mccs {
@@ -185,8 +187,10 @@ static mccsResult_t enable_peer(int a, int b) {
   return mccsSuccess;
 }
 
+// op_arg: nullptr from the plain entry points (Sum / Prod / Max / Min only), the
+// argument of an mccs*OpArg entry point otherwise (all six ops).
 static mccsResult_t launch_single(Comm* c, int func, int dtype, int op, const void* send, void* recv, size_t count,
-                                  hipStream_t stream, int root = 0) {
+                                  hipStream_t stream, int root = 0, const uint64_t* op_arg = nullptr) {
   // inside a group the diagnosis of a rejected call must survive to GroupEnd
   // (the group was cleared at GroupStart)
   if (g_group.depth == 0) err_clear();
@@ -211,13 +215,25 @@ static mccsResult_t launch_single(Comm* c, int func, int dtype, int op, const vo
   const bool need_recv = func != mccsFuncReduce || c->rank == root;
   if ((need_send && !send) || (need_recv && !recv)) return reject(mccsInvalidArgument, "null send or recv buffer");
   if ((func == mccsFuncAllReduce || func == mccsFuncReduceScatter || func == mccsFuncReduce) &&
-      (dtype < 0 || dtype >= mccsNumTypes || op < 0 || op > mccsDevMin))
+      (dtype < 0 || dtype >= mccsNumTypes || op < 0 || op > (op_arg ? mccsDevSumPostDiv : mccsDevMin)))
     return reject(mccsInvalidArgument, "unknown dtype or reduction op");
+  const uint64_t arg = op_arg ? *op_arg : 0;
+  if (op_arg) {
+    const int es = elem_bytes(dtype);
+    if (op <= mccsDevMin && arg != 0)
+      return reject(mccsInvalidArgument, "op_arg must be 0 for Sum / Prod / Max / Min");
+    if (op == mccsDevPreMulSum && es < 8 && (arg >> (8 * es)) != 0)
+      return reject(mccsInvalidArgument, "PreMulSum: op_arg has bits set above the element width");
+    if (op == mccsDevSumPostDiv && !is_integer_dtype(dtype))
+      return reject(mccsInvalidArgument, "SumPostDiv needs an integer dtype");
+    if (op == mccsDevSumPostDiv && (arg < 1 || arg > (uint64_t)INT32_MAX))
+      return reject(mccsInvalidArgument, "SumPostDiv: op_arg (the divisor) outside 1..INT32_MAX");
+  }
   const char* const name = func == mccsFuncAllGather       ? "mccsAllGather"
-                           : func == mccsFuncReduceScatter ? "mccsReduceScatter"
+                           : func == mccsFuncReduceScatter ? (op_arg ? "mccsReduceScatterOpArg" : "mccsReduceScatter")
                            : func == mccsFuncBoadcast      ? "mccsBroadcast"
-                           : func == mccsFuncReduce        ? "mccsReduce"
-                                                           : "mccsAllReduce";
+                           : func == mccsFuncReduce        ? (op_arg ? "mccsReduceOpArg" : "mccsReduce")
+                                                           : (op_arg ? "mccsAllReduceOpArg" : "mccsAllReduce");
   if (std::find(g_group.comms.begin(), g_group.comms.end(), c) == g_group.comms.end()) {
     g_group.comms.push_back(c);
     g_group.streams.push_back(stream);
@@ -225,7 +241,7 @@ static mccsResult_t launch_single(Comm* c, int func, int dtype, int op, const vo
   mccsResult_t er;
   {
     StepScope st(name);
-    er = plan_enqueue(c, func, dtype, op, send, recv, count, rooted ? root : 0);
+    er = plan_enqueue(c, func, dtype, op, send, recv, count, rooted ? root : 0, arg);
   }
   if (er != mccsSuccess) {
     if (g_group.depth == 0) group_discard();
@@ -619,6 +635,72 @@ extern "C" mccsResult_t mccsBroadcast(const void* sendbuff, void* recvbuff, size
 extern "C" mccsResult_t mccsReduce(const void* sendbuff, void* recvbuff, size_t count, int dtype, int op, int root,
                                    mccsComm_t comm, hipStream_t stream) {
   return launch_single((Comm*)comm, mccsFuncReduce, dtype, op, sendbuff, recvbuff, count, stream, root);
+}
+
+extern "C" mccsResult_t mccsAllReduceOpArg(const void* sendbuff, void* recvbuff, size_t count, int dtype, int op,
+                                           uint64_t op_arg, mccsComm_t comm, hipStream_t stream) {
+  return launch_single((Comm*)comm, mccsFuncAllReduce, dtype, op, sendbuff, recvbuff, count, stream, 0, &op_arg);
+}
+
+extern "C" mccsResult_t mccsReduceScatterOpArg(const void* sendbuff, void* recvbuff, size_t recvcount, int dtype,
+                                               int op, uint64_t op_arg, mccsComm_t comm, hipStream_t stream) {
+  return launch_single((Comm*)comm, mccsFuncReduceScatter, dtype, op, sendbuff, recvbuff, recvcount, stream, 0,
+                       &op_arg);
+}
+
+extern "C" mccsResult_t mccsReduceOpArg(const void* sendbuff, void* recvbuff, size_t count, int dtype, int op,
+                                        uint64_t op_arg, int root, mccsComm_t comm, hipStream_t stream) {
+  return launch_single((Comm*)comm, mccsFuncReduce, dtype, op, sendbuff, recvbuff, count, stream, root, &op_arg);
+}
+
+extern "C" mccsResult_t mccsRedOpArgFromDouble(int dtype, double v, uint64_t* op_arg) {
+  err_clear();
+  if (!op_arg || dtype < 0 || dtype >= mccsNumTypes) MCCS_FAIL(mccsInvalidArgument, "unknown dtype or null op_arg");
+  uint64_t bits = 0;
+  switch (dtype) {
+    case mccsFloat64: std::memcpy(&bits, &v, 8); break;
+    case mccsFloat32: {
+      const float f = (float)v;
+      std::memcpy(&bits, &f, 4);
+      break;
+    }
+    // two roundings: to binary32, then to the 16-bit type (nearest even both times)
+    case mccsFloat16: bits = f2h((float)v); break;
+    case mccsBfloat16: bits = f2b((float)v); break;
+    default: {
+      const int w = 8 * elem_bytes(dtype);
+      const bool sgn = dtype == mccsInt8 || dtype == mccsInt32 || dtype == mccsInt64;
+      const double lo = sgn ? -std::ldexp(1.0, w - 1) : 0.0, hi = std::ldexp(1.0, sgn ? w - 1 : w);  // [lo, hi)
+      if (!(v >= lo && v < hi) || v != std::floor(v))
+        MCCS_FAIL(mccsInvalidArgument, "%g is not an integer the dtype can hold", v);
+      bits = sgn ? (uint64_t)(int64_t)v : (uint64_t)v;
+      if (w < 64) bits &= (1ull << w) - 1;
+    }
+  }
+  *op_arg = bits;
+  return mccsSuccess;
+}
+
+extern "C" mccsResult_t mccsAvgOp(int dtype, int nranks, int* op, uint64_t* op_arg) {
+  err_clear();
+  if (!op || !op_arg || dtype < 0 || dtype >= mccsNumTypes || nranks < 1)
+    MCCS_FAIL(mccsInvalidArgument, "unknown dtype, nranks < 1 or null output");
+  if (is_integer_dtype(dtype)) {  // NCCL's mapping: integers divide the finished sum
+    *op = mccsDevSumPostDiv;
+    *op_arg = (uint64_t)nranks;
+    return mccsSuccess;
+  }
+  *op = mccsDevPreMulSum;
+  if (dtype == mccsFloat64) {
+    const double s = 1.0 / nranks;
+    std::memcpy(op_arg, &s, 8);
+    return mccsSuccess;
+  }
+  const float s = 1.0f / (float)nranks;
+  uint32_t b;
+  std::memcpy(&b, &s, 4);
+  *op_arg = dtype == mccsFloat32 ? b : dtype == mccsFloat16 ? f2h(s) : f2b(s);
+  return mccsSuccess;
 }
 
 extern "C" mccsResult_t mccsGroupStart(void) {

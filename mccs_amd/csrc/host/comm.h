@@ -160,6 +160,7 @@ struct WorkElemHost {
   size_t count;
   uint8_t bid, nChannels;
   uint32_t root;  // Broadcast / Reduce: the root rank (0 otherwise)
+  uint64_t op_arg;  // PreMulSum's scalar / SumPostDiv's divisor (mccsDevWorkElem.redOpArg; 0 otherwise)
 };
 
 // One KernelWork (plan.rs): up to MCCS_MAX_WORK_ELEMENTS elements of one
@@ -345,9 +346,10 @@ int gate_env();  // MCCS_GATE: -1 unset, else its value
 mccsResult_t comm_gate(std::vector<Comm*>& cs, const std::vector<bool>& atomics_ok);
 // plan.cpp
 void plan_discard(Comm* c);  // drops the pending plan
-// root: the root rank of a Broadcast / Reduce (per work element; 0 for the other functions)
+// root: the root rank of a Broadcast / Reduce (per work element; 0 for the other functions);
+// op_arg: the scalar of a PreMulSum / SumPostDiv (per work element too; 0 for the other ops)
 mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send, void* recv, size_t count,
-                          int root = 0);
+                          int root = 0, uint64_t op_arg = 0);
 mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_t>& user_streams);
 // ring.hip
 const void* ring_kernel_ptr(int func, int dtype, int op);

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "dtypes.h"
+#include "half_bits.h"
 #include "mccs_devcomm.h"
 #include "mccs_hip.h"
 #include "ring_walk.h"
@@ -35,51 +36,10 @@
 namespace {
 
 using mccs::RingWalk;
-
-float h2f(uint16_t h) {
-  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, exp = (h >> 10) & 0x1f, man = h & 0x3ffu;
-  uint32_t u;
-  if (exp == 0) {
-    float v = std::ldexp((float)man, -24);
-    return sign ? -v : v;
-  }
-  if (exp == 31) u = sign | 0x7f800000u | (man << 13);
-  else u = sign | ((exp + 112) << 23) | (man << 13);
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
-uint16_t f2h(float f) {  // round to nearest even
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  const uint32_t sign = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
-  if (a >= 0x7f800000u) return (uint16_t)(sign | 0x7c00u | (a > 0x7f800000u ? 0x200u : 0));
-  if (a >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);
-  if (a < 0x38800000u) {
-    float v;
-    std::memcpy(&v, &a, 4);
-    return (uint16_t)(sign | (uint32_t)std::nearbyint(v * 16777216.0f));
-  }
-  uint32_t h = (((a >> 23) - 112) << 10) | ((a & 0x7fffffu) >> 13);
-  const uint32_t rem = a & 0x1fffu;
-  if (rem > 0x1000u || (rem == 0x1000u && (h & 1u))) h += 1;
-  return (uint16_t)(sign | h);
-}
-
-float b2f(uint16_t b) {
-  uint32_t u = (uint32_t)b << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
-uint16_t f2b(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
+using mccs::b2f;
+using mccs::f2b;
+using mccs::f2h;
+using mccs::h2f;
 
 template <typename T>
 T iop(int op, T x, T y) {
@@ -155,6 +115,68 @@ void apply(int dt, int op, void* out, const void* x, const void* y, size_t n) {
 #undef INT_CASE
 }
 
+// PreMulSum's pre step (dtypes.h pre_op): out[i] = x[i] * s rounded once in
+// the type, s the low bytes of arg; integers modulo 2^w.  The product is a
+// statement of its own, compiled with contraction off, so no host compiler
+// fuses it with the add that follows (the kernels keep the two roundings too).
+// out may alias x.
+void pre_apply(int dt, uint64_t arg, void* out, const void* x, size_t n) {
+#pragma clang fp contract(off)
+#define INT_CASE(D, T)                                                                                       \
+  case D:                                                                                                    \
+    for (size_t i = 0; i < n; ++i)                                                                           \
+      ((T*)out)[i] = (T)((std::make_unsigned<T>::type)((const T*)x)[i] * (std::make_unsigned<T>::type)arg);  \
+    break;
+  switch (dt) {
+    INT_CASE(mccsInt8, int8_t)
+    INT_CASE(mccsUint8, uint8_t)
+    INT_CASE(mccsInt32, int32_t)
+    INT_CASE(mccsUint32, uint32_t)
+    INT_CASE(mccsInt64, int64_t)
+    INT_CASE(mccsUint64, uint64_t)
+    case mccsFloat32: {
+      float s;
+      const uint32_t b = (uint32_t)arg;
+      std::memcpy(&s, &b, 4);
+      for (size_t i = 0; i < n; ++i) {
+        volatile float p = ((const float*)x)[i] * s;
+        ((float*)out)[i] = p;
+      }
+      break;
+    }
+    case mccsFloat64: {
+      double s;
+      std::memcpy(&s, &arg, 8);
+      for (size_t i = 0; i < n; ++i) {
+        volatile double p = ((const double*)x)[i] * s;
+        ((double*)out)[i] = p;
+      }
+      break;
+    }
+    case mccsFloat16:  // the exact product fits binary32: one rounding, to binary16
+      for (size_t i = 0; i < n; ++i) ((uint16_t*)out)[i] = f2h(h2f(((const uint16_t*)x)[i]) * h2f((uint16_t)arg));
+      break;
+    case mccsBfloat16:
+      for (size_t i = 0; i < n; ++i) ((uint16_t*)out)[i] = f2b(b2f(((const uint16_t*)x)[i]) * b2f((uint16_t)arg));
+      break;
+  }
+#undef INT_CASE
+}
+
+// SumPostDiv's post step (dtypes.h post_op): v[i] = T(v[i] / n), n = (int)arg,
+// C division after the usual promotions (n unsigned for uint32 / uint64).
+void post_apply(int dt, uint64_t arg, void* v, size_t cnt) {
+  const int n = (int)arg;
+  switch (dt) {
+    case mccsInt8: for (size_t i = 0; i < cnt; ++i) ((int8_t*)v)[i] = (int8_t)(((int8_t*)v)[i] / n); break;
+    case mccsUint8: for (size_t i = 0; i < cnt; ++i) ((uint8_t*)v)[i] = (uint8_t)(((uint8_t*)v)[i] / n); break;
+    case mccsInt32: for (size_t i = 0; i < cnt; ++i) ((int32_t*)v)[i] /= n; break;
+    case mccsUint32: for (size_t i = 0; i < cnt; ++i) ((uint32_t*)v)[i] /= (uint32_t)n; break;
+    case mccsInt64: for (size_t i = 0; i < cnt; ++i) ((int64_t*)v)[i] /= (int64_t)n; break;
+    case mccsUint64: for (size_t i = 0; i < cnt; ++i) ((uint64_t*)v)[i] /= (uint64_t)n; break;
+  }
+}
+
 struct HostConn {  // one directed FIFO (rank -> next) of one channel
   // uninitialised: only the slots a call touches are ever faulted in (a
   // zero-filled 4 MiB FIFO per connector cost ms per 1 KiB call)
@@ -167,6 +189,7 @@ struct HostConn {  // one directed FIFO (rank -> next) of one channel
 
 struct Ctx {
   int func, n, nch, dt, op, nthreads_ref, buff_size, root;
+  uint64_t op_arg;  // PreMulSum / SumPostDiv (0 otherwise)
   size_t es, count;
   const void* const* send;
   void* const* recv;
@@ -254,10 +277,18 @@ struct RankChannel {
       const char* rslot = in->data.get() + (rstep % 8) * stepSize * c->es;
       char* sslot = out->data.get() + (sstep % 8) * stepSize * c->es;
       if (bytes) {
-        // vals = srcs[0]; vals = fn(vals, srcs[1]) with srcs = [input?, recv?]
-        if (SRC && RECV) apply(c->dt, c->op, tmp, input + (srcIx + offset) * c->es, rslot, (size_t)real);
-        else if (SRC) std::memcpy(tmp, input + (srcIx + offset) * c->es, bytes);
-        else std::memcpy(tmp, rslot, bytes);
+        // vals = srcs[0]; vals = fn(vals, srcs[1]) with srcs = [input?, recv?];
+        // PreMulSum: the input operand goes through pre first; SumPostDiv: the
+        // final reducing call (input and FIFO in, output out) posts the value
+        // that goes to every destination (ring_kernel.h stream_slice)
+        const bool pre = c->op == mccsDevPreMulSum && SRC;
+        const int fn = c->op > mccsDevMin ? mccsDevSum : c->op;
+        const char* in0 = input + (srcIx + offset) * c->es;
+        if (pre) pre_apply(c->dt, c->op_arg, tmp, in0, (size_t)real);
+        if (SRC && RECV) apply(c->dt, fn, tmp, pre ? tmp : in0, rslot, (size_t)real);
+        else if (SRC && !pre) std::memcpy(tmp, in0, bytes);
+        else if (!SRC) std::memcpy(tmp, rslot, bytes);
+        if (c->op == mccsDevSumPostDiv && SRC && RECV && DST) post_apply(c->dt, c->op_arg, tmp, (size_t)real);
         if (DST) std::memcpy(output + (dstIx + offset) * c->es, tmp, bytes);
         if (SEND) std::memcpy(sslot, tmp, bytes);
       }
@@ -443,15 +474,25 @@ class HostRingPool {
 
 static mccsResult_t host_ring_run(int func, int nranks, const void* const* sendbufs, void* const* recvbufs,
                                   size_t count, int dtype, int op, int nchannels, int nthreads_ref, int buff_size,
-                                  const int* rings, int root = 0) {
+                                  const int* rings, int root = 0, const uint64_t* op_arg = nullptr) {
   if (root < 0 || root >= nranks) return mccsInvalidArgument;
+  // the plain entry points (op_arg == nullptr) know Sum / Prod / Max / Min
   if (nranks < 1 || nranks > 64 || !sendbufs || !recvbufs || dtype < 0 || dtype >= mccsNumTypes || op < 0 ||
-      op > mccsDevMin || nchannels < 1 || nchannels > MCCS_MAX_NCHANNELS || nthreads_ref <= WARP_SIZE ||
-      buff_size < 8192 || buff_size % 8192)
+      op > (op_arg ? mccsDevSumPostDiv : mccsDevMin) || nchannels < 1 || nchannels > MCCS_MAX_NCHANNELS ||
+      nthreads_ref <= WARP_SIZE || buff_size < 8192 || buff_size % 8192)
     return mccsInvalidArgument;
   const size_t es = (size_t)mccs::elem_bytes(dtype);
+  const uint64_t arg = op_arg ? *op_arg : 0;
+  // the argument rules of the mccs*OpArg entry points (mccs_hip.h)
+  if (op <= mccsDevMin && arg != 0) return mccsInvalidArgument;
+  if (op == mccsDevPreMulSum && es < 8 && (arg >> (8 * es)) != 0) return mccsInvalidArgument;
+  if (op == mccsDevSumPostDiv && (!mccs::is_integer_dtype(dtype) || arg < 1 || arg > (uint64_t)INT32_MAX))
+    return mccsInvalidArgument;
   if (nranks == 1) {
     if (recvbufs[0] != sendbufs[0]) std::memmove(recvbufs[0], sendbufs[0], count * es);
+    // one rank: post(pre(x))
+    if (op == mccsDevPreMulSum) pre_apply(dtype, arg, recvbufs[0], recvbufs[0], count);
+    if (op == mccsDevSumPostDiv) post_apply(dtype, arg, recvbufs[0], count);
     return mccsSuccess;
   }
   HostRingPool& pool = HostRingPool::get();
@@ -463,6 +504,7 @@ static mccsResult_t host_ring_run(int func, int nranks, const void* const* sendb
   c.nch = nchannels;
   c.dt = dtype;
   c.op = op;
+  c.op_arg = arg;
   c.nthreads_ref = nthreads_ref;
   c.buff_size = buff_size;
   c.es = es;
@@ -503,4 +545,31 @@ extern "C" mccsResult_t mccs_host_ring_reduce(int nranks, const void* const* sen
                                               int nthreads_ref, int buff_size, const int* rings) {
   return host_ring_run(mccsFuncReduce, nranks, sendbufs, recvbufs, count, dtype, op, nchannels, nthreads_ref,
                        buff_size, rings, root);
+}
+
+// The three reducing collectives with an op argument: all six ops, PreMulSum's
+// scalar / SumPostDiv's divisor in op_arg under the rules of the mccs*OpArg
+// entry points; same schedule, pre and post applied where the kernels do.
+extern "C" mccsResult_t mccs_host_ring_allreduce_oparg(int nranks, const void* const* sendbufs, void* const* recvbufs,
+                                                       size_t count, int dtype, int op, int nchannels,
+                                                       int nthreads_ref, int buff_size, const int* rings,
+                                                       uint64_t op_arg) {
+  return host_ring_run(mccsFuncAllReduce, nranks, sendbufs, recvbufs, count, dtype, op, nchannels, nthreads_ref,
+                       buff_size, rings, 0, &op_arg);
+}
+
+extern "C" mccsResult_t mccs_host_ring_reduce_scatter_oparg(int nranks, const void* const* sendbufs,
+                                                            void* const* recvbufs, size_t recvcount, int dtype, int op,
+                                                            int nchannels, int nthreads_ref, int buff_size,
+                                                            const int* rings, uint64_t op_arg) {
+  return host_ring_run(mccsFuncReduceScatter, nranks, sendbufs, recvbufs, recvcount, dtype, op, nchannels,
+                       nthreads_ref, buff_size, rings, 0, &op_arg);
+}
+
+extern "C" mccsResult_t mccs_host_ring_reduce_oparg(int nranks, const void* const* sendbufs, void* const* recvbufs,
+                                                    size_t count, int dtype, int op, int root, int nchannels,
+                                                    int nthreads_ref, int buff_size, const int* rings,
+                                                    uint64_t op_arg) {
+  return host_ring_run(mccsFuncReduce, nranks, sendbufs, recvbufs, count, dtype, op, nchannels, nthreads_ref,
+                       buff_size, rings, root, &op_arg);
 }

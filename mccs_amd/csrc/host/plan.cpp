@@ -79,7 +79,7 @@ static void enqueue_elem(ChannelSchedule& s, const WorkElemHost& e, int func_ind
 }
 
 static mccsResult_t ring_enqueue(Comm* c, int func, int dtype, int op, const void* send, void* recv, size_t count,
-                                 int root = 0) {
+                                 int root = 0, uint64_t op_arg = 0) {
   const size_t esize = (size_t)elem_bytes(dtype);
   // task.rs:95-102.  ReduceScatter (not in the reference: task.rs stops at unimplemented!()) counts
   // like AllGather, the bytes that enter the ring: count is elements per block.  Broadcast (the int8
@@ -100,6 +100,7 @@ static mccsResult_t ring_enqueue(Comm* c, int func, int dtype, int op, const voi
     e.bid = (uint8_t)bid;
     e.nChannels = (uint8_t)nsel;
     e.root = (uint32_t)root;
+    e.op_arg = op_arg;
     enqueue_elem(c->sched[chans[bid]], e, /*funcIndex, unused (plan.rs:585)*/ 0,
                  func == mccsFuncAllGather ? 1 : esize);
   }
@@ -133,7 +134,7 @@ static bool ll_fits(const Comm* c, size_t bytes) {
 }
 
 mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send, void* recv, size_t count,
-                          int root) {
+                          int root, uint64_t op_arg) {
   if (c->plan_pending && (c->plan_func != func || c->plan_dtype != dtype || c->plan_op != op))
     // pre_launch_schedule batches same func/dtype/op only (plan.rs:122-141)
     MCCS_FAIL(mccsInvalidUsage, "a group mixes collectives of different function / dtype / op on one communicator");
@@ -150,8 +151,9 @@ mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send
   // (the LL one-shot makes no remote atomics: it runs without peer atomics,
   // the count-based variants need them).  A ReduceScatter, Broadcast or
   // Reduce always takes the ring: the direct variants are AllReduce /
-  // AllGather only.
-  if (!c->plan_pending && (func == mccsFuncAllReduce || func == mccsFuncAllGather) &&
+  // AllGather only.  So does a PreMulSum or SumPostDiv of any function and
+  // size: direct_kernel.h knows neither the pre nor the post step.
+  if (!c->plan_pending && (func == mccsFuncAllReduce || func == mccsFuncAllGather) && op <= mccsDevMin &&
       ((c->direct_ok && (oneshot || twoshot)) || ll)) {
     c->plan_direct = true;
     c->direct.send = send;
@@ -163,7 +165,7 @@ mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send
     c->plan_op = op;
     return mccsSuccess;
   }
-  return ring_enqueue(c, func, dtype, op, send, recv, count, root);
+  return ring_enqueue(c, func, dtype, op, send, recv, count, root, op_arg);
 }
 
 static mccsDevWork to_dev_work(const HostWork& elems, bool in_fifo, bool is_last, uint32_t u) {
@@ -179,7 +181,7 @@ static mccsDevWork to_dev_work(const HostWork& elems, bool in_fifo, bool is_last
     d.root = elems[i].root;
     d.bid = elems[i].bid;
     d.nChannels = elems[i].nChannels;
-    d.redOpArg = 0;
+    d.redOpArg = elems[i].op_arg;
   }
   w.header.funcIndex = 0;
   w.header.type = mccsDevWorkTypeColl;
@@ -445,12 +447,13 @@ int coresident_ring_blocks(int block, int device) {
   int ncu = 0;
   if (rt().CuCount(&ncu, device) != hipSuccess) return 0;
   int best = 1 << 30;
-  const void* fns[2 + 3 * mccsNumTypes * 4];
+  const void* fns[2 + 3 * mccsNumTypes * mccsNumDevRedOps];
   int nf = 0;
   fns[nf++] = ring_multi_kernel_ptr(mccsFuncAllGather, mccsInt8, 0);
   fns[nf++] = ring_multi_kernel_ptr(mccsFuncBoadcast, mccsInt8, 0);
   for (int dt = 0; dt < mccsNumTypes; ++dt)
-    for (int op = 0; op < 4; ++op) {
+    for (int op = 0; op < mccsNumDevRedOps; ++op) {
+      if (op == mccsDevSumPostDiv && !is_integer_dtype(dt)) continue;  // no such kernel
       fns[nf++] = ring_multi_kernel_ptr(mccsFuncAllReduce, dt, op);
       fns[nf++] = ring_multi_kernel_ptr(mccsFuncReduceScatter, dt, op);
       fns[nf++] = ring_multi_kernel_ptr(mccsFuncReduce, dt, op);

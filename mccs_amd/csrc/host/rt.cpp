@@ -422,7 +422,7 @@ class FakeRuntime final : public DeviceRuntime {
         for (unsigned k = 0; k < grid.y; ++k) on_dev = on_dev && dev_of(ma->comm[k]) == cur_;
         inl = ma->inline_works;
         extra = " fence=" + std::to_string(ma->cfg.fence_mode) + " guard_order=" + std::to_string(ma->guard_order) +
-                " no_guard=" + std::to_string(ma->cfg.no_guard);
+                " no_guard=" + std::to_string(ma->cfg.no_guard) + " redop_args=" + redop_args(ma, grid.y);
       }
     }
     note("launch dev=" + std::to_string(cur_) + " grid=" + std::to_string(grid.x) + "x" + std::to_string(grid.y) +
@@ -430,6 +430,36 @@ class FakeRuntime final : public DeviceRuntime {
          " inline_works=" + std::to_string(inl) + " stop_event=" + std::to_string((uintptr_t)stop_) +
          " kind=" + (direct ? "direct" : "ring") + extra);
     return hipSuccess;
+  }
+  // redOpArg of every work element a ring launch carries, as the kernels would
+  // read them: rank slots in order, a slot's channels in mask order, a
+  // channel's works along workNext, a work's used elements; hex, '/' between
+  // rank slots, ',' between elements.
+  static std::string redop_args(const mccsMultiLaunchArgs* ma, unsigned nslots) {
+    std::string out;
+    char hex[24];
+    const int nch = __builtin_popcountll(ma->channelMask);
+    for (unsigned k = 0; k < nslots; ++k) {
+      if (k) out += "/";
+      bool first = true;
+      auto elem = [&](const mccsDevWorkElem& e) {
+        std::snprintf(hex, sizeof(hex), "%llx", (unsigned long long)e.redOpArg);
+        out += (first ? "" : ",") + std::string(hex);
+        first = false;
+      };
+      for (int i = 0; i < nch; ++i) {
+        if (ma->inline_works) {
+          elem(ma->inline_work[k * nch + i].elem);
+          continue;
+        }
+        if (!ma->work[k]) continue;
+        for (const mccsDevWork* w = ma->work[k] + i;; w = ma->work[k] + w->header.workNext) {
+          for (int j = 0; j < MCCS_MAX_WORK_ELEMENTS && w->elems[j].isUsed; ++j) elem(w->elems[j]);
+          if (w->header.isLast) break;
+        }
+      }
+    }
+    return out;
   }
   // Quiet fake: what a ring kernel reading its works from the work FIFO
   // does to the host (common.h:153-155): each channel's last work stores its

@@ -4,6 +4,8 @@
 // reduction op, compiled in parallel), the forty ReduceScatter kernels in
 // ring_rs_{sum,prod,max,min}.hip, the forty Reduce kernels in
 // ring_rd_{sum,prod,max,min}.hip and the Broadcast kernel in ring_bc.hip.
+// PreMulSum (ten types) and SumPostDiv (the six integer types) add
+// ring_{ar,rs,rd}_{premulsum,sumpostdiv}.hip: 48 more kernels.
 #include "ring_kernel.h"
 
 namespace mccs {
@@ -30,14 +32,20 @@ const void* ring_ar_kernel_Sum(int dtype, bool multi);
 const void* ring_ar_kernel_Prod(int dtype, bool multi);
 const void* ring_ar_kernel_Max(int dtype, bool multi);
 const void* ring_ar_kernel_Min(int dtype, bool multi);
+const void* ring_ar_kernel_PreMulSum(int dtype, bool multi);
+const void* ring_ar_kernel_SumPostDiv(int dtype, bool multi);
 const void* ring_rs_kernel_Sum(int dtype);
 const void* ring_rs_kernel_Prod(int dtype);
 const void* ring_rs_kernel_Max(int dtype);
 const void* ring_rs_kernel_Min(int dtype);
+const void* ring_rs_kernel_PreMulSum(int dtype);
+const void* ring_rs_kernel_SumPostDiv(int dtype);
 const void* ring_rd_kernel_Sum(int dtype);
 const void* ring_rd_kernel_Prod(int dtype);
 const void* ring_rd_kernel_Max(int dtype);
 const void* ring_rd_kernel_Min(int dtype);
+const void* ring_rd_kernel_PreMulSum(int dtype);
+const void* ring_rd_kernel_SumPostDiv(int dtype);
 const void* ring_bc_kernel();
 hipError_t ring_tu_rd_sum_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_rd_prod_read_profile(unsigned long long* out, bool reset);
@@ -52,11 +60,19 @@ hipError_t ring_tu_ar_sum_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_ar_prod_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_ar_max_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_ar_min_read_profile(unsigned long long* out, bool reset);
+hipError_t ring_tu_ar_premulsum_read_profile(unsigned long long* out, bool reset);
+hipError_t ring_tu_ar_sumpostdiv_read_profile(unsigned long long* out, bool reset);
+hipError_t ring_tu_rs_premulsum_read_profile(unsigned long long* out, bool reset);
+hipError_t ring_tu_rs_sumpostdiv_read_profile(unsigned long long* out, bool reset);
+hipError_t ring_tu_rd_premulsum_read_profile(unsigned long long* out, bool reset);
+hipError_t ring_tu_rd_sumpostdiv_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_ag_set_ref_watchdog(unsigned long long ticks);
 hipError_t ring_tu_ar_sum_set_ref_watchdog(unsigned long long ticks);
 hipError_t ring_tu_ar_prod_set_ref_watchdog(unsigned long long ticks);
 hipError_t ring_tu_ar_max_set_ref_watchdog(unsigned long long ticks);
 hipError_t ring_tu_ar_min_set_ref_watchdog(unsigned long long ticks);
+hipError_t ring_tu_ar_premulsum_set_ref_watchdog(unsigned long long ticks);
+hipError_t ring_tu_ar_sumpostdiv_set_ref_watchdog(unsigned long long ticks);
 
 static const void* ar_kernel(int dtype, int op, bool multi) {
   if (dtype < 0 || dtype >= mccsNumTypes) return nullptr;
@@ -65,6 +81,8 @@ static const void* ar_kernel(int dtype, int op, bool multi) {
     case OpProd: return ring_ar_kernel_Prod(dtype, multi);
     case OpMax: return ring_ar_kernel_Max(dtype, multi);
     case OpMin: return ring_ar_kernel_Min(dtype, multi);
+    case OpPreMulSum: return ring_ar_kernel_PreMulSum(dtype, multi);
+    case OpSumPostDiv: return ring_ar_kernel_SumPostDiv(dtype, multi);  // nullptr for a floating dtype
   }
   return nullptr;
 }
@@ -77,6 +95,8 @@ static const void* rs_kernel(int dtype, int op) {
     case OpProd: return ring_rs_kernel_Prod(dtype);
     case OpMax: return ring_rs_kernel_Max(dtype);
     case OpMin: return ring_rs_kernel_Min(dtype);
+    case OpPreMulSum: return ring_rs_kernel_PreMulSum(dtype);
+    case OpSumPostDiv: return ring_rs_kernel_SumPostDiv(dtype);
   }
   return nullptr;
 }
@@ -89,6 +109,8 @@ static const void* rd_kernel(int dtype, int op) {
     case OpProd: return ring_rd_kernel_Prod(dtype);
     case OpMax: return ring_rd_kernel_Max(dtype);
     case OpMin: return ring_rd_kernel_Min(dtype);
+    case OpPreMulSum: return ring_rd_kernel_PreMulSum(dtype);
+    case OpSumPostDiv: return ring_rd_kernel_SumPostDiv(dtype);
   }
   return nullptr;
 }
@@ -136,7 +158,9 @@ hipError_t ring_read_profile(unsigned long long* out, bool reset) {
       ring_tu_ar_max_read_profile, ring_tu_ar_min_read_profile, ring_tu_rs_sum_read_profile,
       ring_tu_rs_prod_read_profile, ring_tu_rs_max_read_profile, ring_tu_rs_min_read_profile,
       ring_tu_rd_sum_read_profile, ring_tu_rd_prod_read_profile, ring_tu_rd_max_read_profile,
-      ring_tu_rd_min_read_profile, ring_tu_bc_read_profile};
+      ring_tu_rd_min_read_profile, ring_tu_bc_read_profile, ring_tu_ar_premulsum_read_profile,
+      ring_tu_ar_sumpostdiv_read_profile, ring_tu_rs_premulsum_read_profile, ring_tu_rs_sumpostdiv_read_profile,
+      ring_tu_rd_premulsum_read_profile, ring_tu_rd_sumpostdiv_read_profile};
   for (auto rd : readers) {
     hipError_t e = rd(out, reset);
     if (e != hipSuccess) return e;
@@ -195,7 +219,8 @@ extern "C" mccsResult_t mccs_hip_set_ref_watchdog(int timeout_ms) {
       timeout_ms < 0 ? 0ull : (unsigned long long)(timeout_ms == 0 ? 600000 : timeout_ms) * 100000ull;
   hipError_t (*const set[])(unsigned long long) = {
       mccs::ring_tu_ag_set_ref_watchdog, mccs::ring_tu_ar_sum_set_ref_watchdog, mccs::ring_tu_ar_prod_set_ref_watchdog,
-      mccs::ring_tu_ar_max_set_ref_watchdog, mccs::ring_tu_ar_min_set_ref_watchdog};
+      mccs::ring_tu_ar_max_set_ref_watchdog, mccs::ring_tu_ar_min_set_ref_watchdog,
+      mccs::ring_tu_ar_premulsum_set_ref_watchdog, mccs::ring_tu_ar_sumpostdiv_set_ref_watchdog};
   for (auto f : set)
     if (f(ticks) != hipSuccess) {
       (void)hipGetLastError();

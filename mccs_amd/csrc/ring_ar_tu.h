@@ -19,12 +19,15 @@
     return multi ? (const void*)&ring_multi_kernel<mccsFuncAllReduce, DT, OPV>                             \
                  : (const void*)&mccsKernel_AllReduce_RING_SIMPLE_##OPN##_##TN;
 
-// Defines the kernels and mccs::ring_ar_kernel_<OPN>(dtype, multi).
-#define MCCS_AR_TU(OPN, OPV)                                     \
-  MCCS_RING_TYPES(MCCS_AR_KERNEL, OPN, OPV)                      \
+// Defines the kernels and mccs::ring_ar_kernel_<OPN>(dtype, multi) for the
+// element types TYPES lists (MCCS_RING_TYPES, or MCCS_RING_INT_TYPES for
+// SumPostDiv; nullptr for a type it does not list).
+#define MCCS_AR_TU_TYPES(OPN, OPV, TYPES)                        \
+  TYPES(MCCS_AR_KERNEL, OPN, OPV)                                \
   namespace mccs {                                               \
   const void* ring_ar_kernel_##OPN(int dtype, bool multi) {      \
-    switch (dtype) { MCCS_RING_TYPES(MCCS_AR_CASE, OPN, OPV) }   \
+    switch (dtype) { TYPES(MCCS_AR_CASE, OPN, OPV) }             \
     return nullptr;                                              \
   }                                                              \
   }
+#define MCCS_AR_TU(OPN, OPV) MCCS_AR_TU_TYPES(OPN, OPV, MCCS_RING_TYPES)

@@ -10,11 +10,14 @@
   case DT:                             \
     return (const void*)&ring_multi_kernel<mccsFuncReduce, DT, OPV>;
 
-// Defines mccs::ring_rd_kernel_<OPN>(dtype), which instantiates the kernels.
-#define MCCS_RD_TU(OPN, OPV)                                     \
+// Defines mccs::ring_rd_kernel_<OPN>(dtype), which instantiates the kernels,
+// for the element types TYPES lists (MCCS_RING_INT_TYPES for SumPostDiv;
+// nullptr for a type it does not list).
+#define MCCS_RD_TU_TYPES(OPN, OPV, TYPES)                        \
   namespace mccs {                                               \
   const void* ring_rd_kernel_##OPN(int dtype) {                  \
-    switch (dtype) { MCCS_RING_TYPES(MCCS_RD_CASE, OPN, OPV) }   \
+    switch (dtype) { TYPES(MCCS_RD_CASE, OPN, OPV) }             \
     return nullptr;                                              \
   }                                                              \
   }
+#define MCCS_RD_TU(OPN, OPV) MCCS_RD_TU_TYPES(OPN, OPV, MCCS_RING_TYPES)

@@ -57,10 +57,18 @@ __device__ __forceinline__ P uniform_ptr(P p) {
 // an empty slice, or an unaligned one, which takes the typed loop; every wave
 // of the workgroup decides alike).  Same operands and results as
 // reduce_copy_rows.
-template <int DT, int OP, int U, int NS, int ND, int NTMASK, int DP0 = kPlain, int DP1 = kPlain>
+//   PRE / POST  PreMulSum / SumPostDiv (dtypes.h): src0 is the user input and
+//         goes through pre_op before its first use / the value is the
+//         collective's finished one and goes through post_op before it is
+//         stored to every destination.  `arg` is the work element's redOpArg,
+//         wave-uniform.  Both compile away for every other op, whose code is
+//         what it was without them.
+template <int DT, int OP, int U, int NS, int ND, int NTMASK, int DP0 = kPlain, int DP1 = kPlain, bool PRE = false,
+          bool POST = false>
 __device__ __forceinline__ uint32_t reduce_copy_rows_dyn(const void* s0, const void* s1, void* d0, void* d1,
                                                          int64_t nelem, int tid, int nthr, uint32_t* ctr,
-                                                         uint32_t base) {
+                                                         uint32_t base, uint64_t arg = 0) {
+  constexpr bool kPre = PRE && kHasPre<OP>, kPost = POST && kHasPost<OP>;
   constexpr int PACK = kPackElems<DT>;
   constexpr int LP0 = (NTMASK & 1) ? kNonTemporal : kPlain;
   constexpr int LP1 = (NTMASK & 2) ? kNonTemporal : kPlain;
@@ -72,8 +80,10 @@ __device__ __forceinline__ uint32_t reduce_copy_rows_dyn(const void* s0, const v
   if (mis & 15) {  // unaligned: typed loop over every data thread (reference ReduceCopyMulti)
     for (int64_t e = tid; e < nelem; e += nthr) {
       T v = (NTMASK & 1) ? __builtin_nontemporal_load((const T*)s0 + e) : ((const T*)s0)[e];
+      if constexpr (kPre) v = pre_op<DT, OP>(v, arg);
       if constexpr (NS > 1)
         v = scalar_op<DT, OP>(v, (NTMASK & 2) ? __builtin_nontemporal_load((const T*)s1 + e) : ((const T*)s1)[e]);
+      if constexpr (kPost) v = post_op<DT, OP>(v, arg);
       ((T*)d0)[e] = v;
       if constexpr (ND > 1) ((T*)d1)[e] = v;
     }
@@ -110,9 +120,17 @@ __device__ __forceinline__ uint32_t reduce_copy_rows_dyn(const void* s0, const v
     // every load of the unit is issued before the first use (the scheduler
     // would otherwise interleave waits to save registers: fewer bytes in flight)
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (kPre) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) v[u] = pack_pre_op<DT, OP>(v[u], arg);
+    }
     if constexpr (NS > 1) {
 #pragma unroll
       for (int u = 0; u < U; ++u) v[u] = pack_op<DT, OP>(v[u], w[u]);
+    }
+    if constexpr (kPost) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) v[u] = pack_post_op<DT, OP>(v[u], arg);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) st16<DP0>(xk + lane + 64u * u, v[u]);
@@ -125,14 +143,18 @@ __device__ __forceinline__ uint32_t reduce_copy_rows_dyn(const void* s0, const v
   // pack), over every data thread
   for (uint32_t q = nunits * unit + (uint32_t)tid; q < npack; q += (uint32_t)nthr) {
     u32x4 v = ld16<LP0>(a + q);
+    if constexpr (kPre) v = pack_pre_op<DT, OP>(v, arg);
     if constexpr (NS > 1) v = pack_op<DT, OP>(v, ld16<LP1>(b + q));
+    if constexpr (kPost) v = pack_post_op<DT, OP>(v, arg);
     st16<DP0>(x + q, v);
     if constexpr (ND > 1) st16<DP1>(y + q, v);
   }
   for (int64_t e = (int64_t)npack * PACK + tid; e < nelem; e += nthr) {
     T v = (NTMASK & 1) ? __builtin_nontemporal_load((const T*)s0 + e) : ((const T*)s0)[e];
+    if constexpr (kPre) v = pre_op<DT, OP>(v, arg);
     if constexpr (NS > 1)
       v = scalar_op<DT, OP>(v, (NTMASK & 2) ? __builtin_nontemporal_load((const T*)s1 + e) : ((const T*)s1)[e]);
+    if constexpr (kPost) v = post_op<DT, OP>(v, arg);
     ((T*)d0)[e] = v;
     if constexpr (ND > 1) ((T*)d1)[e] = v;
   }
