@@ -38,7 +38,8 @@ What it drives: `RefDrivenRank.all_reduce` (one task per plan, one element
 per work, one work per channel: the shape bench.py times),
 `RefDrivenRank.all_gather` (the AllGather kernel, always a plan of its own)
 and `RefDrivenRank.plan` (pre_launch_schedule's batch, plan.rs:111-169:
-consecutive AllReduce tasks of one dtype and op in one launch, channels
+consecutive AllReduce tasks of one dtype and op in one launch, each with its
+own redOpArg (PreMulSum's scalar, SumPostDiv's divisor; 0 otherwise), channels
 picked by running load so block id b need not sit on channel b, up to 10
 elements per work, a new work at every nWarps change, later works chained
 through workNext relative to the head, block = the largest nthreads).  The
@@ -322,7 +323,7 @@ class Plan:
 
 def plan_queues(tasks, nch: int, func: int = FUNC_ALLREDUCE, nranks: int = 1, schema=None):
     """pre_launch_schedule's merge of one plan's tasks (plan.rs:111-302):
-    tasks = [(send_ptr, recv_ptr, count, dtype)].  Per task get_task_schema
+    tasks = [(send_ptr, recv_ptr, count, dtype[, op_arg])].  Per task get_task_schema
     on its own bytes (count * n for an AllGather, task.rs:95-102),
     select_best_channels on this plan's running coll_bytes (ties by id), bid =
     position in the selection, and enqueue_work_elem_coll: an element joins
@@ -339,7 +340,8 @@ def plan_queues(tasks, nch: int, func: int = FUNC_ALLREDUCE, nranks: int = 1, sc
     load = [0] * nch
     queues = [[] for _ in range(nch)]
     per_task, block = [], 0
-    for t, (_, _, count, dtype) in enumerate(tasks):
+    for t, task in enumerate(tasks):
+        count, dtype = task[2], task[3]
         nbytes = count * ESIZE[dtype]
         k, nthr = schema(nbytes * nranks if func == FUNC_ALLGATHER else nbytes, nch)
         sel = sorted(range(nch), key=lambda i: (load[i], i))[:k]
@@ -361,7 +363,9 @@ def layout_works(tasks, queues, start: int, depth: int = WORK_DEPTH, reference_a
     first works, each non-last work's workNext = its successor's slot minus
     the head's slot (negative when the later works cross the ring's end),
     isLast + inFifo + doneAcks on each channel's last work (the reference
-    leaves inFifo clear on the others).  Returns (works, chans, nworks, acks)."""
+    leaves inFifo clear on the others).  A task's fifth field, where it has
+    one, is its redOpArg (work_elem_conversion, plan.rs:550-600: per element);
+    without it the field stays 0.  Returns (works, chans, nworks, acks)."""
     mask_q = depth - 1
     chans = [c for c in range(len(queues)) if queues[c]]
     nworks = [len(queues[c]) for c in chans]
@@ -383,6 +387,7 @@ def layout_works(tasks, queues, start: int, depth: int = WORK_DEPTH, reference_a
                 e.isUsed, e.nWarps = 1, nwarps
                 e.sendbuff, e.recvbuff, e.count = tasks[t][0], tasks[t][1], tasks[t][2]
                 e.bid, e.nChannels = bid, k
+                e.redOpArg = tasks[t][4] if len(tasks[t]) > 4 else 0
             if wid == 0:
                 at = start + nth
             else:
@@ -394,7 +399,7 @@ def layout_works(tasks, queues, start: int, depth: int = WORK_DEPTH, reference_a
 def build_plan(tasks, nch: int, next_available: int, depth: int = WORK_DEPTH, reference_acks: bool = False,
                func: int = FUNC_ALLREDUCE, nranks: int = 1, schema=None, reserve=None) -> Plan:
     """The host-only part of one plan, no GPU and no waiting: the tasks
-    ([(send_ptr, recv_ptr, count, dtype)], one dtype and op), the channel
+    ([(send_ptr, recv_ptr, count, dtype[, op_arg])], one dtype and op), the channel
     count and the ring's next_available in; the work structs and their slots
     out (see Plan).  `reserve(chans, nworks) -> (start, acks)` replaces the
     plain placement where a live ring has to wait for the slots
@@ -605,9 +610,11 @@ class RefDrivenRank:
     def _write_done(self, c, v):
         (ctypes.c_uint32 * abi.MCCS_MAX_NCHANNELS).from_address(self.h_done)[c] = v
 
-    def all_reduce(self, send_ptr: int, recv_ptr: int, count: int, dtype: int, op: int, stream: int) -> None:
+    def all_reduce(self, send_ptr: int, recv_ptr: int, count: int, dtype: int, op: int, stream: int,
+                   op_arg: int = 0) -> None:
         """One AllReduce task through plan.rs's path (one work element per
-        selected channel), launched on `stream`.  count = 0 launches nothing."""
+        selected channel), launched on `stream`.  count = 0 launches nothing.
+        `op_arg` goes into every element's redOpArg."""
         if count == 0:
             return
         nbytes = count * ESIZE[dtype]
@@ -622,7 +629,7 @@ class RefDrivenRank:
         chans = sorted(sorted(range(self.nch), key=lambda i: (load[i], i))[:k])
         mask_q = self.work_depth - 1
         start, acks = self.ring.reserve(chans, self._read_done, self._write_done)
-        key = (send_ptr, recv_ptr, count, k, nthr)
+        key = (send_ptr, recv_ptr, count, k, nthr, dtype, op, op_arg)
         works = self._works.get(key)
         if works is None:  # work_elem_conversion (plan.rs:550-600), built once per shape
             works = []
@@ -634,6 +641,7 @@ class RefDrivenRank:
                 e.isUsed, e.nWarps = 1, nthr // 32
                 e.sendbuff, e.recvbuff, e.count = send_ptr, recv_ptr, count
                 e.bid, e.nChannels = nth, k
+                e.redOpArg = op_arg
                 works.append(w)
             if len(self._works) > 64:
                 self._works.clear()
@@ -676,7 +684,9 @@ class RefDrivenRank:
     def plan(self, tasks, stream: int) -> Plan | None:
         """One batched plan, as pre_launch_schedule merges consecutive
         AllReduce tasks of one dtype and op (plan.rs:111-169): tasks =
-        [(send_ptr, recv_ptr, count, dtype, op)], zero counts dropped.
+        [(send_ptr, recv_ptr, count, dtype, op[, op_arg])], zero counts
+        dropped.  op_arg may differ from task to task: the scalar is per work
+        element, and the merge looks at func, dtype and op only.
         Returns the Plan; `last_tasks` holds per task (k, nthreads of that
         task, [rings[c] for c in its selection order]), from which the caller
         computes the expected values."""
@@ -686,7 +696,8 @@ class RefDrivenRank:
         dtype, op = tasks[0][3], tasks[0][4]
         if any(t[3] != dtype or t[4] != op for t in tasks):
             raise ValueError("one plan merges tasks of one dtype and op only")
-        p = self._launch_plan([t[:4] for t in tasks], FUNC_ALLREDUCE, dtype, op, stream)
+        p = self._launch_plan([tuple(t[:4]) + (t[5] if len(t) > 5 else 0,) for t in tasks], FUNC_ALLREDUCE, dtype, op,
+                              stream)
         self.last_tasks = [(k, nthr, [self.rings[c] for c in sel]) for k, nthr, sel in p.tasks]
         self.last_plan = self.last_tasks[-1]
         return p

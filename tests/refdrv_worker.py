@@ -22,7 +22,7 @@ so the 1024-entry work ring wraps and flow-controls on workFifoDone
 workFifoDone with doneAcks, and conn->step across ranks.
 
 REFDRV_MODE selects one of the further modes instead (class Modes below):
-allgather, batched, small, odd, edge.  Unset: the run described above.
+allgather, batched, small, odd, edge, avg.  Unset: the run described above.
 """
 import json
 import os
@@ -143,7 +143,7 @@ NTHR_OF_BUCKET = {5000: 96, 10000: 160, 20000: 288, 40000: 544}  # get_task_sche
 
 
 class Modes:
-    """REFDRV_MODE = allgather | batched | small | odd | edge: what plan.rs's
+    """REFDRV_MODE = allgather | batched | small | odd | edge | avg: what plan.rs's
     host side does beyond one aligned AllReduce per plan (see each method).
     Every mode runs on the reference ring with the FIFO at the sender and on a
     two-channel ring override with the FIFO at the receiver.  After every
@@ -535,6 +535,170 @@ class Modes:
                     kernels.add(self.calls[-1][:3])
             rr.close(self.dist.barrier)
         self.reach("all_40_kernels", kernels == {(4, code, op) for code in range(10) for op in range(4)})
+
+    # -- avg --------------------------------------------------------------------------
+    def mode_avg(self):
+        """The sixteen reference-named PreMulSum / SumPostDiv kernels, launched by
+        symbol with the scalar in each element's redOpArg, bit for bit against
+        tests/avg_ref.py: (a) edge values under both arguments of every pair,
+        (b) at n = 3 the inputs on which a fused multiply-add would show, (c) the
+        96-, 160-, 288- and 544-thread blocks in and out of place, (d) one plan
+        whose elements carry different scalars, two in one work and one in a
+        chained work, (e) misaligned buffers between guard bands, (f) six
+        launches of alternating ops on the same buffers.  The cases and what
+        makes each able to fail are tests/refdrv_avg_cases.py's, asserted there
+        before anything is launched (and on the CPU by
+        tests/test_refdrive_avg_cases.py)."""
+        import avg_ref as A
+        import refdrv_avg_cases as K
+        import vnode
+        from footprint import Guarded
+        from mccs_amd import _lib
+        from test_gpu_avg_values import diff
+
+        n, rank, st = self.n, self.rank, self.stream.cuda_stream
+        assert (K.OVERRIDE8, K.NTHR_OF_BUCKET) == (OVERRIDE8, NTHR_OF_BUCKET)
+        lib = _lib.load()
+        for code, op in A.PAIRS:
+            assert lib.mccs_hip_coll_kernel(4, code, op), (code, op)
+        for code in (6, 7, 8, 9):  # SumPostDiv is defined for the integer types only
+            assert not lib.mccs_hip_coll_kernel(4, code, A.SUMPOSTDIV), code
+
+        def one(rr, key, inputs, code, op, arg, exp, plan, inplace=False):
+            """One AllReduce alone in its plan; the output starts as NOT(expected)."""
+            x = inputs[rank]
+            send = self.dev_bytes(x)
+            recv = send if inplace else self.dev_bytes(~np.ascontiguousarray(exp[rank]).view(np.uint8))
+            self.barrier()
+            rr.all_reduce(send.data_ptr(), recv.data_ptr(), x.size, code, op, st, op_arg=arg)
+
+            def check():
+                why = ""
+                if tuple(rr.last_plan) != tuple(plan) or self.calls[-1] != (4, code, op, plan[0], plan[1]):
+                    why += f"plan {rr.last_plan} != {plan}, launch {self.calls[-1]} "
+                why += diff(code, vnode.from_dev(recv, code), exp[rank])
+                if not inplace and not np.array_equal(send.cpu().numpy(), np.ascontiguousarray(x).view(np.uint8)):
+                    why += " source modified"
+                return why
+
+            self.finish(rr, key, check)
+
+        swept, rounded, blocks, two_scalars, chained_scalar = [], [], set(), [], []
+        for v in self.variants():
+            rr = self.open(v)
+            assert rr.buff == K.BUFF
+            # (a) edge values, all sixteen pairs under both arguments
+            kernels = set()
+            for code, op, arg in K.edge_cases(n):
+                inputs = K.edge_inputs(n, code)
+                if n == 2:  # the last chunk ends in a typed tail
+                    assert inputs[0].size % (16 // vnode.ESIZE[code]) != 0
+                plan = K.plan_of(rr.rings, inputs[0].nbytes)
+                exp = K.edge_expected(n, code, op, arg, plan, rr.buff)
+                one(rr, f"{v[0]}/edge/dtype{code}/op{op}/{arg:x}", inputs, code, op, arg, exp, plan)
+                kernels.add(self.calls[-1][:3])
+            swept.append(kernels == {(4, code, op) for code, op in A.PAIRS})
+            # (b) product and sum round separately
+            if n == 3:
+                for code in K.ROUNDING_CODES:
+                    inputs = K.rounding_inputs(code)
+                    plan = K.plan_of(rr.rings, inputs[0].nbytes)
+                    exp, told_apart = K.rounding_expected(code, plan, rr.buff)
+                    op, arg = A.avg_op(code, 3)
+                    one(rr, f"{v[0]}/rounding/dtype{code}", inputs, code, op, arg, exp, plan)
+                    rounded.append(self.calls[-1][:3] == (4, code, A.PREMULSUM) and min(told_apart) >= 0.10)
+            # (c) every block size, out of place and in place
+            for code, op, arg, nbytes, inputs in K.bucket_cases(n):
+                plan = K.plan_of(rr.rings, nbytes)
+                exp = K.bucket_expected(n, code, op, arg, nbytes, inputs, plan, rr.buff)
+                for inplace in (False, True):
+                    one(rr, f"{v[0]}/bucket/dtype{code}/{nbytes}/{'in' if inplace else 'out'}", inputs, code, op, arg,
+                        exp, plan, inplace)
+                    blocks.add((self.calls[-1][1], self.calls[-1][2], self.calls[-1][4], inplace))
+            # (d) one plan, a scalar per element
+            for code, op in K.BATCH_ARGS:
+                tasks = K.batch_tasks(n, code, op)
+                plans = K.batch_plans(rr.rings, code, op)
+                exp = K.batch_expected(n, code, op, plans, rr.buff)
+                send = [self.dev_bytes(inputs[rank]) for _, _, inputs in tasks]
+                recv = [self.dev_bytes(~np.ascontiguousarray(e[rank]).view(np.uint8)) for e in exp]
+                self.barrier()
+                p = rr.plan([(send[t].data_ptr(), recv[t].data_ptr(), tasks[t][0], code, op, tasks[t][1])
+                             for t in range(len(tasks))], st)
+
+                def check():
+                    why = ""
+                    if [tuple(t) for t in rr.last_tasks] != [tuple(pl) for pl in plans] or \
+                            self.calls[-1] != (4, code, op, 2, 544):
+                        why += f"plan {rr.last_tasks} != {plans}, launch {self.calls[-1]} "
+                    for t, (_, _, inputs) in enumerate(tasks):
+                        d = diff(code, vnode.from_dev(recv[t], code), exp[t][rank])
+                        if d:
+                            why += f"task {t}: {d} "
+                        if not np.array_equal(send[t].cpu().numpy(), np.ascontiguousarray(inputs[rank]).view(np.uint8)):
+                            why += f"task {t}: source modified "
+                    return why
+
+                self.finish(rr, f"{v[0]}/batched/dtype{code}/op{op}", check)
+                first, later = p.works[1][1], p.works[2][1]  # channel 1's works: (at, work) in upload order
+                args = [arg for _, arg, _ in tasks]
+                two_scalars.append(p.nworks == [1, 2] and not first.header.isLast and first.elems[2].isUsed == 0
+                                   and [first.elems[i].redOpArg for i in range(2)] == args[1:3] and args[1] != args[2])
+                chained_scalar.append(p.works[2][0] == p.start + 2 and p.works[1][1].header.workNext == 2
+                                      and later.header.isLast and later.elems[0].redOpArg == args[3] != 0
+                                      and later.elems[0].nWarps * 32 == 160 and self.calls[-1][4] == 544)
+            # (e) both buffers one element past a 16-byte boundary, between guard bands
+            for code, op, arg, inputs in K.odd_cases(n):
+                es = vnode.ESIZE[code]
+                plan = K.plan_of(rr.rings, K.ODD_COUNT * es)
+                exp = K.odd_expected(n, code, op, arg, inputs, plan, rr.buff)
+                for inplace in (False, True):
+                    send = Guarded(K.ODD_COUNT * es, es, "cuda")
+                    send.write(inputs[rank])
+                    recv = send
+                    if not inplace:
+                        recv = Guarded(K.ODD_COUNT * es, es, "cuda")
+                        recv.prefill_not(exp[rank])
+                    assert send.ptr % 16 == es and recv.ptr % 16 == es
+                    self.barrier()
+                    rr.all_reduce(send.ptr, recv.ptr, K.ODD_COUNT, code, op, st, op_arg=arg)
+
+                    def check():
+                        why = diff(code, recv.read(vnode.NPDT[code]), exp[rank]) + " " + recv.pads_message()
+                        if recv is not send:
+                            why += send.source_message()
+                        if tuple(rr.last_plan) != tuple(plan):
+                            why += f" plan {rr.last_plan} != {plan}"
+                        return why.strip()
+
+                    self.finish(rr, f"{v[0]}/odd/dtype{code}/{'in' if inplace else 'out'}", check)
+            # (f) six launches of four translation units' kernels on the same buffers
+            inputs = K.sequence_inputs(n)
+            plan = K.plan_of(rr.rings, inputs[0].nbytes)
+            exps = K.sequence_expected(n, plan, rr.buff)
+            send, recv = self.dev_bytes(inputs[rank]), self.fill(inputs[0].nbytes)
+            for i, ((op, arg), exp) in enumerate(zip(K.SEQUENCE, exps)):
+                self.barrier()
+                rr.all_reduce(send.data_ptr(), recv.data_ptr(), K.SEQ_COUNT, K.I32, op, st, op_arg=arg)
+
+                def check():
+                    why = diff(K.I32, vnode.from_dev(recv, K.I32), exp[rank])
+                    if tuple(rr.last_plan) != tuple(plan) or self.calls[-1] != (4, K.I32, op, plan[0], plan[1]):
+                        why += f" plan {rr.last_plan} != {plan}, launch {self.calls[-1]}"
+                    if not np.array_equal(send.cpu().numpy(), inputs[rank].view(np.uint8)):
+                        why += " source modified"
+                    return why
+
+                self.finish(rr, f"{v[0]}/sequence/{i}/op{op}", check)
+            rr.close(self.dist.barrier)
+        self.reach("all_16_avg_kernels", len(swept) == 2 and all(swept))
+        if n == 3:
+            self.reach("rounding_fp16_bf16_fp32_fp64", len(rounded) == 8 and all(rounded))
+        self.reach("avg_nthr_96_160_288_544",
+                   blocks == {(code, op, nthr, inplace) for code, op in ((K.BF16, A.PREMULSUM), (K.I32, A.SUMPOSTDIV))
+                              for nthr in NTHR_OF_BUCKET.values() for inplace in (False, True)})
+        self.reach("two_scalars_in_one_work", len(two_scalars) == 4 and all(two_scalars))
+        self.reach("scalar_in_chained_work", len(chained_scalar) == 4 and all(chained_scalar))
 
 
 def big_case(torch, dist, refdrive, orc, rank, n, dev, allgather):

@@ -13,8 +13,9 @@ structures (conn->step persistence), with workFifoDone = doneAcks.
 
 test_reference_driven_modes runs the worker's further modes: the AllGather
 kernel, batched plans (several tasks per launch, chained works, a negative
-workNext), buckets smaller than the ring, misaligned guarded buffers and edge
-values.  Each asserts that the path it is for was reached.
+workNext), buckets smaller than the ring, misaligned guarded buffers, edge
+values, and the sixteen PreMulSum / SumPostDiv kernels with the scalar in each
+work element's redOpArg.  Each asserts that the path it is for was reached.
 """
 import json
 import os
@@ -70,19 +71,32 @@ REACHES = {
     # the guarded control saw exactly the extra element's bytes
     "odd": [f"{v}/control_reports_extra_bytes/dtype{code}" for v in VARIANTS for code in (6, 7)],
     "edge": ["all_40_kernels"],
+    # every PreMulSum / SumPostDiv symbol went to mccs_hip_launch_coll on every rank, each
+    # block size too, and one plan uploaded two scalars in one work and one in a chained work
+    "avg": ["all_16_avg_kernels", "avg_nthr_96_160_288_544", "two_scalars_in_one_work", "scalar_in_chained_work"],
 }
+# n = 3 only: with the scalar 1/3 a fused multiply-add would show (at n = 2 every product is exact)
+REACHES_AT = {("avg", 3): ["rounding_fp16_bf16_fp32_fp64"]}
 
 
 @pytest.mark.parametrize("mode,world", [("allgather", 2), ("allgather", 3), ("allgather", 4), ("batched", 3),
-                                        ("batched", 4), ("small", 3), ("odd", 3), ("edge", 2)])
+                                        ("batched", 4), ("small", 3), ("odd", 3), ("edge", 2), ("avg", 2),
+                                        ("avg", 3)])
 def test_reference_driven_modes(mode, world):
     """The rest of plan.rs's host side on the reference-named kernels: the
     AllGather kernel, batched plans with chained works, buckets smaller than
-    the ring, misaligned guarded buffers and edge values.  Exact comparisons
-    only; one worker launch per case."""
+    the ring, misaligned guarded buffers and edge values; "avg": the sixteen
+    PreMulSum / SumPostDiv kernels against tests/avg_ref.py (the cases are
+    tests/refdrv_avg_cases.py's).  Exact comparisons only; one worker launch
+    per case."""
     res = _run_worker(world, REFDRV_MODE=mode)
     assert res["all_ok"], {k: v for k, v in res.items() if k != "cases"} | {
         "failed": [k for k, ok in res["cases"].items() if not ok][:20]}
     assert res["world"] == world and res["mode"] == mode and res["launches"] > 0
-    for key in REACHES[mode]:
+    keys = REACHES[mode] + REACHES_AT.get((mode, world), [])
+    for key in keys:
         assert res["reached"].get(key) is True, (key, res["reached"])
+    if mode == "avg":
+        # per variant 32 edge launches, 4 rounding ones at n = 3, 16 bucket ones, 2 plans,
+        # 4 misaligned launches and the sequence's 6: every one of them was checked
+        assert len(res["cases"]) == 2 * (60 + (4 if world == 3 else 0)) + len(keys), len(res["cases"])

@@ -452,3 +452,165 @@ def test_host_segment_roundtrip_without_gpu(monkeypatch):
     finally:
         a.close()
     assert calls.count(("reg", 4 * 4096, refdrive.hipHostRegisterMapped)) == 2 and calls.count(("unreg",)) == 2
+
+
+# ---- redOpArg: PreMulSum's scalar / SumPostDiv's divisor, per work element ------------------
+def _golden():
+    import json
+    import os
+
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "abi_layout.json")) as f:
+        return json.load(f)
+
+
+def _raw_work(word0, last, elems):
+    """One mccsDevWork byte by byte from the golden layout alone: word0 is
+    workNext or doneAcks; elems = [(nWarps, send, recv, count, bid, nChannels, redOpArg)]."""
+    import struct
+
+    g = _golden()
+    b = bytearray(g["sizeof(mccsDevWork)"])
+    struct.pack_into("<I", b, 0, word0 & 0xFFFFFFFF)
+    b[6] = 3 if last else 0  # isLast | inFifo
+    b[g["mccsDevWorkHeader.type"]] = 1
+    for i, (nwarps, send, recv, count, bid, nch, arg) in enumerate(elems):
+        at = g["sizeof(mccsDevWorkHeader)"] + i * g["sizeof(mccsDevWorkElem)"]
+        b[at] = 1  # isUsed
+        b[at + g["mccsDevWorkElem.nWarps"]] = nwarps
+        struct.pack_into("<Q", b, at + g["mccsDevWorkElem.sendbuff"], send)
+        struct.pack_into("<Q", b, at + g["mccsDevWorkElem.recvbuff"], recv)
+        struct.pack_into("<Q", b, at + g["mccsDevWorkElem.count"], count)
+        b[at + g["mccsDevWorkElem.bid"]] = bid
+        b[at + g["mccsDevWorkElem.nChannels"]] = nch
+        struct.pack_into("<Q", b, at + g["mccsDevWorkElem.redOpArg"], arg)
+    return bytes(b)
+
+
+def _arg_at(work, i):
+    """redOpArg of element i, read from the raw work bytes at the golden offset."""
+    g = _golden()
+    assert g["mccsDevWorkElem.redOpArg"] == 40
+    at = g["sizeof(mccsDevWorkHeader)"] + i * g["sizeof(mccsDevWorkElem)"] + g["mccsDevWorkElem.redOpArg"]
+    return int.from_bytes(bytes(work)[at:at + 8], "little")
+
+
+# fp32 counts: 40 000 bytes (544 threads) load channel 0; the two 5 000-byte
+# tasks (96 threads) then share channel 1's first work; the 10 000-byte task
+# (160 threads) opens a chained second work there
+SCALAR_COUNTS = [10000, 1250, 1250, 2500]
+SCALARS = [0x3F400000, 0x3EAAAAAB, 0xFFFFFFFF00000007, None]  # the last task leaves op_arg out
+
+
+def _scalar_tasks(with_args):
+    return [t + ((a,) if with_args and a is not None else ()) for t, a in zip(_tasks(SCALAR_COUNTS), SCALARS)]
+
+
+@pytest.mark.parametrize("position", [0, 1024 + 9])
+def test_four_field_tasks_lay_out_the_same_bytes_as_before(position):
+    """The works of tasks without op_arg, against bytes written by hand from
+    tests/golden/abi_layout.json: what the bench's reference-driven leg uploads."""
+    tasks = _scalar_tasks(False)
+    assert all(len(t) == 4 for t in tasks)
+    p = refdrive.build_plan(tasks, 2, position)
+    (s0, r0, c0, _), (s1, r1, c1, _), (s2, r2, c2, _), (s3, r3, c3, _) = tasks
+    want = [(position, _raw_work(position + 3, True, [(17, s0, r0, c0, 0, 1, 0)])),
+            (position + 1, _raw_work(2, False, [(3, s1, r1, c1, 0, 1, 0), (3, s2, r2, c2, 0, 1, 0)])),
+            (position + 2, _raw_work(position + 3, True, [(5, s3, r3, c3, 0, 1, 0)]))]
+    assert [(at, bytes(w)) for at, w in p.works] == want
+    _check_plan(p, tasks, 2, refdrive.WORK_DEPTH)
+
+
+def test_build_plan_gives_every_element_its_own_red_op_arg():
+    tasks = _scalar_tasks(True)
+    assert [len(t) for t in tasks] == [5, 5, 5, 4]
+    p = refdrive.build_plan(tasks, 2, 7)
+    _check_plan(p, tasks, 2, refdrive.WORK_DEPTH)
+    (_, w0), (_, first), (_, chained) = p.works
+    assert p.nworks == [1, 2] and first.header.workNext == 2 and chained.header.isLast and p.block == 544
+    # two elements of one work, each with its own scalar, all 64 bits of it
+    assert [first.elems[i].isUsed for i in range(3)] == [1, 1, 0]
+    assert (_arg_at(first, 0), _arg_at(first, 1), _arg_at(first, 2)) == (SCALARS[1], SCALARS[2], 0)
+    assert (first.elems[0].redOpArg, first.elems[1].redOpArg) == (SCALARS[1], SCALARS[2])
+    assert _arg_at(w0, 0) == SCALARS[0]
+    # the chained work's task left op_arg out: 0
+    assert chained.elems[0].nWarps == 5 and _arg_at(chained, 0) == 0
+    # with a scalar, the chained work keeps it; nothing but the scalars differs from the plain layout
+    tasks[3] = tasks[3] + (0x40400000,)
+    q = refdrive.build_plan(tasks, 2, 7)
+    assert _arg_at(q.works[2][1], 0) == 0x40400000 and _arg_at(q.works[1][1], 1) == SCALARS[2]
+    plain = refdrive.build_plan(_scalar_tasks(False), 2, 7)
+    g = _golden()
+    for (at, w), (at0, w0) in zip(q.works, plain.works):
+        a, b = bytearray(bytes(w)), bytearray(bytes(w0))
+        for i in range(10):
+            lo = g["sizeof(mccsDevWorkHeader)"] + i * g["sizeof(mccsDevWorkElem)"] + g["mccsDevWorkElem.redOpArg"]
+            a[lo:lo + 8] = bytes(8)
+        assert at == at0 and a == b
+
+
+class _HostOnlyRank(refdrive.RefDrivenRank):
+    """RefDrivenRank's planner state without a GPU: the work ring in host
+    memory, launches recorded instead of made."""
+
+    def __init__(self, nch=2, depth=16):
+        import ctypes
+        import types
+
+        from mccs_amd import _lib, abi
+
+        real = _lib.load()
+        self.launched = []
+        self.lib = types.SimpleNamespace(
+            mccs_task_schema=real.mccs_task_schema,
+            mccs_hip_launch_coll=lambda *a: self.launched.append(a) or 0)
+        self.nch, self.n, self.work_depth = nch, 2, depth
+        self.rings = refdrive.reference_rings(2, nch)
+        self._work_mem = ctypes.create_string_buffer(abi.MCCS_WORK_SIZE * depth)
+        self._done_mem = (ctypes.c_uint32 * abi.MCCS_MAX_NCHANNELS)()
+        self.h_work = self.d_work = ctypes.addressof(self._work_mem)
+        self.h_done = ctypes.addressof(self._done_mem)
+        self.d_comm = 0
+        self.ring = refdrive.WorkRing(nch, depth)
+        self.launches, self._works = 0, {}
+
+    def work_at(self, slot):
+        from mccs_amd import abi
+
+        return self._work_mem.raw[slot * abi.MCCS_WORK_SIZE:(slot + 1) * abi.MCCS_WORK_SIZE]
+
+
+def test_all_reduce_uploads_the_scalar_of_this_call_not_of_an_earlier_one():
+    """Same buffers, count and schema, call after call: the works cache is
+    keyed by dtype, op and op_arg too, so each upload carries its own scalar."""
+    rr = _HostOnlyRank()
+    calls = [(2, 0, 0), (2, 4, 3), (2, 2, 0), (2, 5, 7), (2, 4, 0xFFFFFFFF), (2, 0, 0), (3, 4, 3), (2, 4, 3)]
+    for i, (dtype, op, arg) in enumerate(calls):
+        if arg:
+            rr.all_reduce(0x7000, 0x9000, 2503, dtype, op, 0, op_arg=arg)
+        else:
+            rr.all_reduce(0x7000, 0x9000, 2503, dtype, op, 0)
+        assert rr.launched[-1][:3] == (refdrive.FUNC_ALLREDUCE, dtype, op) and rr.launched[-1][6:8] == (1, 160)
+        w = rr.work_at(i % 16)
+        assert _arg_at(w, 0) == arg, (i, hex(_arg_at(w, 0)))
+        assert w == _raw_work(i + 1, True, [(5, 0x7000, 0x9000, 2503, 0, 1, arg)])
+        rr._write_done(0, i + 1)  # the kernel's acknowledgement
+    keys = list(rr._works)
+    assert len(keys) == len(set(calls)) == 6 and all(k[-3:] in set(calls) for k in keys)  # two calls came back
+
+
+def test_plan_refuses_mixed_ops_and_accepts_mixed_scalars():
+    rr = _HostOnlyRank()
+    a, b = (0x7000, 0x9000, 1250, 7, 4, 0x3EAAAAAB), (0x17000, 0x19000, 1250, 7, 4, 0x40400000)
+    with pytest.raises(ValueError, match="one dtype and op"):
+        rr.plan([a, (0x17000, 0x19000, 1250, 7, 5, 2)], 0)
+    with pytest.raises(ValueError, match="one dtype and op"):
+        rr.plan([a, (0x17000, 0x19000, 1250, 2, 4, 3)], 0)
+    assert not rr.launched
+    p = rr.plan([a, b, (0x27000, 0x29000, 1250, 7, 4)], 0)  # the third task without op_arg
+    assert rr.launched[-1][:3] == (refdrive.FUNC_ALLREDUCE, 7, 4) and len(rr.launched) == 1
+    # least-loaded channel first: tasks 0 and 2 on channel 0, task 1 on channel 1
+    assert [sel for _, _, sel in p.tasks] == [[0], [1], [0]] and p.nworks == [1, 1]
+    assert [_arg_at(rr.work_at(0), i) for i in range(3)] == [0x3EAAAAAB, 0, 0]
+    assert [_arg_at(rr.work_at(1), i) for i in range(2)] == [0x40400000, 0]
+    assert rr.work_at(0) == _raw_work(2, True, [(3, 0x7000, 0x9000, 1250, 0, 1, 0x3EAAAAAB),
+                                                (3, 0x27000, 0x29000, 1250, 0, 1, 0)])
