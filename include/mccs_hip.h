@@ -297,6 +297,46 @@ mccsResult_t mccsBroadcast(const void *sendbuff, void *recvbuff, size_t nbytes, 
                            hipStream_t stream);
 mccsResult_t mccsReduce(const void *sendbuff, void *recvbuff, size_t count, int dtype, int op, int root,
                         mccsComm_t comm, hipStream_t stream);
+/* AllToAll on the ring connections.  Not in the reference (its device ABI
+ * reserves point-to-point function ids only).  Byte-typed like mccsAllGather
+ * and mccsBroadcast: both buffers hold nranks * bytes_per_peer bytes, and after
+ * the call rank r's recvbuff[s*B + i] == rank s's sendbuff[r*B + i] for every
+ * rank s, s == r included (B = bytes_per_peer).
+ * Route, fixed when the communicator is created from its rings (DESIGN.md
+ * §3.2; mccsCommAllToAllRoute reports it).  One hop: when every ordered pair of
+ * ranks (s, t) is the arc s -> next of exactly m >= 1 channels, the same m for
+ * every pair -- the default rings of 2, 3, 4, 5, 7 and 8 ranks -- each channel
+ * carries only the block for its ring successor, the pair's block cut over its
+ * m channels as mccsAllGather cuts a block over m channels; every link carries
+ * only its own pair's bytes, and the call uses all the comm's channels
+ * whatever its size.  Relay: on any other ring set (the default rings of 6
+ * ranks, fewer channels than nranks - 1), or with MCCS_ALLTOALL_HOPS=relay in
+ * the environment when the communicator is created (every rank must agree, as
+ * for MCCS_GATE; mccsCommConnect refuses a mismatch), every channel the call
+ * selects (as mccsAllGather selects them) carries every pair's block hop by hop
+ * along its ring, FIFO slot to FIFO slot, touching no user buffer on the way.
+ * Rank r's own block is copied locally.
+ * Out of place only: overlapping sendbuff and recvbuff ranges are refused with
+ * mccsInvalidArgument (mccsGetLastErrorString names it).  sendbuff is never
+ * written; nothing outside [recvbuff, recvbuff + nranks*B) is written, at any
+ * alignment of either buffer.  bytes_per_peer == 0 succeeds and launches
+ * nothing; NULL buffers are refused with mccsInvalidArgument; nranks == 1 is a
+ * local copy.
+ * Otherwise as for mccsReduceScatter: stream-ordered, returns after launch; a
+ * communicator's collectives run in issue order whatever stream each is issued
+ * on; every launch takes the communicator's launch guard; ranks sharing a GPU
+ * run as one fused launch; the call may be captured into a HIP graph (the
+ * route lives in the captured work list); the watchdog and mccsCommAbort end a
+ * stuck kernel; several AllToAlls of one comm in one group are batched into one
+ * launch, and mixing it with another function on one comm in a group is refused
+ * with mccsInvalidUsage at mccsGroupEnd.  Always the ring (mccsCommLastAlgo
+ * reports MCCS_ALGO_RING), whatever the direct / one-shot / LL thresholds. */
+mccsResult_t mccsAllToAll(const void *sendbuff, void *recvbuff, size_t bytes_per_peer, mccsComm_t comm,
+                          hipStream_t stream);
+/* The comm's AllToAll route: info2[0] hops (1: one hop; nranks - 1: relay; 0
+ * for one rank), info2[1] m, the channels carrying each pair's block (one hop;
+ * 0 for the relay, where the call's size selects them). */
+mccsResult_t mccsCommAllToAllRoute(mccsComm_t comm, int *info2);
 /* PreMulSum, SumPostDiv and the average: the three reducing ring collectives
  * with an op argument.  The reference declares both ops (mccsDevPreMulSum = 4,
  * mccsDevSumPostDiv = 5, collectives.h:28-32; DECL2(AllReduce, PreMulSum /
@@ -497,6 +537,22 @@ mccsResult_t mccs_host_ring_broadcast(int nranks, const void *const *sendbufs, v
 mccsResult_t mccs_host_ring_reduce(int nranks, const void *const *sendbufs, void *const *recvbufs, size_t count,
                                    int dtype, int op, int root, int nchannels, int nthreads_ref, int buff_size,
                                    const int *rings);
+/* The AllToAll route of a ring set (rings: nchannels x nranks send orders, NULL
+ * = identity order on every channel), as mccsAllToAll derives it: hops and m
+ * as mccsCommAllToAllRoute reports them, and two nranks x nchannels tables (may
+ * be NULL): send_bid[r*nchannels + c] is the part of its successor's block rank
+ * r sends on channel c, recv_bid the part of its predecessor's block it
+ * receives there (one hop: the number of earlier channels with the same arc,
+ * so a connection's sender and receiver name the same part; relay: c). */
+mccsResult_t mccs_alltoall_route(int nranks, int nchannels, const int *rings, int force_relay, int *hops, int *m,
+                                 int *send_bid, int *recv_bid);
+/* The AllToAll schedule (mccsAllToAll) and the FIFO protocol on host threads
+ * over host memory: sendbufs[r] and recvbufs[r] hold nranks * bytes_per_peer
+ * bytes.  The route is mccs_alltoall_route's for these rings; a relay uses all
+ * nchannels. */
+mccsResult_t mccs_host_ring_all_to_all(int nranks, const void *const *sendbufs, void *const *recvbufs,
+                                       size_t bytes_per_peer, int nchannels, int nthreads_ref, int buff_size,
+                                       const int *rings, int force_relay);
 /* The three reducing schedules with an op argument (mccsAllReduceOpArg,
  * mccsReduceScatterOpArg, mccsReduceOpArg): all six ops, the same argument
  * rules, pre and post applied where the kernels apply them and rounded as they

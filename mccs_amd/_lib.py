@@ -107,6 +107,12 @@ SIGNATURES: dict[str, tuple] = {
     "mccsReduceScatter": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_int, _c_void_p, _c_void_p]),
     "mccsBroadcast": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_void_p, _c_void_p]),
     "mccsReduce": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),
+    "mccsAllToAll": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_void_p]),
+    "mccsCommAllToAllRoute": (_c_int, [_c_void_p, _P(_c_int)]),
+    "mccs_alltoall_route": (
+        _c_int, [_c_int, _c_int, _P(_c_int), _c_int, _P(_c_int), _P(_c_int), _P(_c_int), _P(_c_int)]),
+    "mccs_host_ring_all_to_all": (
+        _c_int, [_c_int, _P(_c_void_p), _P(_c_void_p), _c_size_t, _c_int, _c_int, _c_int, _P(_c_int), _c_int]),
     "mccsAllReduceOpArg": (
         _c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_int, ctypes.c_uint64, _c_void_p, _c_void_p]),
     "mccsReduceScatterOpArg": (

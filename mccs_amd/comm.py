@@ -10,6 +10,7 @@ Mirrors the reference application API (src/libmccs/src/lib.rs:19-27):
   all_gather(comm, send, recv, size, stream)    all_gather(comm, send, recv, size, stream)
   (none: ReduceScatter is declared but          reduce_scatter(comm, send, recv, recv_count, dtype,
    unimplemented, task.rs:95-102)                              op, stream)
+  (none: no all-to-all)                         all_to_all(comm, send, recv, nbytes, stream)
   (none: Broadcast and Reduce are declared,     broadcast(comm, send, recv, nbytes, root, stream)
    devcomm.h:11-12, and have no kernel)         reduce(comm, send, recv, count, dtype, op, root, stream)
   AllReduceDataType {Float16, Int32}            AllReduceDataType (+ Float32: the one API delta,
@@ -214,6 +215,17 @@ class Communicator:
                op_type=AllReduceOpType.Sum, root: int = 0, stream=None, op_arg: int | None = None) -> None:
         reduce(self, send_buf, recv_buf, count, data_type, op_type, root, stream, op_arg=op_arg)
 
+    def all_to_all(self, send_buf, recv_buf, nbytes: int, stream=None) -> None:
+        all_to_all(self, send_buf, recv_buf, nbytes, stream)
+
+    def all_to_all_route(self) -> dict:
+        """The comm's AllToAll route (mccsCommAllToAllRoute): hops (1: every
+        block goes straight to its ring successor; nranks - 1: relayed along the
+        rings) and m, the channels carrying each pair's block (0 for the relay)."""
+        info = (_ci * 2)()
+        _lib.check(_sig().mccsCommAllToAllRoute(self._h, info), "mccsCommAllToAllRoute")
+        return {"hops": info[0], "m": info[1]}
+
     def all_reduce_avg(self, send_buf, recv_buf, size: int, data_type=AllReduceDataType.Float32, stream=None) -> None:
         all_reduce_avg(self, send_buf, recv_buf, size, data_type, stream)
 
@@ -361,6 +373,14 @@ def reduce(comm: Communicator, send_buf, recv_buf, count: int, data_type=AllRedu
     _lib.check(rc, "mccsReduceOpArg")
 
 
+def all_to_all(comm: Communicator, send_buf, recv_buf, nbytes: int, stream=None) -> None:
+    """mccsAllToAll: `nbytes` bytes per peer; both buffers hold nranks * nbytes
+    bytes.  Afterwards rank r's recv[s*nbytes + i] is rank s's send[r*nbytes + i].
+    Out of place only.  Always the ring connections; stream-ordered."""
+    rc = _sig().mccsAllToAll(_ptr(send_buf), _ptr(recv_buf), int(nbytes), comm._h, _stream(stream))
+    _lib.check(rc, "mccsAllToAll")
+
+
 def avg_op(data_type, nranks: int) -> tuple[AllReduceOpType, int]:
     """mccsAvgOp: the (op, op_arg) that averages over nranks.  Floating types:
     PreMulSum with 1/nranks in the type's bits; integer types: SumPostDiv with
@@ -502,6 +522,37 @@ def host_ring_reduce(sendbufs, recvbufs, count: int, data_type, op_type=AllReduc
     _lib.check(rc, "mccs_host_ring_reduce")
 
 
+def alltoall_route(nranks: int, channels: int, rings=None, force_relay: bool = False) -> dict:
+    """mccs_alltoall_route (host-only): the AllToAll route of a ring set
+    (`channels` x nranks send orders; None = identity on every channel): hops,
+    m, and the per rank and channel send / receive parts as nranks x channels
+    lists."""
+    ro = None
+    if rings is not None:
+        flat = [int(v) for r in rings for v in r]
+        ro = (_ci * len(flat))(*flat)
+    hops, m = _ci(), _ci()
+    sb, rb = (_ci * (nranks * channels))(), (_ci * (nranks * channels))()
+    rc = _sig().mccs_alltoall_route(int(nranks), int(channels), ro, 1 if force_relay else 0, ctypes.byref(hops),
+                                    ctypes.byref(m), sb, rb)
+    _lib.check(rc, "mccs_alltoall_route")
+    cut = lambda t: [list(t[r * channels:(r + 1) * channels]) for r in range(nranks)]
+    return {"hops": hops.value, "m": m.value, "send_bid": cut(sb), "recv_bid": cut(rb)}
+
+
+def host_ring_all_to_all(sendbufs, recvbufs, nbytes: int, channels: int = 1, nthreads: int = 96,
+                         buffer_size: int = 1 << 22, rings=None, force_relay: bool = False) -> None:
+    """The AllToAll schedule on host threads over host memory (numpy arrays or
+    raw host pointers; no GPU): every buffer holds nranks * nbytes bytes."""
+    ro = None
+    if rings is not None:
+        flat = [int(v) for r in rings for v in r]
+        ro = (_ci * len(flat))(*flat)
+    rc = _sig().mccs_host_ring_all_to_all(len(sendbufs), _host_ptrs(sendbufs), _host_ptrs(recvbufs), int(nbytes),
+                                          channels, nthreads, buffer_size, ro, 1 if force_relay else 0)
+    _lib.check(rc, "mccs_host_ring_all_to_all")
+
+
 def ring_profile(device: int = 0, reset: bool = True) -> dict:
     """Per-slice timing of the ring kernels on `device` (MCCS_RING_PROFILE=1
     set before communicator init): slices, mean µs waiting for peer flags,
@@ -554,7 +605,8 @@ def ring_walk(func: int, nranks: int, channels: int, elem_bytes: int, nthreads: 
 
 
 __all__ = ["AllReduceDataType", "AllReduceOpType", "CommConfig", "Communicator", "init_all",
-           "init_communicator_rank", "all_reduce", "all_gather", "reduce_scatter", "broadcast", "reduce",
+           "init_communicator_rank", "all_reduce", "all_gather", "reduce_scatter", "broadcast", "reduce", "all_to_all",
+           "alltoall_route", "host_ring_all_to_all",
            "avg_op", "red_op_arg", "all_reduce_avg", "reduce_scatter_avg", "reduce_avg",
            "group", "default_rings", "task_schema",
            "direct_defaults", "ll_default", "ring_walk",

@@ -155,6 +155,18 @@ static mccsResult_t make_comm(int rank, int nranks, int device, const mccsCommCo
   if (const char* v = std::getenv("MCCS_INLINE_WORKS")) c->inline_works = std::atoi(v) != 0;
   // (at most 4096: a launch guard counts a slot's workgroups in 16 bits)
   if (const char* v = std::getenv("MCCS_DIRECT_BLOCKS")) c->direct_blocks = std::atoi(v) > 0 ? std::min(std::atoi(v), 4096) : 128;
+  // MCCS_ALLTOALL_HOPS=relay: AllToAll relays along the rings even where they
+  // allow one hop (read here, carried in the connect handle: every rank agrees)
+  if (const char* v = std::getenv("MCCS_ALLTOALL_HOPS")) c->a2a_force_relay = v[0] == 'r' || v[0] == 'R';
+  {
+    std::vector<int> flat, sb((size_t)nranks * c->nch), rb((size_t)nranks * c->nch);
+    for (const auto& r : c->rings) flat.insert(flat.end(), r.begin(), r.end());
+    alltoall_route(nranks, c->nch, flat.data(), c->a2a_force_relay, &c->a2a_hops, &c->a2a_m, sb.data(), rb.data());
+    for (int ch = 0; ch < c->nch; ++ch) {
+      c->a2a_send_bid.push_back((uint8_t)sb[(size_t)rank * c->nch + ch]);
+      c->a2a_recv_bid.push_back((uint8_t)rb[(size_t)rank * c->nch + ch]);
+    }
+  }
   c->block_threads = cfg.block_threads;
   // auto lanes: ~64 streaming workgroups per rank (128 at n = 2).  A lane's
   // throughput is bound by its per-slice latency chain (flag poll, loads,
@@ -214,6 +226,12 @@ static mccsResult_t launch_single(Comm* c, int func, int dtype, int op, const vo
   const bool need_send = func != mccsFuncBoadcast || c->rank == root;
   const bool need_recv = func != mccsFuncReduce || c->rank == root;
   if ((need_send && !send) || (need_recv && !recv)) return reject(mccsInvalidArgument, "null send or recv buffer");
+  if (func == MCCS_FUNC_ALLTOALL) {
+    // out of place only: the schedule reads blocks of sendbuff after it wrote others of recvbuff
+    const uintptr_t s0 = (uintptr_t)send, r0 = (uintptr_t)recv, len = (uintptr_t)count * (uintptr_t)c->nranks;
+    if (s0 < r0 + len && r0 < s0 + len)
+      return reject(mccsInvalidArgument, "mccsAllToAll: sendbuff and recvbuff overlap (the call is out of place only)");
+  }
   if ((func == mccsFuncAllReduce || func == mccsFuncReduceScatter || func == mccsFuncReduce) &&
       (dtype < 0 || dtype >= mccsNumTypes || op < 0 || op > (op_arg ? mccsDevSumPostDiv : mccsDevMin)))
     return reject(mccsInvalidArgument, "unknown dtype or reduction op");
@@ -229,7 +247,8 @@ static mccsResult_t launch_single(Comm* c, int func, int dtype, int op, const vo
     if (op == mccsDevSumPostDiv && (arg < 1 || arg > (uint64_t)INT32_MAX))
       return reject(mccsInvalidArgument, "SumPostDiv: op_arg (the divisor) outside 1..INT32_MAX");
   }
-  const char* const name = func == mccsFuncAllGather       ? "mccsAllGather"
+  const char* const name = func == MCCS_FUNC_ALLTOALL      ? "mccsAllToAll"
+                           : func == mccsFuncAllGather     ? "mccsAllGather"
                            : func == mccsFuncReduceScatter ? (op_arg ? "mccsReduceScatterOpArg" : "mccsReduceScatter")
                            : func == mccsFuncBoadcast      ? "mccsBroadcast"
                            : func == mccsFuncReduce        ? (op_arg ? "mccsReduceOpArg" : "mccsReduce")
@@ -443,6 +462,7 @@ extern "C" mccsResult_t mccsCommSetupRank(mccsComm_t* out, int rank, int nranks,
   h.slice_steps = c->slice_steps;
   h.block_threads = c->block_threads;
   h.gate_env = gate_env();
+  h.a2a_relay = c->a2a_force_relay ? 1 : 0;
   if (rt().DeviceGetPCIBusId(h.pci, sizeof(h.pci) - 1, device) != hipSuccess)
     std::snprintf(h.pci, sizeof(h.pci), "ordinal:%d", device);
   gethostname(h.host, sizeof(h.host) - 1);
@@ -475,6 +495,8 @@ static std::string handle_mismatch(const Comm* c, const ConnectHandle& h, const 
   // the node gate's collectives need every rank (a rank that skipped it
   // would leave the others in its vote until the watchdog)
   if (h.gate_env != mine.gate_env) return diff("MCCS_GATE", h.gate_env, mine.gate_env);
+  // both ends of every connection must walk the same AllToAll route
+  if (h.a2a_relay != mine.a2a_relay) return diff("MCCS_ALLTOALL_HOPS=relay", h.a2a_relay, mine.a2a_relay);
   return "";
 }
 
@@ -635,6 +657,20 @@ extern "C" mccsResult_t mccsBroadcast(const void* sendbuff, void* recvbuff, size
 extern "C" mccsResult_t mccsReduce(const void* sendbuff, void* recvbuff, size_t count, int dtype, int op, int root,
                                    mccsComm_t comm, hipStream_t stream) {
   return launch_single((Comm*)comm, mccsFuncReduce, dtype, op, sendbuff, recvbuff, count, stream, root);
+}
+
+extern "C" mccsResult_t mccsAllToAll(const void* sendbuff, void* recvbuff, size_t bytes_per_peer, mccsComm_t comm,
+                                     hipStream_t stream) {
+  return launch_single((Comm*)comm, MCCS_FUNC_ALLTOALL, mccsInt8, mccsDevSum, sendbuff, recvbuff, bytes_per_peer,
+                       stream);
+}
+
+extern "C" mccsResult_t mccsCommAllToAllRoute(mccsComm_t comm, int* info2) {
+  const Comm* c = (const Comm*)comm;
+  if (!c || !info2) return mccsInvalidArgument;
+  info2[0] = c->a2a_hops;
+  info2[1] = c->a2a_m;
+  return mccsSuccess;
 }
 
 extern "C" mccsResult_t mccsAllReduceOpArg(const void* sendbuff, void* recvbuff, size_t count, int dtype, int op,
@@ -844,6 +880,26 @@ extern "C" int mccs_default_rings(int nranks, int nch_req, int* out, int max_cha
   for (int c = 0; c < n; ++c)
     for (int i = 0; i < nranks; ++i) out[c * nranks + i] = rings[c][i];
   return n;
+}
+
+extern "C" mccsResult_t mccs_alltoall_route(int nranks, int nchannels, const int* rings, int force_relay, int* hops,
+                                            int* m, int* send_bid, int* recv_bid) {
+  if (nranks < 1 || nranks > 64 || nchannels < 1 || nchannels > MCCS_MAX_NCHANNELS || !hops || !m)
+    return mccsInvalidArgument;
+  std::vector<int> ident;
+  if (!rings) {  // identity order on every channel, as for the host rings
+    for (int c = 0; c < nchannels; ++c)
+      for (int i = 0; i < nranks; ++i) ident.push_back(i);
+    rings = ident.data();
+  }
+  for (int c = 0; c < nchannels; ++c) {
+    std::vector<int> s(rings + (size_t)c * nranks, rings + (size_t)(c + 1) * nranks);
+    std::sort(s.begin(), s.end());
+    for (int i = 0; i < nranks; ++i)
+      if (s[i] != i) return mccsInvalidArgument;  // not a permutation
+  }
+  alltoall_route(nranks, nchannels, rings, force_relay != 0, hops, m, send_bid, recv_bid);
+  return mccsSuccess;
 }
 
 extern "C" int mccs_ll_default(int nranks) { return default_ll_bytes(nranks); }

@@ -136,6 +136,7 @@ struct ConnectHandle {
   int32_t direct_bytes, oneshot_bytes, ll_bytes;
   int32_t fifo_slots, slice_steps, block_threads;
   int32_t gate_env;  // MCCS_GATE as this rank read it (-1 unset): every rank must run the node gate or none
+  int32_t a2a_relay;  // MCCS_ALLTOALL_HOPS=relay as this rank read it: both ends of a connection walk one route
   // PCI bus id of the rank's GPU: device ordinals are local to a process
   // (HIP_VISIBLE_DEVICES), so co-location and peer lookups use this
   char pci[32];
@@ -159,7 +160,7 @@ struct WorkElemHost {
   void* recv;
   size_t count;
   uint8_t bid, nChannels;
-  uint32_t root;  // Broadcast / Reduce: the root rank (0 otherwise)
+  uint32_t root;  // Broadcast / Reduce: the root rank; AllToAll: the route (ring_cfg.h MCCS_A2A_ROUTE); 0 otherwise
   uint64_t op_arg;  // PreMulSum's scalar / SumPostDiv's divisor (mccsDevWorkElem.redOpArg; 0 otherwise)
 };
 
@@ -310,6 +311,12 @@ struct Comm {
   // derive it from the same device set, so they agree.
   bool direct_ok = false;
   int last_algo = -1;    // MCCS_ALGO_* of the latest launch
+  // AllToAll route (plan.cpp alltoall_route, computed from the rings at
+  // creation): hops 1 with m channels per pair and this rank's per-channel
+  // send / receive parts, or hops nranks - 1 (relay; m = 0: chosen per call)
+  bool a2a_force_relay = false;  // MCCS_ALLTOALL_HOPS=relay, read at creation
+  int a2a_hops = 0, a2a_m = 0;
+  std::vector<uint8_t> a2a_send_bid, a2a_recv_bid;
   int slice_steps = ALLREDUCE_CHUNKSTEPS;  // FIFO steps per ring slice (MCCS_SLICE_STEPS=2: the reference's 2)
   // node gate (gate.cpp): a hand-off mode the gate stepped down to (-1: none;
   // MCCS_FENCE_UNCACHED_RELEASE or MCCS_FENCE_SYSTEM), whether it ran, the
@@ -350,6 +357,16 @@ void plan_discard(Comm* c);  // drops the pending plan
 // op_arg: the scalar of a PreMulSum / SumPostDiv (per work element too; 0 for the other ops)
 mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send, void* recv, size_t count,
                           int root = 0, uint64_t op_arg = 0);
+// The AllToAll route of a ring set (rings: nch x nranks send orders).  One hop
+// (hops = 1) when every ordered pair (s, t) is the arc s -> next of exactly m
+// >= 1 channels, the same m for every pair, and relay is not forced: send_bid /
+// recv_bid (nranks x nch) then give, per rank and channel, which of the m parts
+// of the pair's block the channel sends to its successor / receives from its
+// predecessor (the count of earlier channels with the same arc).  Otherwise the
+// relay: hops = nranks - 1, m = 0 (the channels are chosen per call, as for
+// AllGather), both tables the channel index.  nranks == 1: hops = 0.
+void alltoall_route(int nranks, int nch, const int* rings, bool force_relay, int* hops, int* m, int* send_bid,
+                    int* recv_bid);
 mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_t>& user_streams);
 // ring.hip
 const void* ring_kernel_ptr(int func, int dtype, int op);

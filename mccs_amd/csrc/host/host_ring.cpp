@@ -31,7 +31,13 @@
 #include "half_bits.h"
 #include "mccs_devcomm.h"
 #include "mccs_hip.h"
+#include "ring_cfg.h"
 #include "ring_walk.h"
+
+namespace mccs {
+void alltoall_route(int nranks, int nch, const int* rings, bool force_relay, int* hops, int* m, int* send_bid,
+                    int* recv_bid);  // plan.cpp: the one route, shared with the planner
+}
 
 namespace {
 
@@ -190,6 +196,10 @@ struct HostConn {  // one directed FIFO (rank -> next) of one channel
 struct Ctx {
   int func, n, nch, dt, op, nthreads_ref, buff_size, root;
   uint64_t op_arg;  // PreMulSum / SumPostDiv (0 otherwise)
+  // AllToAll: the route (plan.cpp alltoall_route); walk_nch = the channels a block is cut over
+  int a2a_hops = 0, walk_nch = 0;
+  const int* a2a_send_bid = nullptr;  // n x nch
+  const int* a2a_recv_bid = nullptr;
   size_t es, count;
   const void* const* send;
   void* const* recv;
@@ -229,9 +239,10 @@ struct RankChannel {
     ringIx = (pos - pos0 + n) % n;
     out = &(*c->conns)[ch * n + rank];
     in = &(*c->conns)[ch * n + prev];
-    mccs::ring_walk<int64_t>(w, c->func, n, c->nch, (int)c->es, c->nthreads_ref, c->buff_size, (int64_t)c->count);
+    const int walk_nch = c->walk_nch > 0 ? c->walk_nch : c->nch;
+    mccs::ring_walk<int64_t>(w, c->func, n, walk_nch, (int)c->es, c->nthreads_ref, c->buff_size, (int64_t)c->count);
     mccs::walk_guard(w);
-    parts = mccs::walk_parts<int64_t>(c->func, c->nch, n);
+    parts = mccs::walk_parts<int64_t>(c->func, walk_nch, n);
     stepSize = w.stepSize;
     input = (const char*)c->send[rank];
     output = (char*)c->recv[rank];
@@ -368,10 +379,36 @@ void walk_rooted(RankChannel& k) {
   }
 }
 
+// AllToAll (ring_walk.h a2a_call): count = bytes per peer; the
+// rank's own block is a local copy (channel 0 makes it), every other block
+// travels `d` hops: one send, d-1 recvSend relays, one recv.
+void walk_alltoall(RankChannel& k) {
+  const RingWalk<int64_t>& w = k.w;
+  const int n = k.n, hops = k.c->a2a_hops;
+  const int64_t size = w.size;
+  if (k.ch == 0) std::memcpy(k.output + (int64_t)k.rank * size, k.input + (int64_t)k.rank * size, (size_t)size);
+  const int64_t sbid = k.c->a2a_send_bid[k.rank * k.c->nch + k.ch], rbid = k.c->a2a_recv_bid[k.rank * k.c->nch + k.ch];
+  const int ncalls = mccs::a2a_calls_per_loop(hops);
+  for (int64_t g = 0; g < size; g += w.loopSize) {
+    const int64_t rcs = mccs::real_chunk_size(w, g, k.parts);
+    for (int j = 0; j < ncalls; ++j) {
+      int d;
+      const int role = mccs::a2a_call(j, &d);
+      const int64_t off = mccs::block_chunk_offset(g, role == mccs::kA2ARecv ? rbid : sbid, rcs);
+      const int64_t nelem = mccs::chunk_nelem(size, off, rcs);  // <= 0: empty calls
+      const int64_t src = off + (int64_t)k.user_rank(mccs::a2a_send_block(d)) * size;
+      const int64_t dst = off + (int64_t)k.user_rank(mccs::a2a_recv_block(n, d)) * size;
+      const bool S = role == mccs::kA2ASend, R = role == mccs::kA2ARecv;
+      if (!k.op(!S, !R, S, R, src, dst, nelem)) return;
+    }
+  }
+}
+
 // one (rank, channel) thread
 void run_rank_channel(Ctx* c, int rank, int ch) {
   RankChannel k(c, rank, ch);
-  if (c->func == mccsFuncReduceScatter) walk_reduce_scatter(k);
+  if (c->func == MCCS_FUNC_ALLTOALL) walk_alltoall(k);
+  else if (c->func == mccsFuncReduceScatter) walk_reduce_scatter(k);
   else if (c->func == mccsFuncBoadcast || c->func == mccsFuncReduce) walk_rooted(k);
   else walk_allreduce(k);
 }
@@ -474,7 +511,8 @@ class HostRingPool {
 
 static mccsResult_t host_ring_run(int func, int nranks, const void* const* sendbufs, void* const* recvbufs,
                                   size_t count, int dtype, int op, int nchannels, int nthreads_ref, int buff_size,
-                                  const int* rings, int root = 0, const uint64_t* op_arg = nullptr) {
+                                  const int* rings, int root = 0, const uint64_t* op_arg = nullptr,
+                                  bool a2a_force_relay = false) {
   if (root < 0 || root >= nranks) return mccsInvalidArgument;
   // the plain entry points (op_arg == nullptr) know Sum / Prod / Max / Min
   if (nranks < 1 || nranks > 64 || !sendbufs || !recvbufs || dtype < 0 || dtype >= mccsNumTypes || op < 0 ||
@@ -515,6 +553,21 @@ static mccsResult_t host_ring_run(int func, int nranks, const void* const* sendb
   c.root = root;
   c.conns = &conns;
   c.timeout_s = 60.0;
+  std::vector<int> ident, a2a_sb, a2a_rb;
+  if (func == MCCS_FUNC_ALLTOALL) {
+    if (!rings) {
+      for (int ch = 0; ch < nchannels; ++ch)
+        for (int i = 0; i < nranks; ++i) ident.push_back(i);
+    }
+    a2a_sb.resize((size_t)nranks * nchannels);
+    a2a_rb.resize((size_t)nranks * nchannels);
+    int m = 0;
+    mccs::alltoall_route(nranks, nchannels, rings ? rings : ident.data(), a2a_force_relay, &c.a2a_hops, &m,
+                         a2a_sb.data(), a2a_rb.data());
+    c.walk_nch = m > 0 ? m : nchannels;  // relay: every channel given, as the other host rings
+    c.a2a_send_bid = a2a_sb.data();
+    c.a2a_recv_bid = a2a_rb.data();
+  }
   pool.run(&c, nranks * nchannels);
   return c.failed.load() ? mccsTimeout : mccsSuccess;
 }
@@ -545,6 +598,20 @@ extern "C" mccsResult_t mccs_host_ring_reduce(int nranks, const void* const* sen
                                               int nthreads_ref, int buff_size, const int* rings) {
   return host_ring_run(mccsFuncReduce, nranks, sendbufs, recvbufs, count, dtype, op, nchannels, nthreads_ref,
                        buff_size, rings, root);
+}
+
+extern "C" mccsResult_t mccs_host_ring_all_to_all(int nranks, const void* const* sendbufs, void* const* recvbufs,
+                                                  size_t bytes_per_peer, int nchannels, int nthreads_ref,
+                                                  int buff_size, const int* rings, int force_relay) {
+  if (rings && nranks >= 1 && nranks <= 64 && nchannels >= 1 && nchannels <= MCCS_MAX_NCHANNELS)
+    for (int ch = 0; ch < nchannels; ++ch) {
+      uint64_t seen = 0;
+      for (int i = 0; i < nranks; ++i)
+        if (rings[ch * nranks + i] >= 0 && rings[ch * nranks + i] < nranks) seen |= 1ull << rings[ch * nranks + i];
+      if (seen != (nranks == 64 ? ~0ull : (1ull << nranks) - 1)) return mccsInvalidArgument;  // not a permutation
+    }
+  return host_ring_run(MCCS_FUNC_ALLTOALL, nranks, sendbufs, recvbufs, bytes_per_peer, mccsInt8, mccsDevSum,
+                       nchannels, nthreads_ref, buff_size, rings, 0, nullptr, force_relay != 0);
 }
 
 // The three reducing collectives with an op argument: all six ops, PreMulSum's

@@ -111,6 +111,75 @@ static mccsResult_t ring_enqueue(Comm* c, int func, int dtype, int op, const voi
   return mccsSuccess;
 }
 
+void alltoall_route(int nranks, int nch, const int* rings, bool force_relay, int* hops, int* m, int* send_bid,
+                    int* recv_bid) {
+  const int n = nranks;
+  // next[c][r], prev[c][r] from channel c's send order
+  std::vector<int> next((size_t)nch * n), prev((size_t)nch * n);
+  for (int c = 0; c < nch; ++c)
+    for (int i = 0; i < n; ++i) {
+      const int a = rings[c * n + i], b = rings[c * n + (i + 1) % n];
+      next[(size_t)c * n + a] = b;
+      prev[(size_t)c * n + b] = a;
+    }
+  // arcs[s][t]: channels on which s sends to t
+  std::vector<int> arcs((size_t)n * n, 0);
+  for (int c = 0; c < nch; ++c)
+    for (int r = 0; r < n; ++r) ++arcs[(size_t)r * n + next[(size_t)c * n + r]];
+  int per_pair = n > 1 ? arcs[1] : 0;  // pair (0, 1)
+  for (int s = 0; s < n; ++s)
+    for (int t = 0; t < n; ++t)
+      if (s != t && arcs[(size_t)s * n + t] != per_pair) per_pair = 0;
+  const bool one_hop = n > 1 && per_pair >= 1 && !force_relay;
+  *hops = one_hop ? 1 : n - 1;
+  *m = one_hop ? per_pair : 0;
+  for (int r = 0; r < n; ++r)
+    for (int c = 0; c < nch; ++c) {
+      int sb = c, rb = c;
+      if (one_hop) {
+        sb = rb = 0;
+        for (int k = 0; k < c; ++k) {
+          sb += next[(size_t)k * n + r] == next[(size_t)c * n + r];
+          rb += prev[(size_t)k * n + r] == prev[(size_t)c * n + r];
+        }
+      }
+      if (send_bid) send_bid[r * nch + c] = sb;
+      if (recv_bid) recv_bid[r * nch + c] = rb;
+    }
+}
+
+// AllToAll (count = bytes per peer).  One hop: every channel of the comm, each
+// with this rank's parts of its successor's / predecessor's block (every arc is
+// some pair's only way); only the thread count follows task_schema.  Relay:
+// the channels task_schema and select_channels pick, as for AllGather.
+static mccsResult_t a2a_enqueue(Comm* c, const void* send, void* recv, size_t count) {
+  int nch = 0, nthr = 0;
+  task_schema(count * (size_t)c->nranks, c->nch, &nch, &nthr);
+  const bool one_hop = c->a2a_hops == 1 && c->a2a_m >= 1;
+  int chans[MCCS_MAX_NCHANNELS];
+  int nsel = c->nch;
+  if (one_hop)
+    for (int i = 0; i < nsel; ++i) chans[i] = i;
+  else
+    nsel = select_channels(c, nch, chans);
+  for (int i = 0; i < nsel; ++i) {
+    WorkElemHost e{};
+    e.nWarps = (uint8_t)(nthr / WARP_SIZE);
+    e.send = send;
+    e.recv = recv;
+    e.count = count;
+    e.bid = one_hop ? c->a2a_send_bid[chans[i]] : (uint8_t)i;
+    e.nChannels = (uint8_t)(one_hop ? c->a2a_m : nsel);
+    e.root = MCCS_A2A_ROUTE(c->a2a_hops, one_hop ? c->a2a_recv_bid[chans[i]] : i, i, nsel);
+    enqueue_elem(c->sched[chans[i]], e, 0, 1);
+  }
+  c->plan_pending = true;
+  c->plan_func = MCCS_FUNC_ALLTOALL;
+  c->plan_dtype = mccsInt8;
+  c->plan_op = mccsDevSum;
+  return mccsSuccess;
+}
+
 void plan_discard(Comm* c) {
   for (auto& s : c->sched) s.reset();
   c->plan_pending = false;
@@ -165,6 +234,7 @@ mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send
     c->plan_op = op;
     return mccsSuccess;
   }
+  if (func == MCCS_FUNC_ALLTOALL) return a2a_enqueue(c, send, recv, count);
   return ring_enqueue(c, func, dtype, op, send, recv, count, root, op_arg);
 }
 
@@ -447,10 +517,11 @@ int coresident_ring_blocks(int block, int device) {
   int ncu = 0;
   if (rt().CuCount(&ncu, device) != hipSuccess) return 0;
   int best = 1 << 30;
-  const void* fns[2 + 3 * mccsNumTypes * mccsNumDevRedOps];
+  const void* fns[3 + 3 * mccsNumTypes * mccsNumDevRedOps];
   int nf = 0;
   fns[nf++] = ring_multi_kernel_ptr(mccsFuncAllGather, mccsInt8, 0);
   fns[nf++] = ring_multi_kernel_ptr(mccsFuncBoadcast, mccsInt8, 0);
+  fns[nf++] = ring_multi_kernel_ptr(MCCS_FUNC_ALLTOALL, mccsInt8, 0);
   for (int dt = 0; dt < mccsNumTypes; ++dt)
     for (int op = 0; op < mccsNumDevRedOps; ++op) {
       if (op == mccsDevSumPostDiv && !is_integer_dtype(dt)) continue;  // no such kernel

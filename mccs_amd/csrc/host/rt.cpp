@@ -423,6 +423,7 @@ class FakeRuntime final : public DeviceRuntime {
         inl = ma->inline_works;
         extra = " fence=" + std::to_string(ma->cfg.fence_mode) + " guard_order=" + std::to_string(ma->guard_order) +
                 " no_guard=" + std::to_string(ma->cfg.no_guard) + " redop_args=" + redop_args(ma, grid.y);
+        if (fn == ring_multi_kernel_ptr(MCCS_FUNC_ALLTOALL, mccsInt8, mccsDevSum)) extra += " a2a=" + a2a_routes(ma, grid.y);
       }
     }
     note("launch dev=" + std::to_string(cur_) + " grid=" + std::to_string(grid.x) + "x" + std::to_string(grid.y) +
@@ -445,6 +446,34 @@ class FakeRuntime final : public DeviceRuntime {
       auto elem = [&](const mccsDevWorkElem& e) {
         std::snprintf(hex, sizeof(hex), "%llx", (unsigned long long)e.redOpArg);
         out += (first ? "" : ",") + std::string(hex);
+        first = false;
+      };
+      for (int i = 0; i < nch; ++i) {
+        if (ma->inline_works) {
+          elem(ma->inline_work[k * nch + i].elem);
+          continue;
+        }
+        if (!ma->work[k]) continue;
+        for (const mccsDevWork* w = ma->work[k] + i;; w = ma->work[k] + w->header.workNext) {
+          for (int j = 0; j < MCCS_MAX_WORK_ELEMENTS && w->elems[j].isUsed; ++j) elem(w->elems[j]);
+          if (w->header.isLast) break;
+        }
+      }
+    }
+    return out;
+  }
+  // An AllToAll launch's route as its work elements carry it (ring_cfg.h
+  // MCCS_A2A_ROUTE), in redop_args' order: hops:bid:recv_bid:nChannels per
+  // element, '/' between rank slots, ',' between elements.
+  static std::string a2a_routes(const mccsMultiLaunchArgs* ma, unsigned nslots) {
+    std::string out;
+    const int nch = __builtin_popcountll(ma->channelMask);
+    for (unsigned k = 0; k < nslots; ++k) {
+      if (k) out += "/";
+      bool first = true;
+      auto elem = [&](const mccsDevWorkElem& e) {
+        out += (first ? "" : ",") + std::to_string(MCCS_A2A_HOPS(e.root)) + ":" + std::to_string(e.bid) + ":" +
+               std::to_string(MCCS_A2A_RECV_BID(e.root)) + ":" + std::to_string(e.nChannels);
         first = false;
       };
       for (int i = 0; i < nch; ++i) {

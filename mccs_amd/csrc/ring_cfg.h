@@ -79,6 +79,32 @@ struct mccsLaunchGuard {
   ((sizeof(struct mccsDevCommAndChannels) + MCCS_MAX_NCHANNELS * sizeof(struct mccsRingConnView) + 127) / \
    128 * 128)
 
+// ---- AllToAll (ring_a2a.hip, ring_walk.h a2a_call, host/plan.cpp) ----------
+// The function id is the library's own: the device ABI (mccsDevFunc_t) names
+// no all-to-all, and the id never leaves the library (it selects the kernel on
+// the host and the walk at compile time; work headers carry funcIndex 0).
+#define MCCS_FUNC_ALLTOALL 8  // == mccsNumFuncs: past every mccsDevFunc_t value
+// An AllToAll work element: count = bytes per peer, nChannels = m (the
+// channels a pair's block is cut over), bid = the part of the block this
+// channel SENDS, and mccsDevWorkElem.root, free for this function, holds the
+// rest of the route:
+//   bits  0..7   hops: the largest distance a loop walks.  1: the channel
+//                carries only the block for its ring successor (one hop);
+//                nranks - 1: every block, relayed along the ring
+//   bits  8..15  recv_bid: the part of the block this channel RECEIVES (one
+//                hop: counted from the receiver's side, it may differ from
+//                bid; relay: == bid)
+//   bits 16..23  part, bits 24..31 parts: the rank's own block, copied send ->
+//                recv without a FIFO step, is cut into `parts` pieces over the
+//                element's channels and this channel copies piece `part`
+// Captured graphs and batched groups carry the route with the element.
+#define MCCS_A2A_ROUTE(hops, recv_bid, part, parts) \
+  ((uint32_t)(hops) | (uint32_t)(recv_bid) << 8 | (uint32_t)(part) << 16 | (uint32_t)(parts) << 24)
+#define MCCS_A2A_HOPS(route) ((int)((route) & 0xffu))
+#define MCCS_A2A_RECV_BID(route) ((int)((route) >> 8 & 0xffu))
+#define MCCS_A2A_PART(route) ((int)((route) >> 16 & 0xffu))
+#define MCCS_A2A_PARTS(route) ((int)((route) >> 24 & 0xffu))
+
 // Per-device ring profile counters (s_memrealtime ticks, 100 MHz), summed
 // over every slice of every workgroup while mccsRingKernelCfg.profile is set.
 #define MCCS_PROF_SLICES 0  // slices executed

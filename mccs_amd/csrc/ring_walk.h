@@ -7,6 +7,9 @@
 // They all take the arithmetic from here, so "the ring's result, bit for bit"
 // cannot drift between them.  mccs_ring_walk (host/api.cpp) prints the walk
 // for tests/test_ring_walk.py, which holds it to the Python models.
+// AllToAll cuts a pair's block as AllGather cuts a block; which call of a loop
+// moves which block (a2a_call) is stated here too, for the kernel and the
+// host-thread ring alike.
 //
 // I is the integer type of the walk: int64_t for the ring and the host
 // paths, uint32_t for the direct kernels (direct_kernel.h says why).
@@ -122,6 +125,32 @@ __host__ __device__ __forceinline__ int allreduce_call_chunk(int ringIx, int n, 
   const int chunk = j <= n - 1 ? ringIx + n - 1 - j : ringIx + 2 * n - 1 - j;
   return chunk >= n ? chunk - n : chunk;
 }
+
+// AllToAll: the primitive calls of one loop (ring_cfg.h has the route a work
+// element carries).  For each distance d = 1 .. hops a rank
+//   sends its block for userRanks[d]                          (send),
+//   hands on the d-1 blocks that arrive for ranks beyond it   (recvSend: FIFO
+//     slot to FIFO slot, no user buffer),
+//   receives the block of userRanks[n-d] into its place       (recv).
+// The k-th block to arrive in phase d left the rank k hops back, so the d-th
+// is this rank's.  hops = 1 is the one-hop route (send to the successor,
+// receive from the predecessor); hops = n-1 the relay.
+enum : int { kA2ASend = 0, kA2ARelay = 1, kA2ARecv = 2 };
+__host__ __device__ __forceinline__ int a2a_calls_per_loop(int hops) { return hops * (hops + 3) / 2; }
+// Call j of a loop: its distance d and role.  Phase d holds d + 1 calls.
+__host__ __device__ __forceinline__ int a2a_call(int j, int* d_out) {
+  int d = 1;
+  while (j > d) {
+    j -= d + 1;
+    ++d;
+  }
+  *d_out = d;
+  return j == 0 ? kA2ASend : j == d ? kA2ARecv : kA2ARelay;
+}
+// Index into ring.userRanks of the block a call of distance d reads from the
+// send buffer (send) or writes in the receive buffer (recv).
+__host__ __device__ __forceinline__ int a2a_send_block(int d) { return d; }
+__host__ __device__ __forceinline__ int a2a_recv_block(int n, int d) { return n - d; }
 
 // Slice size of a primitive call of nelem elements (prims_simple.h:156-157):
 // sps steps per slice, spc slices per call.

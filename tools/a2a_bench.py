@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""Per-call time of AllToAll on the one-GPU virtual node: one hop, the relay
+(MCCS_ALLTOALL_HOPS=relay) and an AllGather of the same bytes per rank.
+
+An AllToAll of B bytes per peer moves n * B bytes out of and into every rank; an
+AllGather of B bytes per rank writes as many per rank.  A number for the record
+(DESIGN.md §3.2); it sets no pass mark.  Not the xGMI number: all ranks share
+one GPU's HBM (tools/vnode_bench.py), so the relay's extra link traffic costs
+here only its extra FIFO copies.
+
+  python tools/a2a_bench.py [--n 8] [--sizes-kib 64 1024] [--out FILE.jsonl]
+
+Every (n, size, mode) step runs in a fresh child process under its own time
+limit; the first step that fails or runs out of time ends the run.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def step(n, kib, iters):
+    """One step: AllToAll (the route the environment selects) and AllGather, the ring at every size."""
+    import torch
+
+    from mccs_amd import comm as C
+
+    comms = C.init_all([0] * n, C.CommConfig(direct_bytes=-1, oneshot_bytes=-1, ll_bytes=-1))
+    B = kib << 10
+    xs = [torch.randint(0, 255, (n * B,), dtype=torch.uint8, device="cuda") for _ in range(n)]
+    ys = [torch.empty(n * B, dtype=torch.uint8, device="cuda") for _ in range(n)]
+    calls = {
+        "alltoall": lambda r: C.all_to_all(comms[r], xs[r], ys[r], B),
+        "allgather": lambda r: C.all_gather(comms[r], xs[r], ys[r], B),
+    }
+    out = {"n": n, "KiB_per_peer": kib, "lanes": comms[0].lanes, "channels": comms[0].nchannels, "iters": iters,
+           **comms[0].all_to_all_route()}
+
+    def run(call, k):
+        for _ in range(k):
+            with C.group():
+                for r in range(n):
+                    call(r)
+        for c in comms:
+            c.sync()
+        torch.cuda.synchronize()
+
+    for name, call in calls.items():
+        run(call, 2)  # warm-up: code object load, steady FIFO state
+        t0 = time.perf_counter()
+        run(call, iters)
+        out[name + "_us"] = round((time.perf_counter() - t0) / iters * 1e6, 1)
+    out["alltoall_over_allgather"] = round(out["alltoall_us"] / out["allgather_us"], 2)
+    torch.cuda.synchronize()
+    for c in comms:
+        c.destroy()
+    print(json.dumps(out), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, nargs="+", default=[8])
+    ap.add_argument("--sizes-kib", type=int, nargs="+", default=[64, 1024])
+    ap.add_argument("--iters", type=int, default=200, help="timed calls per collective")
+    ap.add_argument("--step-timeout", type=int, default=120, help="seconds per step")
+    ap.add_argument("--out", default=None, help="also append the result lines to this file")
+    ap.add_argument("--step", type=int, nargs=2, default=None, help=argparse.SUPPRESS)  # child: n KiB
+    args = ap.parse_args()
+    if args.step:
+        step(args.step[0], args.step[1], args.iters)
+        return 0
+    for n in args.n:
+        for kib in args.sizes_kib:
+            for relay in (False, True):
+                env = dict(os.environ)
+                env.pop("MCCS_ALLTOALL_HOPS", None)
+                if relay:
+                    env["MCCS_ALLTOALL_HOPS"] = "relay"
+                cmd = ["timeout", "-k", "10", str(args.step_timeout), sys.executable, os.path.abspath(__file__),
+                       "--step", str(n), str(kib), "--iters", str(args.iters)]
+                r = subprocess.run(cmd, capture_output=True, text=True, env=env)
+                lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+                if r.returncode != 0 or not lines:
+                    print(f"step n={n} KiB={kib} relay={relay} failed (exit {r.returncode}); stopping\n"
+                          f"{r.stdout[-2000:]}{r.stderr[-2000:]}", file=sys.stderr)
+                    return 1
+                print(lines[-1], flush=True)
+                if args.out:
+                    with open(args.out, "a") as f:
+                        f.write(lines[-1] + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
