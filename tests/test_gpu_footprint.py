@@ -27,6 +27,7 @@ import footprint as F
 import ring_sim
 import vnode
 from footprint import Guarded
+from footprint_cases import assignments, gen, lane_parts, offset_set, ring_paths  # noqa: F401  (moved there)
 from mccs_amd import comm as C
 
 pytestmark = pytest.mark.gpu
@@ -38,18 +39,6 @@ NPDT, ESIZE = vnode.NPDT, vnode.ESIZE
 RING_ONLY = dict(direct_bytes=-1, oneshot_bytes=-1, ll_bytes=-1)
 DIRECT, LL_MAX = 8 << 20, 1 << 20
 DEV = "cuda"
-
-
-def gen(code, count, rng):
-    """Full-range integers (sums wrap), fp values with busy mantissas."""
-    if code in (F16, F32, F64):
-        return (rng.standard_normal(count) * 4).astype(NPDT[code])
-    info = np.iinfo(NPDT[code])
-    return rng.integers(info.min // 2, info.max // 2, count).astype(NPDT[code])
-
-
-def offset_set(es):
-    return sorted({0, es, 8, 16 - es})
 
 
 # =====================================================================================
@@ -284,21 +273,6 @@ def test_chunk_reduce_footprint_fans(orc, nsrcs, ndsts, alias):
 # =====================================================================================
 # (b), (c) collectives on the virtual node
 # =====================================================================================
-def assignments(n, es):
-    """(name, per-rank (send offset, receive offset), in place): every pair
-    of {0, es, 8, 16 - es} on all ranks alike, then offsets that differ per
-    rank, a single misaligned rank, and in place at nonzero offsets."""
-    offs = offset_set(es)
-    nz = [o for o in offs if o]
-    out = [(f"send+{s} recv+{r}", [(s, r)] * n, False) for s in offs for r in offs]
-    out.append(("per rank", [((r * es) % 16, offs[(r + 1) % len(offs)]) for r in range(n)], False))
-    out.append(("only the last rank's send", [(es if r == n - 1 else 0, 0) for r in range(n)], False))
-    out.append(("only rank 0's recv", [(0, 16 - es if r == 0 else 0) for r in range(n)], False))
-    out.append(("in place, per rank", [(nz[r % len(nz)],) * 2 for r in range(n)], True))
-    out.append(("in place, only rank 1", [(es if r == 1 else 0,) * 2 for r in range(n)], True))
-    return out
-
-
 def run_allreduce(comms, inputs, exp, code, offs, inplace, want_algo, count=None):
     """One grouped AllReduce on guarded buffers; returns {rank: what went wrong}."""
     n, nbytes = len(comms), exp.nbytes
@@ -337,57 +311,6 @@ def ring_chunks(n, count, nch, nthr, buff, es):
 
 def ring_loops(n, count, nch, nthr, buff, es):
     return len(list(ring_sim.rank_program(0, n, count, nch, 0, nthr, buff, es))) // (2 * n - 1)
-
-
-def lane_parts(c, es, lanes, buff, spc):
-    """Element counts of the parts ring_kernel.h's slice_ops cuts a chunk of c
-    elements into: spc slices per chunk (1 by default, 2 with the reference's
-    two-step slices), each over `lanes` workgroups at 256-byte multiples, a
-    lane never more than its fixed share of the slot group."""
-    step = buff // 8 // es
-    span = step * (4 // spc)
-    slice_size = max(-(-c // (16 * spc)) * 16, span // 32)
-    align = 256 // es
-    cap = span // lanes // align * align
-    out = []
-    for s in range(spc):
-        real = max(min(c - s * slice_size, slice_size), 0)
-        part = min(-(-(-(-real // lanes)) // align) * align, cap)
-        for lane in range(lanes):
-            lo = min(lane * part, real)
-            hi = real if lane == lanes - 1 else min(lo + part, real)
-            out.append(hi - lo)
-    assert sum(out) == c
-    return out
-
-
-def ring_paths(chunks, es, aligned, lanes, buff):
-    """The parts of reduce_copy_rows_dyn a bucket with these chunks reaches,
-    whichever slicing is configured.  A wave unit is 64 lanes x U packs with
-    U <= 8: a part of 16 KiB holds whole units, a part whose packs are no
-    multiple of 64 leaves remainder packs, for every U."""
-    out = set()
-    pack = 16 // es
-    if any(c <= 0 for c in chunks):
-        out.add("empty chunk")
-    if not aligned:
-        out.add("typed fallback")
-        return out
-    per_slicing = []
-    for spc in (1, 2):
-        got = set()
-        for c in chunks:
-            for p in lane_parts(c, es, lanes, buff, spc) if c > 0 else ():
-                if p * es >= 16 << 10:
-                    got.add("wave units")
-                if p // pack % 64:
-                    got.add("remainder packs")
-                if p % pack:
-                    got.add("typed tail")
-                if 0 < p < pack:
-                    got.add("no pack")
-        per_slicing.append(got)
-    return out | (per_slicing[0] & per_slicing[1])
 
 
 def sweep_ring(orc, comms, cases, buff=1 << 22, only=None, seed=0):
