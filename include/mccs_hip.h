@@ -337,6 +337,39 @@ mccsResult_t mccsAllToAll(const void *sendbuff, void *recvbuff, size_t bytes_per
  * for one rank), info2[1] m, the channels carrying each pair's block (one hop;
  * 0 for the relay, where the call's size selects them). */
 mccsResult_t mccsCommAllToAllRoute(mccsComm_t comm, int *info2);
+/* AllToAllv: AllToAll with per-peer byte counts and displacements (MPI's
+ * Alltoallv, in bytes).  Each of the four arrays has nranks entries, read by
+ * the host during the call (the caller may free them afterwards).  Rank r sends
+ * sendcounts[t] bytes from sendbuff + sdispls[t] to rank t and receives
+ * recvcounts[s] bytes from rank s at recvbuff + rdispls[s]; the self block
+ * (sendcounts[r] bytes) moves from sendbuff + sdispls[r] to recvbuff +
+ * rdispls[r] without a FIFO step.  The contract is MPI's: rank s's
+ * sendcounts[t] equals rank t's recvcounts[s].  Ranks that disagree stall until
+ * the watchdog or receive wrong bytes; like disagreeing roots this is not
+ * detected.  sendbuff is never written, and no byte of recvbuff outside the
+ * nranks receive segments is written, at any alignment.
+ * One hop only.  The call needs the one-hop AllToAll route (above): a channel
+ * then carries only its successor's block, so a pair's size is known to its
+ * two ranks and to nobody else.  On a relay route (the default rings of 6
+ * ranks, fewer channels than the one-hop set needs, a user ring set without
+ * the equal-m property, MCCS_ALLTOALL_HOPS=relay) a relaying rank would need
+ * the sizes of blocks that are neither its row nor its column, and the call is
+ * refused with mccsInvalidUsage; mccsGetLastErrorString names the route.
+ * Refused with mccsInvalidArgument: a NULL array; a NULL buffer with a non-zero
+ * count on that side; sendcounts[rank] != recvcounts[rank]; two receive
+ * segments of non-zero length that overlap; a receive segment that overlaps a
+ * send segment of non-zero length (the call is out of place).  Send segments
+ * may overlap each other: the same bytes may go to two peers.
+ * All counts zero: success, nothing is launched.  nranks == 1: the self copy
+ * only.  Always the ring: no direct threshold applies.  Every element runs
+ * with the schema's largest thread count (a pair's two ends know no common
+ * byte total to derive a smaller one from).  Graph capture: counts and
+ * displacements are baked into the captured work elements, and a replay
+ * repeats them.  Several calls of one comm in one group are batched into one
+ * launch; mixing with another function is refused as for mccsAllToAll.
+ * Otherwise as mccsAllToAll. */
+mccsResult_t mccsAllToAllv(const void *sendbuff, const size_t *sendcounts, const size_t *sdispls, void *recvbuff,
+                           const size_t *recvcounts, const size_t *rdispls, mccsComm_t comm, hipStream_t stream);
 /* PreMulSum, SumPostDiv and the average: the three reducing ring collectives
  * with an op argument.  The reference declares both ops (mccsDevPreMulSum = 4,
  * mccsDevSumPostDiv = 5, collectives.h:28-32; DECL2(AllReduce, PreMulSum /
@@ -553,6 +586,15 @@ mccsResult_t mccs_alltoall_route(int nranks, int nchannels, const int *rings, in
 mccsResult_t mccs_host_ring_all_to_all(int nranks, const void *const *sendbufs, void *const *recvbufs,
                                        size_t bytes_per_peer, int nchannels, int nthreads_ref, int buff_size,
                                        const int *rings, int force_relay);
+/* The AllToAllv schedule (mccsAllToAllv) on host threads over host memory:
+ * counts is the nranks x nranks byte matrix (counts[s*nranks + t]: what s sends
+ * to t), sdispls[r*nranks + t] and rdispls[r*nranks + s] each rank's
+ * displacement rows.  Refuses a ring set whose route is not one hop
+ * (mccsInvalidUsage). */
+mccsResult_t mccs_host_ring_all_to_all_v(int nranks, const void *const *sendbufs, void *const *recvbufs,
+                                         const size_t *counts, const size_t *sdispls, const size_t *rdispls,
+                                         int nchannels, int nthreads_ref, int buff_size, const int *rings,
+                                         int force_relay);
 /* The three reducing schedules with an op argument (mccsAllReduceOpArg,
  * mccsReduceScatterOpArg, mccsReduceOpArg): all six ops, the same argument
  * rules, pre and post applied where the kernels apply them and rounded as they

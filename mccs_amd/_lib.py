@@ -113,6 +113,12 @@ SIGNATURES: dict[str, tuple] = {
         _c_int, [_c_int, _c_int, _P(_c_int), _c_int, _P(_c_int), _P(_c_int), _P(_c_int), _P(_c_int)]),
     "mccs_host_ring_all_to_all": (
         _c_int, [_c_int, _P(_c_void_p), _P(_c_void_p), _c_size_t, _c_int, _c_int, _c_int, _P(_c_int), _c_int]),
+    "mccsAllToAllv": (
+        _c_int, [_c_void_p, _P(_c_size_t), _P(_c_size_t), _c_void_p, _P(_c_size_t), _P(_c_size_t), _c_void_p,
+                 _c_void_p]),
+    "mccs_host_ring_all_to_all_v": (
+        _c_int, [_c_int, _P(_c_void_p), _P(_c_void_p), _P(_c_size_t), _P(_c_size_t), _P(_c_size_t), _c_int, _c_int,
+                 _c_int, _P(_c_int), _c_int]),
     "mccsAllReduceOpArg": (
         _c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_int, ctypes.c_uint64, _c_void_p, _c_void_p]),
     "mccsReduceScatterOpArg": (

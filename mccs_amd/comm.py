@@ -11,6 +11,7 @@ Mirrors the reference application API (src/libmccs/src/lib.rs:19-27):
   (none: ReduceScatter is declared but          reduce_scatter(comm, send, recv, recv_count, dtype,
    unimplemented, task.rs:95-102)                              op, stream)
   (none: no all-to-all)                         all_to_all(comm, send, recv, nbytes, stream)
+  (none)                                        all_to_all_v(comm, send, scounts, sdispls, recv, rcounts, rdispls, stream)
   (none: Broadcast and Reduce are declared,     broadcast(comm, send, recv, nbytes, root, stream)
    devcomm.h:11-12, and have no kernel)         reduce(comm, send, recv, count, dtype, op, root, stream)
   AllReduceDataType {Float16, Int32}            AllReduceDataType (+ Float32: the one API delta,
@@ -25,6 +26,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import math
 import enum
 import time
 from dataclasses import dataclass
@@ -218,6 +220,10 @@ class Communicator:
     def all_to_all(self, send_buf, recv_buf, nbytes: int, stream=None) -> None:
         all_to_all(self, send_buf, recv_buf, nbytes, stream)
 
+    def all_to_all_v(self, send_buf, send_counts, send_displs, recv_buf, recv_counts, recv_displs,
+                     stream=None) -> None:
+        all_to_all_v(self, send_buf, send_counts, send_displs, recv_buf, recv_counts, recv_displs, stream)
+
     def all_to_all_route(self) -> dict:
         """The comm's AllToAll route (mccsCommAllToAllRoute): hops (1: every
         block goes straight to its ring successor; nranks - 1: relayed along the
@@ -379,6 +385,56 @@ def all_to_all(comm: Communicator, send_buf, recv_buf, nbytes: int, stream=None)
     Out of place only.  Always the ring connections; stream-ordered."""
     rc = _sig().mccsAllToAll(_ptr(send_buf), _ptr(recv_buf), int(nbytes), comm._h, _stream(stream))
     _lib.check(rc, "mccsAllToAll")
+
+
+def _sizes(vals):
+    if isinstance(vals, ctypes.Array) and vals._type_ is ctypes.c_size_t:  # marshalled once by the caller
+        return vals
+    vals = [int(v) for v in vals]
+    return (ctypes.c_size_t * max(1, len(vals)))(*vals)
+
+
+def all_to_all_v(comm: Communicator, send_buf, send_counts, send_displs, recv_buf, recv_counts, recv_displs,
+                 stream=None) -> None:
+    """mccsAllToAllv: per-peer byte counts and displacements (nranks entries
+    each, in bytes).  Rank r sends send_counts[t] bytes from send + send_displs[t]
+    to rank t and receives recv_counts[s] bytes from rank s at recv +
+    recv_displs[s].  One-hop AllToAll routes only (all_to_all_route); out of
+    place only; a buffer may be None when all its counts are 0.  A caller whose
+    sizes repeat may pass ctypes c_size_t arrays, which are used as they are."""
+    n = comm.nranks
+    for name, a in (("send_counts", send_counts), ("send_displs", send_displs), ("recv_counts", recv_counts),
+                    ("recv_displs", recv_displs)):
+        if a is not None and len(a) != n:
+            raise ValueError(f"{name} has {len(a)} entries for {n} ranks")
+    arr = lambda a: None if a is None else _sizes(a)
+    rc = _sig().mccsAllToAllv(_ptr(send_buf), arr(send_counts), arr(send_displs), _ptr(recv_buf), arr(recv_counts),
+                              arr(recv_displs), comm._h, _stream(stream))
+    _lib.check(rc, "mccsAllToAllv")
+
+
+def all_to_all_single(comm: Communicator, output, input, output_split_sizes=None, input_split_sizes=None,
+                      stream=None) -> None:
+    """torch.distributed.all_to_all_single's shape: splits run along dim 0 of
+    contiguous tensors, packed in rank order.  No splits: dim 0 is cut evenly
+    and the call is all_to_all."""
+    n = comm.nranks
+    if not (input.is_contiguous() and output.is_contiguous()):
+        raise ValueError("all_to_all_single needs contiguous tensors")
+    row = lambda t: math.prod(t.shape[1:]) * t.element_size()  # bytes of one dim-0 row
+    if output_split_sizes is None and input_split_sizes is None:
+        if input.shape[0] % n or output.numel() * output.element_size() != input.numel() * input.element_size():
+            raise ValueError("without splits dim 0 must divide by nranks and both tensors hold the same bytes")
+        all_to_all(comm, input, output, input.shape[0] // n * row(input), stream)
+        return
+    isp = [input.shape[0] // n] * n if input_split_sizes is None else [int(v) for v in input_split_sizes]
+    osp = [output.shape[0] // n] * n if output_split_sizes is None else [int(v) for v in output_split_sizes]
+    if len(isp) != n or len(osp) != n or sum(isp) != input.shape[0] or sum(osp) != output.shape[0]:
+        raise ValueError("split sizes must have nranks entries that sum to dim 0")
+    sc = [v * row(input) for v in isp]
+    rc = [v * row(output) for v in osp]
+    packed = lambda c: [sum(c[:i]) for i in range(n)]
+    all_to_all_v(comm, input, sc, packed(sc), output, rc, packed(rc), stream)
 
 
 def avg_op(data_type, nranks: int) -> tuple[AllReduceOpType, int]:
@@ -553,6 +609,24 @@ def host_ring_all_to_all(sendbufs, recvbufs, nbytes: int, channels: int = 1, nth
     _lib.check(rc, "mccs_host_ring_all_to_all")
 
 
+def host_ring_all_to_all_v(sendbufs, recvbufs, counts, send_displs, recv_displs, channels: int = 1,
+                           nthreads: int = 544, buffer_size: int = 1 << 22, rings=None,
+                           force_relay: bool = False) -> None:
+    """The AllToAllv schedule on host threads over host memory (no GPU).
+    counts[s][t] bytes go from sendbufs[s] + send_displs[s][t] to recvbufs[t] +
+    recv_displs[t][s].  A ring set whose route is not one hop is refused."""
+    n = len(sendbufs)
+    ro = None
+    if rings is not None:
+        flat = [int(v) for r in rings for v in r]
+        ro = (_ci * len(flat))(*flat)
+    flat2 = lambda m: _sizes([v for row in m for v in row])
+    rc = _sig().mccs_host_ring_all_to_all_v(n, _host_ptrs(sendbufs), _host_ptrs(recvbufs), flat2(counts),
+                                            flat2(send_displs), flat2(recv_displs), channels, nthreads, buffer_size,
+                                            ro, 1 if force_relay else 0)
+    _lib.check(rc, "mccs_host_ring_all_to_all_v")
+
+
 def ring_profile(device: int = 0, reset: bool = True) -> dict:
     """Per-slice timing of the ring kernels on `device` (MCCS_RING_PROFILE=1
     set before communicator init): slices, mean µs waiting for peer flags,
@@ -607,6 +681,7 @@ def ring_walk(func: int, nranks: int, channels: int, elem_bytes: int, nthreads: 
 __all__ = ["AllReduceDataType", "AllReduceOpType", "CommConfig", "Communicator", "init_all",
            "init_communicator_rank", "all_reduce", "all_gather", "reduce_scatter", "broadcast", "reduce", "all_to_all",
            "alltoall_route", "host_ring_all_to_all",
+           "all_to_all_v", "all_to_all_single", "host_ring_all_to_all_v",
            "avg_op", "red_op_arg", "all_reduce_avg", "reduce_scatter_avg", "reduce_avg",
            "group", "default_rings", "task_schema",
            "direct_defaults", "ll_default", "ring_walk",

@@ -276,6 +276,85 @@ static mccsResult_t launch_single(Comm* c, int func, int dtype, int op, const vo
   return mccsSuccess;
 }
 
+// A rejected call's diagnosis: inside a group the first failure is kept to GroupEnd.
+static mccsResult_t reject_call(mccsResult_t e, const char* why) {
+  const bool first = g_group.depth == 0 || g_group.error == mccsSuccess;
+  if (g_group.depth > 0 && first) g_group.error = e;
+  if (first) err_note(__FILE__, __LINE__, "%s", why);
+  return e;
+}
+
+// mccsAllToAllv: the argument rules of mccs_hip.h, then the plan.  *planned: something to launch.
+static mccsResult_t a2av_check_and_plan(Comm* c, const void* send, const size_t* sendcounts, const size_t* sdispls,
+                                        void* recv, const size_t* recvcounts, const size_t* rdispls,
+                                        hipStream_t stream, bool* planned) {
+  if (!sendcounts || !sdispls || !recvcounts || !rdispls)
+    return reject_call(mccsInvalidArgument, "null count or displacement array");
+  const int n = c->nranks, r = c->rank;
+  if (n > 1 && (c->a2a_hops != 1 || c->a2a_m < 1)) {
+    char why[256];
+    std::snprintf(why, sizeof(why),
+                  "the AllToAll route is not one hop (%s: hops = %d over %d channels of %d ranks); a relaying rank "
+                  "would need the sizes of blocks that are neither its row nor its column",
+                  c->a2a_force_relay ? "MCCS_ALLTOALL_HOPS=relay" : "relay", c->a2a_hops, c->nch, n);
+    return reject_call(mccsInvalidUsage, why);
+  }
+  size_t any_send = 0, any_recv = 0;
+  for (int i = 0; i < n; ++i) {
+    any_send |= sendcounts[i];
+    any_recv |= recvcounts[i];
+  }
+  if ((any_send && !send) || (any_recv && !recv))
+    return reject_call(mccsInvalidArgument, "null buffer with a non-zero count");
+  if (sendcounts[r] != recvcounts[r])
+    return reject_call(mccsInvalidArgument, "sendcounts[rank] != recvcounts[rank]");
+  const uintptr_t s0 = (uintptr_t)send, r0 = (uintptr_t)recv;
+  for (int i = 0; i < n; ++i) {
+    if (!recvcounts[i]) continue;
+    const uintptr_t a = r0 + rdispls[i], ae = a + recvcounts[i];
+    for (int j = 0; j < n; ++j) {
+      if (j > i && recvcounts[j] && a < r0 + rdispls[j] + recvcounts[j] && r0 + rdispls[j] < ae)
+        return reject_call(mccsInvalidArgument, "two receive segments overlap");
+      if (sendcounts[j] && a < s0 + sdispls[j] + sendcounts[j] && s0 + sdispls[j] < ae)
+        return reject_call(mccsInvalidArgument,
+                           "a receive segment overlaps a send segment (the call is out of place only)");
+    }
+  }
+  if (!any_send && !any_recv) return mccsSuccess;  // nothing moves: nothing is launched
+  if (std::find(g_group.comms.begin(), g_group.comms.end(), c) == g_group.comms.end()) {
+    g_group.comms.push_back(c);
+    g_group.streams.push_back(stream);
+  }
+  *planned = true;
+  const mccsResult_t er = plan_enqueue_a2av(c, send, sendcounts, sdispls, recv, recvcounts, rdispls);
+  if (er != mccsSuccess) {
+    if (g_group.depth == 0) group_discard();
+    else if (g_group.error == mccsSuccess) g_group.error = er;
+  }
+  return er;
+}
+
+static mccsResult_t launch_a2av(Comm* c, const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
+                                const size_t* recvcounts, const size_t* rdispls, hipStream_t stream) {
+  if (g_group.depth == 0) err_clear();
+  if (!c || !c->connected) return reject_call(mccsInvalidUsage, "the communicator is not connected");
+  if (c->failed) return reject_call(mccsRemoteError, "the communicator failed earlier (watchdog or abort): destroy it");
+  bool planned = false;
+  {
+    StepScope st("mccsAllToAllv");  // names the call in every diagnosis
+    const mccsResult_t er =
+        a2av_check_and_plan(c, send, sendcounts, sdispls, recv, recvcounts, rdispls, stream, &planned);
+    if (er != mccsSuccess || !planned) return er;
+  }
+  if (g_group.depth == 0) {
+    StepScope st("mccsAllToAllv launch");
+    const mccsResult_t r = plan_launch_group(g_group.comms, g_group.streams);
+    group_discard();
+    return r;
+  }
+  return mccsSuccess;
+}
+
 }  // namespace mccs
 
 using namespace mccs;
@@ -663,6 +742,12 @@ extern "C" mccsResult_t mccsAllToAll(const void* sendbuff, void* recvbuff, size_
                                      hipStream_t stream) {
   return launch_single((Comm*)comm, MCCS_FUNC_ALLTOALL, mccsInt8, mccsDevSum, sendbuff, recvbuff, bytes_per_peer,
                        stream);
+}
+
+extern "C" mccsResult_t mccsAllToAllv(const void* sendbuff, const size_t* sendcounts, const size_t* sdispls,
+                                      void* recvbuff, const size_t* recvcounts, const size_t* rdispls, mccsComm_t comm,
+                                      hipStream_t stream) {
+  return launch_a2av((Comm*)comm, sendbuff, sendcounts, sdispls, recvbuff, recvcounts, rdispls, stream);
 }
 
 extern "C" mccsResult_t mccsCommAllToAllRoute(mccsComm_t comm, int* info2) {

@@ -367,6 +367,10 @@ mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send
 // AllGather), both tables the channel index.  nranks == 1: hops = 0.
 void alltoall_route(int nranks, int nch, const int* rings, bool force_relay, int* hops, int* m, int* send_bid,
                     int* recv_bid);
+// AllToAllv on the one-hop route (the caller checked the route and the arguments):
+// per channel one element with both walks, plus the self block's element.
+mccsResult_t plan_enqueue_a2av(Comm* c, const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
+                               const size_t* recvcounts, const size_t* rdispls);
 mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_t>& user_streams);
 // ring.hip
 const void* ring_kernel_ptr(int func, int dtype, int op);

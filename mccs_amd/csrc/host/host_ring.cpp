@@ -200,6 +200,10 @@ struct Ctx {
   int a2a_hops = 0, walk_nch = 0;
   const int* a2a_send_bid = nullptr;  // n x nch
   const int* a2a_recv_bid = nullptr;
+  // AllToAllv: the n x n byte counts ([s * n + t]: s sends to t) and per-rank displacement rows
+  const size_t* v_counts = nullptr;
+  const size_t* v_sdispls = nullptr;  // [r * n + t]
+  const size_t* v_rdispls = nullptr;  // [r * n + s]
   size_t es, count;
   const void* const* send;
   void* const* recv;
@@ -404,10 +408,40 @@ void walk_alltoall(RankChannel& k) {
   }
 }
 
+// AllToAllv (ring_walk.h a2av_next): the channel's send walk
+// over the bytes for its successor and its receive walk over the bytes of its
+// predecessor, each of its own length; the self block is a local copy
+// (channel 0 makes it).
+void walk_alltoallv(RankChannel& k) {
+  const RingWalk<int64_t>& w = k.w;
+  const int n = k.n, r = k.rank;
+  const int t = k.user_rank(1), p = k.user_rank(n - 1);
+  const size_t* cnt = k.c->v_counts;
+  const size_t* sd = k.c->v_sdispls + (size_t)r * n;
+  const size_t* rd = k.c->v_rdispls + (size_t)r * n;
+  if (k.ch == 0 && cnt[(size_t)r * n + r]) std::memcpy(k.output + rd[r], k.input + sd[r], cnt[(size_t)r * n + r]);
+  const int64_t S = (int64_t)cnt[(size_t)r * n + t], R = (int64_t)cnt[(size_t)p * n + r];
+  const int64_t sbid = k.c->a2a_send_bid[r * k.c->nch + k.ch], rbid = k.c->a2a_recv_bid[r * k.c->nch + k.ch];
+  k.input += sd[t];
+  k.output += rd[p];
+  const int64_t ncalls = mccs::a2av_loops(S, w.loopSize) + mccs::a2av_loops(R, w.loopSize);
+  int64_t g = 0;
+  int side = mccs::a2av_first(S);
+  for (int64_t call = 0; call < ncalls; ++call) {
+    const bool recv = side == mccs::kA2AvRecv;
+    const int64_t size = recv ? R : S;
+    const int64_t rcs = mccs::a2av_chunk_size(w, size, g, k.parts);
+    const int64_t off = mccs::block_chunk_offset(g, recv ? rbid : sbid, rcs);
+    if (!k.op(recv, !recv, !recv, recv, off, off, mccs::chunk_nelem(size, off, rcs))) return;  // <= 0: an empty call
+    side = mccs::a2av_next(S, R, w.loopSize, &g, side);
+  }
+}
+
 // one (rank, channel) thread
 void run_rank_channel(Ctx* c, int rank, int ch) {
   RankChannel k(c, rank, ch);
-  if (c->func == MCCS_FUNC_ALLTOALL) walk_alltoall(k);
+  if (c->func == MCCS_FUNC_ALLTOALLV) walk_alltoallv(k);
+  else if (c->func == MCCS_FUNC_ALLTOALL) walk_alltoall(k);
   else if (c->func == mccsFuncReduceScatter) walk_reduce_scatter(k);
   else if (c->func == mccsFuncBoadcast || c->func == mccsFuncReduce) walk_rooted(k);
   else walk_allreduce(k);
@@ -612,6 +646,67 @@ extern "C" mccsResult_t mccs_host_ring_all_to_all(int nranks, const void* const*
     }
   return host_ring_run(MCCS_FUNC_ALLTOALL, nranks, sendbufs, recvbufs, bytes_per_peer, mccsInt8, mccsDevSum,
                        nchannels, nthreads_ref, buff_size, rings, 0, nullptr, force_relay != 0);
+}
+
+// AllToAllv on host threads: counts is the n x n byte matrix (counts[s * n + t]:
+// what s sends to t), sdispls / rdispls hold each rank's displacement row
+// (sdispls[r * n + t], rdispls[r * n + s]).  One hop only, as mccsAllToAllv.
+extern "C" mccsResult_t mccs_host_ring_all_to_all_v(int nranks, const void* const* sendbufs, void* const* recvbufs,
+                                                    const size_t* counts, const size_t* sdispls,
+                                                    const size_t* rdispls, int nchannels, int nthreads_ref,
+                                                    int buff_size, const int* rings, int force_relay) {
+  if (nranks < 1 || nranks > 64 || !sendbufs || !recvbufs || !counts || !sdispls || !rdispls || nchannels < 1 ||
+      nchannels > MCCS_MAX_NCHANNELS || nthreads_ref <= WARP_SIZE || buff_size < 8192 || buff_size % 8192)
+    return mccsInvalidArgument;
+  if (rings)
+    for (int ch = 0; ch < nchannels; ++ch) {
+      uint64_t seen = 0;
+      for (int i = 0; i < nranks; ++i)
+        if (rings[ch * nranks + i] >= 0 && rings[ch * nranks + i] < nranks) seen |= 1ull << rings[ch * nranks + i];
+      if (seen != (nranks == 64 ? ~0ull : (1ull << nranks) - 1)) return mccsInvalidArgument;  // not a permutation
+    }
+  if (nranks == 1) {
+    if (counts[0]) std::memmove((char*)recvbufs[0] + rdispls[0], (const char*)sendbufs[0] + sdispls[0], counts[0]);
+    return mccsSuccess;
+  }
+  std::vector<int> ident;
+  if (!rings)
+    for (int ch = 0; ch < nchannels; ++ch)
+      for (int i = 0; i < nranks; ++i) ident.push_back(i);
+  std::vector<int> sb((size_t)nranks * nchannels), rb((size_t)nranks * nchannels);
+  int hops = 0, m = 0;
+  mccs::alltoall_route(nranks, nchannels, rings ? rings : ident.data(), force_relay != 0, &hops, &m, sb.data(),
+                       rb.data());
+  if (hops != 1 || m < 1) return mccsInvalidUsage;  // a relay would need sizes that are neither its row nor its column
+  HostRingPool& pool = HostRingPool::get();
+  std::lock_guard<std::mutex> call(pool.call_mu);
+  std::vector<HostConn>& conns = pool.fifos((size_t)nchannels * nranks, (size_t)buff_size);
+  Ctx c;
+  c.func = MCCS_FUNC_ALLTOALLV;
+  c.n = nranks;
+  c.nch = nchannels;
+  c.dt = mccsInt8;
+  c.op = mccsDevSum;
+  c.op_arg = 0;
+  c.nthreads_ref = nthreads_ref;
+  c.buff_size = buff_size;
+  c.es = 1;
+  c.count = 0;  // each walk has its own size
+  c.send = sendbufs;
+  c.recv = recvbufs;
+  c.rings = rings;
+  c.root = 0;
+  c.conns = &conns;
+  c.timeout_s = 60.0;
+  c.a2a_hops = 1;
+  c.walk_nch = m;
+  c.a2a_send_bid = sb.data();
+  c.a2a_recv_bid = rb.data();
+  c.v_counts = counts;
+  c.v_sdispls = sdispls;
+  c.v_rdispls = rdispls;
+  pool.run(&c, nranks * nchannels);
+  return c.failed.load() ? mccsTimeout : mccsSuccess;
 }
 
 // The three reducing collectives with an op argument: all six ops, PreMulSum's

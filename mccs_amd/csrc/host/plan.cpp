@@ -180,6 +180,73 @@ static mccsResult_t a2a_enqueue(Comm* c, const void* send, void* recv, size_t co
   return mccsSuccess;
 }
 
+// AllToAllv (counts and displacements in bytes, validated by api.cpp; the
+// route is one hop).  Every channel of the comm runs: channel ch carries part
+// send_bid of the block for its successor t and part recv_bid of the block of
+// its predecessor p, so a pair's sizes stay between its two ranks.  The element
+// holds both walks (ring_walk.h a2av_next): count = sendcounts[t], redOpArg =
+// recvcounts[p], the buffers offset to the two segments.  The rank's own
+// block is a second element of the work (route hops = 0: no FIFO call).
+// The thread count is the schema's largest for every element of every rank:
+// the granule it sets cuts a pair's block, and the two ends of a connection
+// know no common byte total to derive a smaller one from.
+mccsResult_t plan_enqueue_a2av(Comm* c, const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
+                               const size_t* recvcounts, const size_t* rdispls) {
+  if (c->plan_pending && c->plan_func != MCCS_FUNC_ALLTOALLV)
+    MCCS_FAIL(mccsInvalidUsage, "a group mixes collectives of different function / dtype / op on one communicator");
+  const int n = c->nranks, r = c->rank;
+  const uint8_t nwarps = (uint8_t)((kSimpleMaxThreads + WARP_SIZE) / WARP_SIZE);
+  const size_t self = sendcounts[r];
+  if (n == 1) {  // the self copy only, cut as any one-rank call (ring_kernel.h local_copy)
+    int nch = 0, nthr = 0;
+    task_schema(self, c->nch, &nch, &nthr);
+    int chans[MCCS_MAX_NCHANNELS];
+    const int nsel = select_channels(c, nch, chans);
+    for (int i = 0; i < nsel; ++i) {
+      WorkElemHost e{};
+      e.nWarps = nwarps;
+      e.send = (const char*)send + sdispls[0];
+      e.recv = (char*)recv + rdispls[0];
+      e.count = self;
+      e.bid = (uint8_t)i;
+      e.nChannels = (uint8_t)nsel;
+      e.root = MCCS_A2A_ROUTE(0, 0, i, nsel);
+      enqueue_elem(c->sched[chans[i]], e, 0, 1);
+    }
+  } else {
+    if (c->a2a_hops != 1 || c->a2a_m < 1) return mccsInternalError;  // api.cpp refused it
+    for (int ch = 0; ch < c->nch; ++ch) {
+      const std::vector<int>& ring = c->rings[ch];
+      const int pos = (int)(std::find(ring.begin(), ring.end(), r) - ring.begin());
+      const int t = ring[(pos + 1) % n], p = ring[(pos + n - 1) % n];
+      WorkElemHost e{};
+      e.nWarps = nwarps;
+      e.send = (const char*)send + sdispls[t];
+      e.recv = (char*)recv + rdispls[p];
+      e.count = sendcounts[t];
+      e.op_arg = (uint64_t)recvcounts[p];
+      e.bid = c->a2a_send_bid[ch];
+      e.nChannels = (uint8_t)c->a2a_m;
+      e.root = MCCS_A2A_ROUTE(1, c->a2a_recv_bid[ch], 0, 0);
+      enqueue_elem(c->sched[ch], e, 0, 1);
+      if (self == 0) continue;
+      WorkElemHost s{};
+      s.nWarps = nwarps;
+      s.send = (const char*)send + sdispls[r];
+      s.recv = (char*)recv + rdispls[r];
+      s.count = self;
+      s.nChannels = 1;
+      s.root = MCCS_A2A_ROUTE(0, 0, ch, c->nch);
+      enqueue_elem(c->sched[ch], s, 0, 1);
+    }
+  }
+  c->plan_pending = true;
+  c->plan_func = MCCS_FUNC_ALLTOALLV;
+  c->plan_dtype = mccsInt8;
+  c->plan_op = mccsDevSum;
+  return mccsSuccess;
+}
+
 void plan_discard(Comm* c) {
   for (auto& s : c->sched) s.reset();
   c->plan_pending = false;
@@ -517,11 +584,12 @@ int coresident_ring_blocks(int block, int device) {
   int ncu = 0;
   if (rt().CuCount(&ncu, device) != hipSuccess) return 0;
   int best = 1 << 30;
-  const void* fns[3 + 3 * mccsNumTypes * mccsNumDevRedOps];
+  const void* fns[4 + 3 * mccsNumTypes * mccsNumDevRedOps];
   int nf = 0;
   fns[nf++] = ring_multi_kernel_ptr(mccsFuncAllGather, mccsInt8, 0);
   fns[nf++] = ring_multi_kernel_ptr(mccsFuncBoadcast, mccsInt8, 0);
   fns[nf++] = ring_multi_kernel_ptr(MCCS_FUNC_ALLTOALL, mccsInt8, 0);
+  fns[nf++] = ring_multi_kernel_ptr(MCCS_FUNC_ALLTOALLV, mccsInt8, 0);
   for (int dt = 0; dt < mccsNumTypes; ++dt)
     for (int op = 0; op < mccsNumDevRedOps; ++op) {
       if (op == mccsDevSumPostDiv && !is_integer_dtype(dt)) continue;  // no such kernel

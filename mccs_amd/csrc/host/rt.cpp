@@ -424,6 +424,8 @@ class FakeRuntime final : public DeviceRuntime {
         extra = " fence=" + std::to_string(ma->cfg.fence_mode) + " guard_order=" + std::to_string(ma->guard_order) +
                 " no_guard=" + std::to_string(ma->cfg.no_guard) + " redop_args=" + redop_args(ma, grid.y);
         if (fn == ring_multi_kernel_ptr(MCCS_FUNC_ALLTOALL, mccsInt8, mccsDevSum)) extra += " a2a=" + a2a_routes(ma, grid.y);
+        if (fn == ring_multi_kernel_ptr(MCCS_FUNC_ALLTOALLV, mccsInt8, mccsDevSum))
+          extra += " a2av=" + a2a_routes(ma, grid.y, true);
       }
     }
     note("launch dev=" + std::to_string(cur_) + " grid=" + std::to_string(grid.x) + "x" + std::to_string(grid.y) +
@@ -465,13 +467,24 @@ class FakeRuntime final : public DeviceRuntime {
   // An AllToAll launch's route as its work elements carry it (ring_cfg.h
   // MCCS_A2A_ROUTE), in redop_args' order: hops:bid:recv_bid:nChannels per
   // element, '/' between rank slots, ',' between elements.
-  static std::string a2a_routes(const mccsMultiLaunchArgs* ma, unsigned nslots) {
+  // An AllToAllv launch (v): route word (hex), bid, nChannels, count,
+  // redOpArg (the receive walk's bytes) and both buffers (hex), ':' between.
+  static std::string a2a_routes(const mccsMultiLaunchArgs* ma, unsigned nslots, bool v = false) {
     std::string out;
     const int nch = __builtin_popcountll(ma->channelMask);
     for (unsigned k = 0; k < nslots; ++k) {
       if (k) out += "/";
       bool first = true;
       auto elem = [&](const mccsDevWorkElem& e) {
+        if (v) {
+          char buf[160];
+          std::snprintf(buf, sizeof(buf), "%x:%u:%u:%llu:%llu:%llx:%llx", (unsigned)e.root, (unsigned)e.bid,
+                        (unsigned)e.nChannels, (unsigned long long)e.count, (unsigned long long)e.redOpArg,
+                        (unsigned long long)(uintptr_t)e.sendbuff, (unsigned long long)(uintptr_t)e.recvbuff);
+          out += (first ? "" : ",") + std::string(buf);
+          first = false;
+          return;
+        }
         out += (first ? "" : ",") + std::to_string(MCCS_A2A_HOPS(e.root)) + ":" + std::to_string(e.bid) + ":" +
                std::to_string(MCCS_A2A_RECV_BID(e.root)) + ":" + std::to_string(e.nChannels);
         first = false;

@@ -105,6 +105,18 @@ struct mccsLaunchGuard {
 #define MCCS_A2A_PART(route) ((int)((route) >> 16 & 0xffu))
 #define MCCS_A2A_PARTS(route) ((int)((route) >> 24 & 0xffu))
 
+// ---- AllToAllv (ring_a2av.hip, ring_walk.h a2av_next, host/plan.cpp) -------
+// Per-peer byte counts on the one-hop route only.  Library-internal like 8.
+#define MCCS_FUNC_ALLTOALLV 9
+// An AllToAllv work element of channel c (successor t, predecessor p) holds two
+// walks over the pair's m channels: sendbuff = send + sdispls[t] and count =
+// sendcounts[t] (part bid), recvbuff = recv + rdispls[p] and redOpArg =
+// recvcounts[p] (part recv_bid of the route word, hops = 1).  The rank's own
+// block is a second element: hops = 0, both buffers offset to the self
+// segments, count its bytes, part / parts over the comm's channels; it makes no
+// FIFO call.  nWarps is the same in every element of every rank: the granule
+// it sets cuts the pair's block on both ends of a connection.
+
 // Per-device ring profile counters (s_memrealtime ticks, 100 MHz), summed
 // over every slice of every workgroup while mccsRingKernelCfg.profile is set.
 #define MCCS_PROF_SLICES 0  // slices executed

@@ -152,6 +152,44 @@ __host__ __device__ __forceinline__ int a2a_call(int j, int* d_out) {
 __host__ __device__ __forceinline__ int a2a_send_block(int d) { return d; }
 __host__ __device__ __forceinline__ int a2a_recv_block(int n, int d) { return n - d; }
 
+// AllToAllv: per-peer byte counts on the one-hop route (ring_cfg.h
+// MCCS_FUNC_ALLTOALLV).  Channel c of rank r, with successor t
+// and predecessor p, walks two blocks cut over the pair's m channels as
+// AllToAll cuts one (esize 1, nChannels = m): the send walk over S =
+// sendcounts[t] with part send_bid, the receive walk over R = recvcounts[p]
+// with part recv_bid.  stepSize, chunkSize, loopSize and the granule are
+// common (one thread count, one buffer size); only `size` differs.  With Ls =
+// a2av_loops(S) and Lr = a2av_loops(R), the element's calls are, for loop
+// i = 0 .. max(Ls, Lr) - 1:  send(i) if i < Ls,  recv(i) if i < Lr.
+// An exhausted side makes no call and takes no step, so a connection advances
+// by its own pair's count alone, on both of its ends.  Inside a live side a
+// channel past the end of a short block still makes its empty, stepping call.
+// The list has Ls + Lr calls; a2av_first / a2av_next step through it (the
+// caller counts the calls: a2av_next after the last one is meaningless).
+enum : int { kA2AvSend = 0, kA2AvRecv = 1 };
+template <typename I>
+__host__ __device__ __forceinline__ I a2av_loops(I size, I loopSize) {
+  return size > 0 ? div_up(size, loopSize) : 0;
+}
+template <typename I>
+__host__ __device__ __forceinline__ int a2av_first(I S) {
+  return S > 0 ? kA2AvSend : kA2AvRecv;
+}
+// The call after `side` of the loop at *g: its side; *g moves to its loop.
+template <typename I>
+__host__ __device__ __forceinline__ int a2av_next(I S, I R, I loopSize, I* g, int side) {
+  if (side == kA2AvSend && *g < R) return kA2AvRecv;
+  *g += loopSize;
+  return *g < S ? kA2AvSend : kA2AvRecv;
+}
+// realChunkSize of one side's loop: real_chunk_size with that side's size.
+template <typename I>
+__host__ __device__ __forceinline__ I a2av_chunk_size(const RingWalk<I>& w, I size, I gridOffset, I parts) {
+  I rcs = div_up(size - gridOffset, parts);
+  rcs = w.chunkSize < rcs ? w.chunkSize : rcs;
+  return (I)(int)round_up(rcs, w.gran);
+}
+
 // Slice size of a primitive call of nelem elements (prims_simple.h:156-157):
 // sps steps per slice, spc slices per call.
 template <typename I>

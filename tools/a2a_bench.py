@@ -9,11 +9,21 @@ one GPU's HBM (tools/vnode_bench.py), so the relay's extra link traffic costs
 here only its extra FIFO copies.
 
   python tools/a2a_bench.py [--n 8] [--sizes-kib 64 1024] [--out FILE.jsonl]
+  python tools/a2a_bench.py --v [--out FILE.jsonl]
+
+--v: AllToAllv beside AllToAll.  Per size one process alternates a
+uniform-count AllToAllv with an AllToAll of the same bytes, five repeats of
+each, and reports both ranges, the ratio of the medians and AllToAll's own
+spread (max / min: the margin the ratio is read against); then a skewed matrix
+of the same total bytes per rank (a circulant of weights 1 3 0 1 0 2 0 1 ...
+times the size, zeros included), and the uniform matrix without the self
+block, whose works have one element and ride in the launch arguments.
 
 Every (n, size, mode) step runs in a fresh child process under its own time
 limit; the first step that fails or runs out of time ends the run.
 """
 import argparse
+import ctypes
 import json
 import os
 import subprocess
@@ -62,6 +72,69 @@ def step(n, kib, iters):
     print(json.dumps(out), flush=True)
 
 
+def step_v(n, kib, iters, repeats=5):
+    """One --v step: uniform AllToAllv and AllToAll alternating, then the skewed matrix."""
+    import statistics
+
+    import torch
+
+    from mccs_amd import comm as C
+
+    comms = C.init_all([0] * n, C.CommConfig(direct_bytes=-1, oneshot_bytes=-1, ll_bytes=-1))
+    B = kib << 10
+    xs = [torch.randint(0, 255, (n * B,), dtype=torch.uint8, device="cuda") for _ in range(n)]
+    ys = [torch.empty(n * B, dtype=torch.uint8, device="cuda") for _ in range(n)]
+    weights = ([1, 3, 0, 1, 0, 2, 0, 1] * n)[:n]
+    weights[0] += n - sum(weights)  # every row and column still sums to n * B
+    skew = [[B * weights[(t - s) % n] for t in range(n)] for s in range(n)]
+    packed = lambda c: [sum(c[:i]) for i in range(n)]
+    uni = [B] * n
+
+    sz = lambda v: (ctypes.c_size_t * n)(*v)  # marshalled once: the loop times the library, not the wrapper
+
+    def v_call(cnt):
+        cols = [[cnt[s][r] for s in range(n)] for r in range(n)]
+        a = [(sz(cnt[r]), sz(packed(cnt[r])), sz(cols[r]), sz(packed(cols[r]))) for r in range(n)]
+        return lambda r: C.all_to_all_v(comms[r], xs[r], a[r][0], a[r][1], ys[r], a[r][2], a[r][3])
+
+    # no self block: one element per work, which rides in the launch arguments like the uniform call's
+    noself = [[0 if s == t else B for t in range(n)] for s in range(n)]
+    calls = {"alltoall": lambda r: C.all_to_all(comms[r], xs[r], ys[r], B),
+             "alltoallv_uniform": v_call([uni] * n), "alltoallv_skewed": v_call(skew),
+             "alltoallv_noself": v_call(noself)}
+
+    def run(call, k):
+        for _ in range(k):
+            with C.group():
+                for r in range(n):
+                    call(r)
+        for c in comms:
+            c.sync()
+        torch.cuda.synchronize()
+
+    times = {k: [] for k in calls}
+    for call in calls.values():
+        run(call, 2)
+    for _ in range(repeats):
+        for name, call in calls.items():  # alternating, in one process
+            t0 = time.perf_counter()
+            run(call, iters)
+            times[name].append(round((time.perf_counter() - t0) / iters * 1e6, 1))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    out = {"bench": "a2av", "n": n, "KiB_per_peer": kib, "lanes": comms[0].lanes, "channels": comms[0].nchannels,
+           "iters": iters, "repeats": repeats, **comms[0].all_to_all_route()}
+    for k, v in times.items():
+        out[k + "_us"] = [min(v), med[k], max(v)]  # min, median, max of the repeats
+    out["v_uniform_over_alltoall"] = round(med["alltoallv_uniform"] / med["alltoall"], 3)
+    out["v_skewed_over_alltoall"] = round(med["alltoallv_skewed"] / med["alltoall"], 3)
+    out["v_noself_over_alltoall"] = round(med["alltoallv_noself"] / med["alltoall"], 3)
+    out["alltoall_spread"] = round(max(times["alltoall"]) / min(times["alltoall"]), 3)
+    torch.cuda.synchronize()
+    for c in comms:
+        c.destroy()
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[8])
@@ -69,20 +142,21 @@ def main():
     ap.add_argument("--iters", type=int, default=200, help="timed calls per collective")
     ap.add_argument("--step-timeout", type=int, default=120, help="seconds per step")
     ap.add_argument("--out", default=None, help="also append the result lines to this file")
+    ap.add_argument("--v", action="store_true", help="AllToAllv beside AllToAll (one hop only)")
     ap.add_argument("--step", type=int, nargs=2, default=None, help=argparse.SUPPRESS)  # child: n KiB
     args = ap.parse_args()
     if args.step:
-        step(args.step[0], args.step[1], args.iters)
+        (step_v if args.v else step)(args.step[0], args.step[1], args.iters)
         return 0
     for n in args.n:
         for kib in args.sizes_kib:
-            for relay in (False, True):
+            for relay in ((False,) if args.v else (False, True)):
                 env = dict(os.environ)
                 env.pop("MCCS_ALLTOALL_HOPS", None)
                 if relay:
                     env["MCCS_ALLTOALL_HOPS"] = "relay"
                 cmd = ["timeout", "-k", "10", str(args.step_timeout), sys.executable, os.path.abspath(__file__),
-                       "--step", str(n), str(kib), "--iters", str(args.iters)]
+                       "--step", str(n), str(kib), "--iters", str(args.iters)] + (["--v"] if args.v else [])
                 r = subprocess.run(cmd, capture_output=True, text=True, env=env)
                 lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
                 if r.returncode != 0 or not lines:
