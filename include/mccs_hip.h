@@ -365,11 +365,49 @@ mccsResult_t mccsCommAllToAllRoute(mccsComm_t comm, int *info2);
  * with the schema's largest thread count (a pair's two ends know no common
  * byte total to derive a smaller one from).  Graph capture: counts and
  * displacements are baked into the captured work elements, and a replay
- * repeats them.  Several calls of one comm in one group are batched into one
+ * repeats them; mccsAllToAllvDev (below) reads them on the device at every
+ * replay.  Several calls of one comm in one group are batched into one
  * launch; mixing with another function is refused as for mccsAllToAll.
  * Otherwise as mccsAllToAll. */
 mccsResult_t mccsAllToAllv(const void *sendbuff, const size_t *sendcounts, const size_t *sdispls, void *recvbuff,
                            const size_t *recvcounts, const size_t *rdispls, mccsComm_t comm, hipStream_t stream);
+/* AllToAllvDev: mccsAllToAllv with the sizes in device memory, read by the
+ * kernel when it runs.  `table` is 8-byte aligned memory the rank's GPU can
+ * read, 4 * nranks unsigned 64-bit words, all in bytes, row * nranks + peer:
+ *   row 0  sendcounts[t]     row 2  recvcounts[s]
+ *   row 1  sdispls[t]        row 3  rdispls[s]
+ * with mccsAllToAllv's meaning: rank r sends sendcounts[t] bytes from sendbuff +
+ * sdispls[t] to rank t and receives recvcounts[s] bytes from rank s at recvbuff
+ * + rdispls[s]; the self block moves sendcounts[r] bytes without a FIFO step.
+ * The host never reads the table.  The caller's contract:
+ *   - the table is complete before the call's position in stream order and is
+ *     not modified until the call has completed on the stream;
+ *   - rank s's sendcounts[t] equals rank t's recvcounts[s], and sendcounts[r]
+ *     == recvcounts[r];
+ *   - receive segments overlap neither each other nor a send segment;
+ *   - every segment lies inside its buffer.
+ * None of this can be checked by the host and none is checked on the device:
+ * the count and displacement checks mccsAllToAllv makes are the caller's here.
+ * Ranks that disagree stall until the watchdog or receive wrong bytes, as for
+ * disagreeing roots; a displacement outside a buffer is an out-of-bounds
+ * access.
+ * One hop only: a relay route is refused with mccsInvalidUsage exactly as for
+ * mccsAllToAllv.  Refused with mccsInvalidArgument: a NULL table, a table that
+ * is not 8-byte aligned, a NULL buffer (the host knows no count that would
+ * excuse one).
+ * The call always launches, on every channel of the comm, also when every count
+ * turns out to be zero (a zero count makes no FIFO call and takes no step on
+ * that side).  Its works always go through the work FIFO or, in a capture, the
+ * graph work arena, never in the launch arguments.  nranks == 1: the self copy,
+ * its size and both offsets read from the table.  Always the ring.
+ * Graph capture: the captured elements hold the table's address and the two
+ * base pointers, and every replay reads the table anew, so a graph captured once
+ * moves each step's own sizes (write the table, or have a kernel write it,
+ * earlier on the stream).  Several calls of one comm in one group are batched
+ * into one launch; mixing with another function, mccsAllToAllv included, is
+ * refused as for mccsAllToAll.  Otherwise as mccsAllToAllv. */
+mccsResult_t mccsAllToAllvDev(const void *sendbuff, void *recvbuff, const uint64_t *table, mccsComm_t comm,
+                              hipStream_t stream);
 /* PreMulSum, SumPostDiv and the average: the three reducing ring collectives
  * with an op argument.  The reference declares both ops (mccsDevPreMulSum = 4,
  * mccsDevSumPostDiv = 5, collectives.h:28-32; DECL2(AllReduce, PreMulSum /
@@ -595,6 +633,17 @@ mccsResult_t mccs_host_ring_all_to_all_v(int nranks, const void *const *sendbufs
                                          const size_t *counts, const size_t *sdispls, const size_t *rdispls,
                                          int nchannels, int nthreads_ref, int buff_size, const int *rings,
                                          int force_relay);
+/* The AllToAllvDev schedule on host threads: tables[r] is rank r's size table
+ * (mccsAllToAllvDev's layout) in host memory.  Each channel's element is
+ * resolved from the table by the arithmetic the kernel uses, then walked as
+ * mccs_host_ring_all_to_all_v walks it. */
+mccsResult_t mccs_host_ring_all_to_all_v_tables(int nranks, const void *const *sendbufs, void *const *recvbufs,
+                                                const uint64_t *const *tables, int nchannels, int nthreads_ref,
+                                                int buff_size, const int *rings, int force_relay);
+/* Index of the word of `row` (0 sendcounts, 1 sdispls, 2 recvcounts, 3
+ * rdispls) for `peer` in a size table of nranks ranks, as the kernel and the
+ * host-thread ring compute it; -1 for an argument out of range. */
+long long mccs_a2avd_index(int row, int nranks, int peer);
 /* The three reducing schedules with an op argument (mccsAllReduceOpArg,
  * mccsReduceScatterOpArg, mccsReduceOpArg): all six ops, the same argument
  * rules, pre and post applied where the kernels apply them and rounded as they

@@ -119,6 +119,10 @@ SIGNATURES: dict[str, tuple] = {
     "mccs_host_ring_all_to_all_v": (
         _c_int, [_c_int, _P(_c_void_p), _P(_c_void_p), _P(_c_size_t), _P(_c_size_t), _P(_c_size_t), _c_int, _c_int,
                  _c_int, _P(_c_int), _c_int]),
+    "mccsAllToAllvDev": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "mccs_a2avd_index": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
+    "mccs_host_ring_all_to_all_v_tables": (
+        _c_int, [_c_int, _P(_c_void_p), _P(_c_void_p), _P(_c_void_p), _c_int, _c_int, _c_int, _P(_c_int), _c_int]),
     "mccsAllReduceOpArg": (
         _c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_int, ctypes.c_uint64, _c_void_p, _c_void_p]),
     "mccsReduceScatterOpArg": (

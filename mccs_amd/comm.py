@@ -12,6 +12,7 @@ Mirrors the reference application API (src/libmccs/src/lib.rs:19-27):
    unimplemented, task.rs:95-102)                              op, stream)
   (none: no all-to-all)                         all_to_all(comm, send, recv, nbytes, stream)
   (none)                                        all_to_all_v(comm, send, scounts, sdispls, recv, rcounts, rdispls, stream)
+  (none)                                        all_to_all_v_dev(comm, send, recv, table, stream): sizes on the device
   (none: Broadcast and Reduce are declared,     broadcast(comm, send, recv, nbytes, root, stream)
    devcomm.h:11-12, and have no kernel)         reduce(comm, send, recv, count, dtype, op, root, stream)
   AllReduceDataType {Float16, Int32}            AllReduceDataType (+ Float32: the one API delta,
@@ -224,6 +225,12 @@ class Communicator:
                      stream=None) -> None:
         all_to_all_v(self, send_buf, send_counts, send_displs, recv_buf, recv_counts, recv_displs, stream)
 
+    def all_to_all_v_dev(self, send_buf, recv_buf, table, stream=None) -> None:
+        all_to_all_v_dev(self, send_buf, recv_buf, table, stream)
+
+    def exchange_counts(self, table, stream=None) -> None:
+        exchange_counts(self, table, stream)
+
     def all_to_all_route(self) -> dict:
         """The comm's AllToAll route (mccsCommAllToAllRoute): hops (1: every
         block goes straight to its ring successor; nranks - 1: relayed along the
@@ -411,6 +418,44 @@ def all_to_all_v(comm: Communicator, send_buf, send_counts, send_displs, recv_bu
     rc = _sig().mccsAllToAllv(_ptr(send_buf), arr(send_counts), arr(send_displs), _ptr(recv_buf), arr(recv_counts),
                               arr(recv_displs), comm._h, _stream(stream))
     _lib.check(rc, "mccsAllToAllv")
+
+
+def _table_ptr(comm: Communicator, table) -> int:
+    """A size table's address: a contiguous CUDA int64 / uint64 tensor of 4 * nranks elements, or a raw pointer."""
+    if not hasattr(table, "data_ptr"):
+        return 0 if table is None else int(table)
+    import torch
+
+    if table.dtype not in (torch.int64, torch.uint64):
+        raise ValueError(f"the size table holds 64-bit integers, not {table.dtype}")
+    if table.numel() != 4 * comm.nranks:
+        raise ValueError(f"the size table has {table.numel()} elements, not 4 * {comm.nranks}")
+    if not table.is_cuda or not table.is_contiguous():
+        raise ValueError("the size table is a contiguous CUDA tensor")
+    return table.data_ptr()
+
+
+def all_to_all_v_dev(comm: Communicator, send_buf, recv_buf, table, stream=None) -> None:
+    """mccsAllToAllvDev: all_to_all_v with the sizes in device memory.  table
+    holds 4 * nranks 64-bit words in bytes: send counts, send displacements,
+    receive counts, receive displacements (nranks each).  The kernel reads it
+    when it runs, so a replayed graph moves what the table holds at that
+    replay.  The host checks none of the sizes: the table must be complete
+    earlier on the stream, stay unmodified until the call completes, agree
+    with the peers' tables, and keep every segment inside its buffer.  Always
+    launches; one-hop routes only."""
+    rc = _sig().mccsAllToAllvDev(_ptr(send_buf), _ptr(recv_buf), _table_ptr(comm, table), comm._h, _stream(stream))
+    _lib.check(rc, "mccsAllToAllvDev")
+
+
+def exchange_counts(comm: Communicator, table, stream=None) -> None:
+    """Fills row 2 of a size table (receive counts) from the peers' row 0
+    (send counts) on the device: the uniform all_to_all of 8 bytes per peer.
+    Issue it on every rank, before all_to_all_v_dev on the same stream."""
+    p = _table_ptr(comm, table)
+    if not p:
+        raise ValueError("exchange_counts needs a size table")
+    all_to_all(comm, p, p + 2 * comm.nranks * 8, 8, stream)
 
 
 def all_to_all_single(comm: Communicator, output, input, output_split_sizes=None, input_split_sizes=None,
@@ -627,6 +672,26 @@ def host_ring_all_to_all_v(sendbufs, recvbufs, counts, send_displs, recv_displs,
     _lib.check(rc, "mccs_host_ring_all_to_all_v")
 
 
+def host_ring_all_to_all_v_tables(sendbufs, recvbufs, tables, channels: int = 1, nthreads: int = 544,
+                                  buffer_size: int = 1 << 22, rings=None, force_relay: bool = False) -> None:
+    """The AllToAllvDev schedule on host threads over host memory (no GPU).
+    tables[r] is rank r's size table: a contiguous numpy uint64 / int64 array of
+    4 * nranks words (or a raw host pointer), resolved by the kernel's own
+    arithmetic.  A ring set whose route is not one hop is refused."""
+    n = len(sendbufs)
+    for t in tables:
+        if hasattr(t, "ctypes") and (t.dtype.itemsize != 8 or t.dtype.kind not in "iu" or t.size != 4 * n or
+                                     not t.flags["C_CONTIGUOUS"]):
+            raise ValueError(f"a size table is a contiguous array of 4 * {n} 64-bit integers")
+    ro = None
+    if rings is not None:
+        flat = [int(v) for r in rings for v in r]
+        ro = (_ci * len(flat))(*flat)
+    rc = _sig().mccs_host_ring_all_to_all_v_tables(n, _host_ptrs(sendbufs), _host_ptrs(recvbufs), _host_ptrs(tables),
+                                                   channels, nthreads, buffer_size, ro, 1 if force_relay else 0)
+    _lib.check(rc, "mccs_host_ring_all_to_all_v_tables")
+
+
 def ring_profile(device: int = 0, reset: bool = True) -> dict:
     """Per-slice timing of the ring kernels on `device` (MCCS_RING_PROFILE=1
     set before communicator init): slices, mean µs waiting for peer flags,
@@ -682,6 +747,7 @@ __all__ = ["AllReduceDataType", "AllReduceOpType", "CommConfig", "Communicator",
            "init_communicator_rank", "all_reduce", "all_gather", "reduce_scatter", "broadcast", "reduce", "all_to_all",
            "alltoall_route", "host_ring_all_to_all",
            "all_to_all_v", "all_to_all_single", "host_ring_all_to_all_v",
+           "all_to_all_v_dev", "exchange_counts", "host_ring_all_to_all_v_tables",
            "avg_op", "red_op_arg", "all_reduce_avg", "reduce_scatter_avg", "reduce_avg",
            "group", "default_rings", "task_schema",
            "direct_defaults", "ll_default", "ring_walk",

@@ -284,6 +284,17 @@ static mccsResult_t reject_call(mccsResult_t e, const char* why) {
   return e;
 }
 
+// The v calls run on the one-hop AllToAll route only.
+static bool a2av_needs_relay(const Comm* c) { return c->nranks > 1 && (c->a2a_hops != 1 || c->a2a_m < 1); }
+static mccsResult_t reject_relay(const Comm* c) {
+  char why[256];
+  std::snprintf(why, sizeof(why),
+                "the AllToAll route is not one hop (%s: hops = %d over %d channels of %d ranks); a relaying rank "
+                "would need the sizes of blocks that are neither its row nor its column",
+                c->a2a_force_relay ? "MCCS_ALLTOALL_HOPS=relay" : "relay", c->a2a_hops, c->nch, c->nranks);
+  return reject_call(mccsInvalidUsage, why);
+}
+
 // mccsAllToAllv: the argument rules of mccs_hip.h, then the plan.  *planned: something to launch.
 static mccsResult_t a2av_check_and_plan(Comm* c, const void* send, const size_t* sendcounts, const size_t* sdispls,
                                         void* recv, const size_t* recvcounts, const size_t* rdispls,
@@ -291,14 +302,7 @@ static mccsResult_t a2av_check_and_plan(Comm* c, const void* send, const size_t*
   if (!sendcounts || !sdispls || !recvcounts || !rdispls)
     return reject_call(mccsInvalidArgument, "null count or displacement array");
   const int n = c->nranks, r = c->rank;
-  if (n > 1 && (c->a2a_hops != 1 || c->a2a_m < 1)) {
-    char why[256];
-    std::snprintf(why, sizeof(why),
-                  "the AllToAll route is not one hop (%s: hops = %d over %d channels of %d ranks); a relaying rank "
-                  "would need the sizes of blocks that are neither its row nor its column",
-                  c->a2a_force_relay ? "MCCS_ALLTOALL_HOPS=relay" : "relay", c->a2a_hops, c->nch, n);
-    return reject_call(mccsInvalidUsage, why);
-  }
+  if (a2av_needs_relay(c)) return reject_relay(c);
   size_t any_send = 0, any_recv = 0;
   for (int i = 0; i < n; ++i) {
     any_send |= sendcounts[i];
@@ -348,6 +352,38 @@ static mccsResult_t launch_a2av(Comm* c, const void* send, const size_t* sendcou
   }
   if (g_group.depth == 0) {
     StepScope st("mccsAllToAllv launch");
+    const mccsResult_t r = plan_launch_group(g_group.comms, g_group.streams);
+    group_discard();
+    return r;
+  }
+  return mccsSuccess;
+}
+
+// mccsAllToAllvDev: the sizes are on the device, so the host checks the three
+// pointers and the route and nothing else; the call always plans and launches.
+static mccsResult_t launch_a2av_dev(Comm* c, const void* send, void* recv, const uint64_t* table, hipStream_t stream) {
+  if (g_group.depth == 0) err_clear();
+  if (!c || !c->connected) return reject_call(mccsInvalidUsage, "the communicator is not connected");
+  if (c->failed) return reject_call(mccsRemoteError, "the communicator failed earlier (watchdog or abort): destroy it");
+  {
+    StepScope st("mccsAllToAllvDev");  // names the call in every diagnosis
+    if (!table) return reject_call(mccsInvalidArgument, "null size table");
+    if ((uintptr_t)table % 8) return reject_call(mccsInvalidArgument, "the size table is not 8-byte aligned");
+    if (!send || !recv) return reject_call(mccsInvalidArgument, "null buffer (the host knows no count to excuse it)");
+    if (a2av_needs_relay(c)) return reject_relay(c);
+    if (std::find(g_group.comms.begin(), g_group.comms.end(), c) == g_group.comms.end()) {
+      g_group.comms.push_back(c);
+      g_group.streams.push_back(stream);
+    }
+    const mccsResult_t er = plan_enqueue_a2av_dev(c, send, recv, table);
+    if (er != mccsSuccess) {
+      if (g_group.depth == 0) group_discard();
+      else if (g_group.error == mccsSuccess) g_group.error = er;
+      return er;
+    }
+  }
+  if (g_group.depth == 0) {
+    StepScope st("mccsAllToAllvDev launch");
     const mccsResult_t r = plan_launch_group(g_group.comms, g_group.streams);
     group_discard();
     return r;
@@ -748,6 +784,17 @@ extern "C" mccsResult_t mccsAllToAllv(const void* sendbuff, const size_t* sendco
                                       void* recvbuff, const size_t* recvcounts, const size_t* rdispls, mccsComm_t comm,
                                       hipStream_t stream) {
   return launch_a2av((Comm*)comm, sendbuff, sendcounts, sdispls, recvbuff, recvcounts, rdispls, stream);
+}
+
+extern "C" mccsResult_t mccsAllToAllvDev(const void* sendbuff, void* recvbuff, const uint64_t* table, mccsComm_t comm,
+                                         hipStream_t stream) {
+  return launch_a2av_dev((Comm*)comm, sendbuff, recvbuff, table, stream);
+}
+
+// The word of a size table (ring_walk.h a2avd_index), for the tests' own table builder.
+extern "C" long long mccs_a2avd_index(int row, int nranks, int peer) {
+  if (row < 0 || row >= kA2AvdRows || nranks < 1 || peer < 0 || peer >= nranks) return -1;
+  return (long long)a2avd_index(row, nranks, peer);
 }
 
 extern "C" mccsResult_t mccsCommAllToAllRoute(mccsComm_t comm, int* info2) {

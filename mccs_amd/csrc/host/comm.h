@@ -371,6 +371,8 @@ void alltoall_route(int nranks, int nch, const int* rings, bool force_relay, int
 // per channel one element with both walks, plus the self block's element.
 mccsResult_t plan_enqueue_a2av(Comm* c, const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
                                const size_t* recvcounts, const size_t* rdispls);
+// AllToAllvDev: per channel the FIFO element and the self element, both naming the size table.
+mccsResult_t plan_enqueue_a2av_dev(Comm* c, const void* send, void* recv, const uint64_t* table);
 mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_t>& user_streams);
 // ring.hip
 const void* ring_kernel_ptr(int func, int dtype, int op);

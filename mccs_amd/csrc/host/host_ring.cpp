@@ -204,6 +204,7 @@ struct Ctx {
   const size_t* v_counts = nullptr;
   const size_t* v_sdispls = nullptr;  // [r * n + t]
   const size_t* v_rdispls = nullptr;  // [r * n + s]
+  const uint64_t* const* v_tables = nullptr;  // or: each rank's size table (ring_cfg.h MCCS_FUNC_ALLTOALLV_DEV)
   size_t es, count;
   const void* const* send;
   void* const* recv;
@@ -411,19 +412,31 @@ void walk_alltoall(RankChannel& k) {
 // AllToAllv (ring_walk.h a2av_next): the channel's send walk
 // over the bytes for its successor and its receive walk over the bytes of its
 // predecessor, each of its own length; the self block is a local copy
-// (channel 0 makes it).
+// (channel 0 makes it).  With size tables (mccs_host_ring_all_to_all_v_tables)
+// the channel's element and the self element are resolved from the rank's table
+// as the AllToAllvDev kernel resolves them (ring_walk.h a2avd_resolve), from the
+// route words the planner gives them; the walk is the same.
 void walk_alltoallv(RankChannel& k) {
   const RingWalk<int64_t>& w = k.w;
   const int n = k.n, r = k.rank;
   const int t = k.user_rank(1), p = k.user_rank(n - 1);
-  const size_t* cnt = k.c->v_counts;
-  const size_t* sd = k.c->v_sdispls + (size_t)r * n;
-  const size_t* rd = k.c->v_rdispls + (size_t)r * n;
-  if (k.ch == 0 && cnt[(size_t)r * n + r]) std::memcpy(k.output + rd[r], k.input + sd[r], cnt[(size_t)r * n + r]);
-  const int64_t S = (int64_t)cnt[(size_t)r * n + t], R = (int64_t)cnt[(size_t)p * n + r];
   const int64_t sbid = k.c->a2a_send_bid[r * k.c->nch + k.ch], rbid = k.c->a2a_recv_bid[r * k.c->nch + k.ch];
-  k.input += sd[t];
-  k.output += rd[p];
+  mccs::A2AvdElem e, self;
+  if (k.c->v_tables) {
+    auto ld = [](const uint64_t* q) { return *q; };
+    e = mccs::a2avd_resolve(k.c->v_tables[r], n, r, MCCS_A2AVD_ROUTE(rbid, t, p), ld);
+    self = mccs::a2avd_resolve(k.c->v_tables[r], n, r, MCCS_A2A_ROUTE(0, 0, k.ch, k.c->nch), ld);
+  } else {
+    const size_t* cnt = k.c->v_counts;
+    const size_t* sd = k.c->v_sdispls + (size_t)r * n;
+    const size_t* rd = k.c->v_rdispls + (size_t)r * n;
+    e = {cnt[(size_t)r * n + t], sd[t], cnt[(size_t)p * n + r], rd[p]};
+    self = {cnt[(size_t)r * n + r], sd[r], 0, rd[r]};
+  }
+  if (k.ch == 0 && self.S) std::memcpy(k.output + self.recvOff, k.input + self.sendOff, self.S);
+  const int64_t S = (int64_t)e.S, R = (int64_t)e.R;
+  k.input += e.sendOff;
+  k.output += e.recvOff;
   const int64_t ncalls = mccs::a2av_loops(S, w.loopSize) + mccs::a2av_loops(R, w.loopSize);
   int64_t g = 0;
   int side = mccs::a2av_first(S);
@@ -651,12 +664,14 @@ extern "C" mccsResult_t mccs_host_ring_all_to_all(int nranks, const void* const*
 // AllToAllv on host threads: counts is the n x n byte matrix (counts[s * n + t]:
 // what s sends to t), sdispls / rdispls hold each rank's displacement row
 // (sdispls[r * n + t], rdispls[r * n + s]).  One hop only, as mccsAllToAllv.
-extern "C" mccsResult_t mccs_host_ring_all_to_all_v(int nranks, const void* const* sendbufs, void* const* recvbufs,
-                                                    const size_t* counts, const size_t* sdispls,
-                                                    const size_t* rdispls, int nchannels, int nthreads_ref,
-                                                    int buff_size, const int* rings, int force_relay) {
-  if (nranks < 1 || nranks > 64 || !sendbufs || !recvbufs || !counts || !sdispls || !rdispls || nchannels < 1 ||
-      nchannels > MCCS_MAX_NCHANNELS || nthreads_ref <= WARP_SIZE || buff_size < 8192 || buff_size % 8192)
+// With `tables` (each rank's size table, mccs_host_ring_all_to_all_v_tables) the
+// three arrays are unused and every size is read from the tables.
+static mccsResult_t host_ring_a2av(int nranks, const void* const* sendbufs, void* const* recvbufs,
+                                   const size_t* counts, const size_t* sdispls, const size_t* rdispls,
+                                   const uint64_t* const* tables, int nchannels, int nthreads_ref, int buff_size,
+                                   const int* rings, int force_relay) {
+  if (nranks < 1 || nranks > 64 || !sendbufs || !recvbufs || (!tables && (!counts || !sdispls || !rdispls)) ||
+      nchannels < 1 || nchannels > MCCS_MAX_NCHANNELS || nthreads_ref <= WARP_SIZE || buff_size < 8192 || buff_size % 8192)
     return mccsInvalidArgument;
   if (rings)
     for (int ch = 0; ch < nchannels; ++ch) {
@@ -665,8 +680,14 @@ extern "C" mccsResult_t mccs_host_ring_all_to_all_v(int nranks, const void* cons
         if (rings[ch * nranks + i] >= 0 && rings[ch * nranks + i] < nranks) seen |= 1ull << rings[ch * nranks + i];
       if (seen != (nranks == 64 ? ~0ull : (1ull << nranks) - 1)) return mccsInvalidArgument;  // not a permutation
     }
+  if (tables)
+    for (int r = 0; r < nranks; ++r)
+      if (!tables[r]) return mccsInvalidArgument;
   if (nranks == 1) {
-    if (counts[0]) std::memmove((char*)recvbufs[0] + rdispls[0], (const char*)sendbufs[0] + sdispls[0], counts[0]);
+    mccs::A2AvdElem self = {counts ? counts[0] : 0, sdispls ? sdispls[0] : 0, 0, rdispls ? rdispls[0] : 0};
+    if (tables)
+      self = mccs::a2avd_resolve(tables[0], 1, 0, MCCS_A2A_ROUTE(0, 0, 0, 1), [](const uint64_t* q) { return *q; });
+    if (self.S) std::memmove((char*)recvbufs[0] + self.recvOff, (const char*)sendbufs[0] + self.sendOff, self.S);
     return mccsSuccess;
   }
   std::vector<int> ident;
@@ -705,8 +726,30 @@ extern "C" mccsResult_t mccs_host_ring_all_to_all_v(int nranks, const void* cons
   c.v_counts = counts;
   c.v_sdispls = sdispls;
   c.v_rdispls = rdispls;
+  c.v_tables = tables;
   pool.run(&c, nranks * nchannels);
   return c.failed.load() ? mccsTimeout : mccsSuccess;
+}
+
+extern "C" mccsResult_t mccs_host_ring_all_to_all_v(int nranks, const void* const* sendbufs, void* const* recvbufs,
+                                                    const size_t* counts, const size_t* sdispls,
+                                                    const size_t* rdispls, int nchannels, int nthreads_ref,
+                                                    int buff_size, const int* rings, int force_relay) {
+  if (!counts || !sdispls || !rdispls) return mccsInvalidArgument;
+  return host_ring_a2av(nranks, sendbufs, recvbufs, counts, sdispls, rdispls, nullptr, nchannels, nthreads_ref,
+                        buff_size, rings, force_relay);
+}
+
+// The AllToAllvDev schedule on host threads: tables[r] is rank r's size table
+// in host memory (4 * nranks words, ring_walk.h a2avd_index).  Each channel's
+// element is resolved through a2avd_resolve, then walked as above.
+extern "C" mccsResult_t mccs_host_ring_all_to_all_v_tables(int nranks, const void* const* sendbufs,
+                                                           void* const* recvbufs, const uint64_t* const* tables,
+                                                           int nchannels, int nthreads_ref, int buff_size,
+                                                           const int* rings, int force_relay) {
+  if (!tables) return mccsInvalidArgument;
+  return host_ring_a2av(nranks, sendbufs, recvbufs, nullptr, nullptr, nullptr, tables, nchannels, nthreads_ref,
+                        buff_size, rings, force_relay);
 }
 
 // The three reducing collectives with an op argument: all six ops, PreMulSum's

@@ -247,6 +247,55 @@ mccsResult_t plan_enqueue_a2av(Comm* c, const void* send, const size_t* sendcoun
   return mccsSuccess;
 }
 
+// AllToAllvDev (ring_cfg.h MCCS_FUNC_ALLTOALLV_DEV): the sizes are in `table`
+// on the device, so the elements carry the call's base pointers and the
+// table's address, and the kernel resolves them when it runs.  The host knows
+// no count: every channel gets its FIFO element and its self element (two
+// elements per channel, so never an inline work), and the byte accounting of
+// enqueue_elem gets 0 (esize 0): a Dev call does not move the channels' loads.
+// One rank: the self element on every channel of the comm, cut by bid /
+// nChannels as any one-rank call.
+mccsResult_t plan_enqueue_a2av_dev(Comm* c, const void* send, void* recv, const uint64_t* table) {
+  if (c->plan_pending && c->plan_func != MCCS_FUNC_ALLTOALLV_DEV)
+    MCCS_FAIL(mccsInvalidUsage, "a group mixes collectives of different function / dtype / op on one communicator");
+  const int n = c->nranks, r = c->rank;
+  const uint8_t nwarps = (uint8_t)((kSimpleMaxThreads + WARP_SIZE) / WARP_SIZE);
+  if (n > 1 && (c->a2a_hops != 1 || c->a2a_m < 1)) return mccsInternalError;  // api.cpp refused it
+  for (int ch = 0; ch < c->nch; ++ch) {
+    WorkElemHost s{};  // the self element
+    s.nWarps = nwarps;
+    s.send = send;
+    s.recv = recv;
+    s.count = (size_t)(uintptr_t)table;
+    s.root = MCCS_A2A_ROUTE(0, 0, ch, c->nch);
+    if (n == 1) {
+      s.bid = (uint8_t)ch;
+      s.nChannels = (uint8_t)c->nch;
+      enqueue_elem(c->sched[ch], s, 0, 0);
+      continue;
+    }
+    const std::vector<int>& ring = c->rings[ch];
+    const int pos = (int)(std::find(ring.begin(), ring.end(), r) - ring.begin());
+    const int t = ring[(pos + 1) % n], p = ring[(pos + n - 1) % n];
+    WorkElemHost e{};
+    e.nWarps = nwarps;
+    e.send = send;
+    e.recv = recv;
+    e.count = (size_t)(uintptr_t)table;
+    e.bid = c->a2a_send_bid[ch];
+    e.nChannels = (uint8_t)c->a2a_m;
+    e.root = MCCS_A2AVD_ROUTE(c->a2a_recv_bid[ch], t, p);
+    enqueue_elem(c->sched[ch], e, 0, 0);
+    s.nChannels = 1;
+    enqueue_elem(c->sched[ch], s, 0, 0);
+  }
+  c->plan_pending = true;
+  c->plan_func = MCCS_FUNC_ALLTOALLV_DEV;
+  c->plan_dtype = mccsInt8;
+  c->plan_op = mccsDevSum;
+  return mccsSuccess;
+}
+
 void plan_discard(Comm* c) {
   for (auto& s : c->sched) s.reset();
   c->plan_pending = false;
@@ -464,6 +513,7 @@ static mccsResult_t upload_work_graph(Comm* c, LaunchDesc* ld, hipGraph_t graph)
 // off.
 static int inline_channels(const Comm* c) {
   if (!c->inline_works) return 0;
+  if (c->plan_func == MCCS_FUNC_ALLTOALLV_DEV) return 0;  // one rank queues one element per channel: still the FIFO
   int used = 0;
   for (int ch = 0; ch < c->nch; ++ch) {
     const auto& works = c->sched[ch].works;
@@ -584,12 +634,13 @@ int coresident_ring_blocks(int block, int device) {
   int ncu = 0;
   if (rt().CuCount(&ncu, device) != hipSuccess) return 0;
   int best = 1 << 30;
-  const void* fns[4 + 3 * mccsNumTypes * mccsNumDevRedOps];
+  const void* fns[5 + 3 * mccsNumTypes * mccsNumDevRedOps];
   int nf = 0;
   fns[nf++] = ring_multi_kernel_ptr(mccsFuncAllGather, mccsInt8, 0);
   fns[nf++] = ring_multi_kernel_ptr(mccsFuncBoadcast, mccsInt8, 0);
   fns[nf++] = ring_multi_kernel_ptr(MCCS_FUNC_ALLTOALL, mccsInt8, 0);
   fns[nf++] = ring_multi_kernel_ptr(MCCS_FUNC_ALLTOALLV, mccsInt8, 0);
+  fns[nf++] = ring_multi_kernel_ptr(MCCS_FUNC_ALLTOALLV_DEV, mccsInt8, 0);
   for (int dt = 0; dt < mccsNumTypes; ++dt)
     for (int op = 0; op < mccsNumDevRedOps; ++op) {
       if (op == mccsDevSumPostDiv && !is_integer_dtype(dt)) continue;  // no such kernel

@@ -426,6 +426,9 @@ class FakeRuntime final : public DeviceRuntime {
         if (fn == ring_multi_kernel_ptr(MCCS_FUNC_ALLTOALL, mccsInt8, mccsDevSum)) extra += " a2a=" + a2a_routes(ma, grid.y);
         if (fn == ring_multi_kernel_ptr(MCCS_FUNC_ALLTOALLV, mccsInt8, mccsDevSum))
           extra += " a2av=" + a2a_routes(ma, grid.y, true);
+        // AllToAllvDev: the same record under its own key (count is the size table's address)
+        if (fn == ring_multi_kernel_ptr(MCCS_FUNC_ALLTOALLV_DEV, mccsInt8, mccsDevSum))
+          extra += " a2avd=" + a2a_routes(ma, grid.y, true);
       }
     }
     note("launch dev=" + std::to_string(cur_) + " grid=" + std::to_string(grid.x) + "x" + std::to_string(grid.y) +

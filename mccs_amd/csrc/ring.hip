@@ -4,7 +4,8 @@
 // reduction op, compiled in parallel), the forty ReduceScatter kernels in
 // ring_rs_{sum,prod,max,min}.hip, the forty Reduce kernels in
 // ring_rd_{sum,prod,max,min}.hip, the Broadcast kernel in ring_bc.hip and the
-// AllToAll kernel in ring_a2a.hip, the AllToAllv kernel in ring_a2av.hip.
+// AllToAll kernel in ring_a2a.hip, the AllToAllv kernel in ring_a2av.hip,
+// the AllToAllvDev kernel (sizes read on the device) in ring_a2avd.hip.
 // PreMulSum (ten types) and SumPostDiv (the six integer types) add
 // ring_{ar,rs,rd}_{premulsum,sumpostdiv}.hip: 48 more kernels.
 #include "ring_kernel.h"
@@ -50,6 +51,7 @@ const void* ring_rd_kernel_SumPostDiv(int dtype);
 const void* ring_bc_kernel();
 const void* ring_a2a_kernel();
 const void* ring_a2av_kernel();
+const void* ring_a2avd_kernel();
 hipError_t ring_tu_rd_sum_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_rd_prod_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_rd_max_read_profile(unsigned long long* out, bool reset);
@@ -57,6 +59,7 @@ hipError_t ring_tu_rd_min_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_bc_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_a2a_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_a2av_read_profile(unsigned long long* out, bool reset);
+hipError_t ring_tu_a2avd_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_rs_sum_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_rs_prod_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_rs_max_read_profile(unsigned long long* out, bool reset);
@@ -133,6 +136,7 @@ const void* ring_multi_kernel_ptr(int func, int dtype, int op) {
   if (func == mccsFuncBoadcast) return ring_bc_kernel();
   if (func == MCCS_FUNC_ALLTOALL) return ring_a2a_kernel();
   if (func == MCCS_FUNC_ALLTOALLV) return ring_a2av_kernel();
+  if (func == MCCS_FUNC_ALLTOALLV_DEV) return ring_a2avd_kernel();
   if (func != mccsFuncAllReduce) return nullptr;
   return ar_kernel(dtype, op, true);
 }
@@ -168,7 +172,7 @@ hipError_t ring_read_profile(unsigned long long* out, bool reset) {
       ring_tu_rd_min_read_profile, ring_tu_bc_read_profile, ring_tu_ar_premulsum_read_profile,
       ring_tu_ar_sumpostdiv_read_profile, ring_tu_rs_premulsum_read_profile, ring_tu_rs_sumpostdiv_read_profile,
       ring_tu_rd_premulsum_read_profile, ring_tu_rd_sumpostdiv_read_profile, ring_tu_a2a_read_profile,
-      ring_tu_a2av_read_profile};
+      ring_tu_a2av_read_profile, ring_tu_a2avd_read_profile};
   for (auto rd : readers) {
     hipError_t e = rd(out, reset);
     if (e != hipSuccess) return e;

@@ -117,6 +117,25 @@ struct mccsLaunchGuard {
 // FIFO call.  nWarps is the same in every element of every rank: the granule
 // it sets cuts the pair's block on both ends of a connection.
 
+// ---- AllToAllvDev (ring_a2avd.hip, ring_walk.h a2avd_resolve, host/plan.cpp) -
+// AllToAllv whose sizes the kernel reads from device memory when it runs, so a
+// replayed graph takes the sizes of the moment.  Library-internal like 8 and 9.
+#define MCCS_FUNC_ALLTOALLV_DEV 10
+// The size table of a call: 4 * nranks 64-bit words in bytes, row * nranks +
+// peer (ring_walk.h a2avd_index): row 0 sendcounts, 1 sdispls, 2 recvcounts,
+// 3 rdispls.  An AllToAllvDev work element holds the call's BASE pointers in
+// sendbuff / recvbuff, the table's address in count, and redOpArg = 0; bid,
+// nChannels, nWarps and the route word are those of the AllToAllv element.
+// The part / parts bytes of a hops = 1 route word are unused, so there they
+// name the pair's peers: bits 16..23 the successor t, bits 24..31 the
+// predecessor p (a rank is < 64).  The self element (hops = 0) keeps part /
+// parts; the kernel takes the rank from the communicator.  The kernel rewrites
+// its LDS copy of the element into the AllToAllv form (count = S, redOpArg =
+// R, both buffers offset) before anything else reads it.
+#define MCCS_A2AVD_ROUTE(recv_bid, next, prev) MCCS_A2A_ROUTE(1, recv_bid, next, prev)
+#define MCCS_A2AVD_NEXT(route) MCCS_A2A_PART(route)
+#define MCCS_A2AVD_PREV(route) MCCS_A2A_PARTS(route)
+
 // Per-device ring profile counters (s_memrealtime ticks, 100 MHz), summed
 // over every slice of every workgroup while mccsRingKernelCfg.profile is set.
 #define MCCS_PROF_SLICES 0  // slices executed

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "mccs_devcomm.h"
+#include "ring_cfg.h"  // the AllToAll route word (a2avd_resolve)
 
 namespace mccs {
 
@@ -188,6 +189,39 @@ __host__ __device__ __forceinline__ I a2av_chunk_size(const RingWalk<I>& w, I si
   I rcs = div_up(size - gridOffset, parts);
   rcs = w.chunkSize < rcs ? w.chunkSize : rcs;
   return (I)(int)round_up(rcs, w.gran);
+}
+
+// AllToAllvDev: the size table a call's elements are resolved from (ring_cfg.h
+// MCCS_FUNC_ALLTOALLV_DEV).  4 * nranks 64-bit words in bytes; the word of
+// `row` for `peer` is at a2avd_index.  The kernel, the host-thread ring and
+// the tests' expectations index the table through this one definition.
+enum : int { kA2AvdSendCounts = 0, kA2AvdSendDispls = 1, kA2AvdRecvCounts = 2, kA2AvdRecvDispls = 3, kA2AvdRows = 4 };
+__host__ __device__ __forceinline__ int64_t a2avd_index(int row, int nranks, int peer) {
+  return (int64_t)row * nranks + peer;
+}
+// What an AllToAllv element holds, read from the table: the send walk's bytes
+// S and offset into sendbuff, the receive walk's bytes R and offset into
+// recvbuff.
+struct A2AvdElem {
+  uint64_t S, sendOff, R, recvOff;
+};
+// Element of the route word `route` on rank `rank`.  hops = 1: S and its
+// displacement are the successor's words of rows 0 and 1, R and its
+// displacement the predecessor's words of rows 2 and 3.  hops = 0 (the self
+// element, and the one element of a one-rank call): the rank's own words of
+// rows 0, 1 and 3; R = 0, as in the AllToAllv self element (the contract makes
+// recvcounts[rank] == sendcounts[rank]).  ld(p) loads the word at p.
+template <typename Load>
+__host__ __device__ __forceinline__ A2AvdElem a2avd_resolve(const uint64_t* table, int nranks, int rank,
+                                                            uint32_t route, Load ld) {
+  const bool self = MCCS_A2A_HOPS(route) == 0;
+  const int t = self ? rank : MCCS_A2AVD_NEXT(route), p = self ? rank : MCCS_A2AVD_PREV(route);
+  A2AvdElem e;
+  e.S = ld(table + a2avd_index(kA2AvdSendCounts, nranks, t));
+  e.sendOff = ld(table + a2avd_index(kA2AvdSendDispls, nranks, t));
+  e.R = self ? 0 : ld(table + a2avd_index(kA2AvdRecvCounts, nranks, p));
+  e.recvOff = ld(table + a2avd_index(kA2AvdRecvDispls, nranks, p));
+  return e;
 }
 
 // Slice size of a primitive call of nelem elements (prims_simple.h:156-157):

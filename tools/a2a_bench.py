@@ -10,6 +10,7 @@ here only its extra FIFO copies.
 
   python tools/a2a_bench.py [--n 8] [--sizes-kib 64 1024] [--out FILE.jsonl]
   python tools/a2a_bench.py --v [--out FILE.jsonl]
+  python tools/a2a_bench.py --v --dev [--out FILE.jsonl]
 
 --v: AllToAllv beside AllToAll.  Per size one process alternates a
 uniform-count AllToAllv with an AllToAll of the same bytes, five repeats of
@@ -18,6 +19,14 @@ spread (max / min: the margin the ratio is read against); then a skewed matrix
 of the same total bytes per rank (a circulant of weights 1 3 0 1 0 2 0 1 ...
 times the size, zeros included), and the uniform matrix without the self
 block, whose works have one element and ride in the launch arguments.
+
+--v --dev: AllToAllvDev (the sizes in a table on the device) beside the
+host-count AllToAllv with a self block, the yardstick: both queue two elements
+per channel and take the work FIFO, so the difference is the table reads.
+Uniform counts; per size one process alternates the yardstick, the eager Dev
+call and a replayed graph holding exchange_counts and the Dev call, five
+repeats of each, and reports the three ranges, the ratios of the medians and the
+yardstick's own spread (max / min), the margin the ratios are read against.
 
 Every (n, size, mode) step runs in a fresh child process under its own time
 limit; the first step that fails or runs out of time ends the run.
@@ -135,6 +144,75 @@ def step_v(n, kib, iters, repeats=5):
     print(json.dumps(out), flush=True)
 
 
+def step_dev(n, kib, iters, repeats=5):
+    """One --v --dev step: host-count AllToAllv (self block), AllToAllvDev eager, and
+    exchange_counts + AllToAllvDev in a replayed graph, alternating."""
+    import statistics
+
+    import torch
+
+    from mccs_amd import comm as C
+
+    comms = C.init_all([0] * n, C.CommConfig(direct_bytes=-1, oneshot_bytes=-1, ll_bytes=-1))
+    B = kib << 10
+    xs = [torch.randint(0, 255, (n * B,), dtype=torch.uint8, device="cuda") for _ in range(n)]
+    ys = [torch.empty(n * B, dtype=torch.uint8, device="cuda") for _ in range(n)]
+    disp = [t * B for t in range(n)]
+    sz = lambda v: (ctypes.c_size_t * n)(*v)  # marshalled once: the loop times the library, not the wrapper
+    a = (sz([B] * n), sz(disp))
+    tabs = [torch.tensor([B] * n + disp + [B] * n + disp, dtype=torch.int64, device="cuda") for _ in range(n)]
+    tptr = [t.data_ptr() for t in tabs]
+    torch.cuda.synchronize()
+
+    def grouped(call):
+        with C.group():
+            for r in range(n):
+                call(r)
+
+    host = lambda r: C.all_to_all_v(comms[r], xs[r], a[0], a[1], ys[r], a[0], a[1])
+    dev = lambda r: C.all_to_all_v_dev(comms[r], xs[r], ys[r], tptr[r])
+    grouped(host)
+    grouped(dev)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        grouped(lambda r: C.exchange_counts(comms[r], tptr[r]))
+        grouped(dev)
+    calls = {"alltoallv_host_self": lambda: grouped(host), "alltoallv_dev": lambda: grouped(dev),
+             "alltoallv_dev_graph_with_exchange": g.replay}
+
+    def run(call, k):
+        for _ in range(k):
+            call()
+        for c in comms:
+            c.sync()
+        torch.cuda.synchronize()
+
+    times = {k: [] for k in calls}
+    for call in calls.values():
+        run(call, 2)
+    for _ in range(repeats):
+        for name, call in calls.items():  # alternating, in one process
+            t0 = time.perf_counter()
+            run(call, iters)
+            times[name].append(round((time.perf_counter() - t0) / iters * 1e6, 1))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    out = {"bench": "a2avd", "n": n, "KiB_per_peer": kib, "lanes": comms[0].lanes, "channels": comms[0].nchannels,
+           "iters": iters, "repeats": repeats, **comms[0].all_to_all_route()}
+    for k, v in times.items():
+        out[k + "_us"] = [min(v), med[k], max(v)]  # min, median, max of the repeats
+    out["dev_over_host"] = round(med["alltoallv_dev"] / med["alltoallv_host_self"], 3)
+    out["dev_graph_over_host"] = round(med["alltoallv_dev_graph_with_exchange"] / med["alltoallv_host_self"], 3)
+    out["host_spread"] = round(max(times["alltoallv_host_self"]) / min(times["alltoallv_host_self"]), 3)
+    for r in range(n):  # the exchanged row 2 is still the uniform count
+        assert tabs[r].tolist() == [B] * n + disp + [B] * n + disp, r
+    del g
+    torch.cuda.synchronize()
+    for c in comms:
+        c.destroy()
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[8])
@@ -143,10 +221,13 @@ def main():
     ap.add_argument("--step-timeout", type=int, default=120, help="seconds per step")
     ap.add_argument("--out", default=None, help="also append the result lines to this file")
     ap.add_argument("--v", action="store_true", help="AllToAllv beside AllToAll (one hop only)")
+    ap.add_argument("--dev", action="store_true", help="with --v: AllToAllvDev beside the host-count AllToAllv")
     ap.add_argument("--step", type=int, nargs=2, default=None, help=argparse.SUPPRESS)  # child: n KiB
     args = ap.parse_args()
+    if args.dev and not args.v:
+        ap.error("--dev goes with --v")
     if args.step:
-        (step_v if args.v else step)(args.step[0], args.step[1], args.iters)
+        (step_dev if args.v and args.dev else step_v if args.v else step)(args.step[0], args.step[1], args.iters)
         return 0
     for n in args.n:
         for kib in args.sizes_kib:
@@ -156,7 +237,8 @@ def main():
                 if relay:
                     env["MCCS_ALLTOALL_HOPS"] = "relay"
                 cmd = ["timeout", "-k", "10", str(args.step_timeout), sys.executable, os.path.abspath(__file__),
-                       "--step", str(n), str(kib), "--iters", str(args.iters)] + (["--v"] if args.v else [])
+                       "--step", str(n), str(kib), "--iters", str(args.iters)] + (["--v"] if args.v else []) + \
+                      (["--dev"] if args.v and args.dev else [])
                 r = subprocess.run(cmd, capture_output=True, text=True, env=env)
                 lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
                 if r.returncode != 0 or not lines:
