@@ -7,6 +7,10 @@ call_list():  the call list of one work element, written from the issue's
               recv(i) if i < Lr, with L = ceil(count / loopSize), 0 for 0.
 elements():   per (rank, channel) the (S, R) pair a one-hop ring set gives:
               S = cnt[r][next_c(r)], R = cnt[prev_c(r)][r].
+channel_cut(), slice_cut(): how a pair's block is cut over its channels and a
+              call into slices, written from the description of the cut;
+              boundary_values() and boundary_matrices() put counts on its
+              edges, cut_situations() names what a set of counts reaches.
 The count matrices are built for buffer_size = 1 << 16: 8 KiB steps, 32 KiB
 chunks, so one loop of a pair is C = 32768 * m bytes.
 """
@@ -212,3 +216,120 @@ def wrong_candidates(sends, cnt, lay) -> dict:
 def frame(payload_len: int, lead: int = 32, tail: int = 64):
     a = np.full(lead + payload_len + tail, SENTINEL, np.uint8)
     return a, slice(lead, lead + payload_len)
+
+
+# ---- the byte cut of one pair's block, and counts on its edges ----------------
+# Written from the description of the cut, not from the library: a pair's block
+# of `count` bytes goes over the pair's m channels in loops of CHUNK * m bytes.
+GRAN = 4096  # the granule realChunkSize is rounded up to (544 threads)
+STEP = BUFF // 8  # one FIFO step
+CHUNK_STEPS = 4  # steps per chunk; one slice holds sps of them, a call spc = CHUNK_STEPS / sps slices
+SLICINGS = {"default": 1, "slice2": 2}  # name -> spc: one 4-step slice per call; MCCS_SLICE_STEPS=2: two 2-step slices
+SELF_VALUES = (0, 1, 17, 513, 4097)
+
+
+def channel_cut(count: int, m: int, gran: int = GRAN, chunk: int = CHUNK) -> list[tuple[int, int, int, int]]:
+    """(gridOffset, rcs, offset, nelem) per loop and part: in the loop at g,
+    rcs = round_up(min(chunk, ceil((count - g) / m)), gran); part p starts at
+    g + p * rcs and gets max(0, min(rcs, count - start)) bytes."""
+    rows, g = [], 0
+    while g < count:
+        rcs = min(chunk, -(-(count - g) // m))
+        rcs = -(-rcs // gran) * gran
+        for p in range(m):
+            start = g + p * rcs
+            rows.append((g, rcs, start, max(0, min(rcs, count - start))))
+        g += chunk * m
+    return rows
+
+
+def slice_size(nelem: int, spc: int) -> int:
+    """sliceSize of a call of nelem bytes cut into spc slices of sps = CHUNK_STEPS / spc steps."""
+    sps = CHUNK_STEPS // spc
+    return max(-(-nelem // (16 * spc)) * 16, STEP * sps // 32)
+
+
+def slice_cut(nelem: int, spc: int) -> list[int]:
+    """The bytes of each of a call's spc slices."""
+    size = slice_size(nelem, spc)
+    return [max(0, min(size, nelem - s * size)) for s in range(spc)]
+
+
+def boundary_values(m: int) -> list[int]:
+    """Counts on the edges of the cut: the 16-byte pack, the slice floors, the
+    granule, the channel edges inside one loop, the loop edges."""
+    G, C = GRAN, loop_bytes(m)
+    vals = [1, 16, 17, 511, 512, 513, 1024, 1025, G - 1, G, G + 1, (m - 1) * G, (m - 1) * G + 1, m * G - 1, m * G,
+            m * G + 1, C - G, C - G + 1, C - 1, C, C + 1, C + m * G, 2 * C - 1, 2 * C, 3 * C - G + 1]
+    return sorted({v for v in vals if v > 0})
+
+
+def boundary_matrices(n: int, m: int, rings) -> list[list[list[int]]]:
+    """Count matrices whose off-diagonal entries walk through 0 and
+    boundary_values(m): first in ascending order (neighbouring values meet in
+    one element: mostly equal loop counts), then with stride 11 through the
+    same list (far values meet, in both orders).  On a one-hop ring set every
+    off-diagonal entry is the S of one rank's elements and the R of another's,
+    so the first pass alone puts every value on both sides.  The diagonal
+    cycles through SELF_VALUES."""
+    vals = [0] + boundary_values(m)
+    stride = 11
+    while np.gcd(stride, len(vals)) != 1:
+        stride += 1
+    stream = vals + [vals[(3 + stride * k) % len(vals)] for k in range(len(vals))]
+    slots = n * (n - 1)
+    nmat = min(20, max(2, -(-(len(vals) + 14) // slots)))
+    out, k = [], 0
+    for i in range(nmat):
+        cnt = [[0] * n for _ in range(n)]
+        for s in range(n):
+            for t in range(n):
+                if s == t:
+                    cnt[s][t] = SELF_VALUES[(i + s) % len(SELF_VALUES)]
+                else:
+                    cnt[s][t] = stream[k % len(stream)]
+                    k += 1
+        out.append(cnt)
+    return out
+
+
+def cut_situations(cnts, m: int) -> set:
+    """What the cut of the counts `cnts` (each the S or the R of some element)
+    reaches, as a set of names.  "last": the last channel of a loop whose start
+    is not past the end of the block (it gets count - start >= 0 bytes);
+    "past": a channel whose start is past the end; "slice2 second": the second
+    slice of a call under MCCS_SLICE_STEPS=2; "default slice": the one slice
+    of a call under the default slicing."""
+    out = set()
+    for count in cnts:
+        rows = channel_cut(count, m)
+        for i in range(0, len(rows), m):
+            loop = rows[i:i + m]
+            live = [row for row in loop if row[2] <= count]
+            if len(live) < m:
+                out.add("past")
+            last = live[-1][3]
+            for name, v in (("0", 0), ("1", 1), ("G-1", GRAN - 1), ("G", GRAN), ("chunk", CHUNK)):
+                if last == v:
+                    out.add("last " + name)
+            if loop[0][0] > 0 and sum(row[3] for row in loop) == 1:
+                out.add("second loop 1")
+            for _, _, _, nelem in loop:
+                a, b = slice_cut(nelem, 2)
+                if a == slice_size(nelem, 2) and b == 0:  # the first slice exactly full
+                    out.add("slice2 second 0")
+                if b == 1:
+                    out.add("slice2 second 1")
+                if b > 0 and b == slice_size(nelem, 2):
+                    out.add("slice2 second full")
+                (a,) = slice_cut(nelem, 1)  # the default slicing has no second slice: its one slice on its floor
+                floor = STEP * CHUNK_STEPS // 32
+                for name, v in (("1", 1), ("floor", floor), ("floor + 1", floor + 1)):
+                    if a == v:
+                        out.add("default slice " + name)
+    return out
+
+
+SITUATIONS = {"last 0", "last 1", "last G-1", "last G", "last chunk", "past", "second loop 1", "slice2 second 0",
+              "slice2 second 1", "slice2 second full", "default slice 1", "default slice floor",
+              "default slice floor + 1"}
