@@ -408,6 +408,46 @@ mccsResult_t mccsAllToAllv(const void *sendbuff, const size_t *sendcounts, const
  * refused as for mccsAllToAll.  Otherwise as mccsAllToAllv. */
 mccsResult_t mccsAllToAllvDev(const void *sendbuff, void *recvbuff, const uint64_t *table, mccsComm_t comm,
                               hipStream_t stream);
+/* Send / Recv: grouped point-to-point (torch's batch_isend_irecv; the pieces of
+ * a Gather or Scatter).  mccsSend moves count * elem_bytes(dtype) bytes from
+ * sendbuff to rank `peer`, mccsRecv receives as many from rank `peer` into
+ * recvbuff; the data path is byte-typed, dtype only scales count.  A message
+ * involves its two ranks only: no other rank of the communicator enters a call.
+ * Matching is NCCL's: on each ordered pair (s, t) the k-th send of s to t over
+ * the communicator's life matches the k-th receive of t from s.  A size that
+ * differs between the two ends, or a call whose partner never comes, stalls
+ * until the watchdog; like disagreeing roots this is not detected.
+ * Groups.  The sends and receives of one communicator inside mccsGroupStart /
+ * mccsGroupEnd form one launch; outside a group each call is a launch of its
+ * own.  A zero-byte call succeeds and takes no FIFO step (inside a group it
+ * still holds its place in the order of its pair); a group whose calls are all
+ * empty launches nothing.
+ * One hop only.  A message s -> t travels on the m channels whose ring has t
+ * right after s, cut over them as mccsAllToAllv cuts a pair's block, which
+ * needs the one-hop AllToAll route (mccsCommAllToAllRoute).  On a relay route
+ * (the default rings of 6 ranks, fewer channels than the one-hop set needs, a
+ * user ring set without the equal-m property, MCCS_ALLTOALL_HOPS=relay) the
+ * call is refused with mccsInvalidUsage, in mccsAllToAllv's words;
+ * mccsGetLastErrorString names the route.
+ * Refused with mccsInvalidArgument: peer outside 0 .. nranks - 1; peer == the
+ * calling rank (a self send is out of scope: copy the buffer); an unknown
+ * dtype; a NULL buffer with a non-zero count; a communicator of one rank (it
+ * has no peer).  Mixing with another function in one group on one communicator
+ * is refused with mccsInvalidUsage, as for every function.
+ * Stricter than NCCL: group what you exchange.  One workgroup walks a
+ * channel's send and its receive in lockstep (call i of the send, then call i
+ * of the receive), and the j-th send and the j-th receive of a group that
+ * share a channel share an element.  Ranks that exchange messages with each
+ * other must therefore issue those calls in one group each, on both sides.  If
+ * rank A groups its send to B with its receive from B while B issues the same
+ * two calls ungrouped, as two launches, the pair can stall where NCCL would
+ * not.  An ungrouped send larger than the FIFO's free space (buffer_size)
+ * completes only once the peer's receive runs.
+ * Always the ring (mccsCommLastAlgo reports it); every element runs with the
+ * schema's largest thread count, as mccsAllToAllv's.  Graph capture: pointers
+ * and sizes are baked into the captured work elements. */
+mccsResult_t mccsSend(const void *sendbuff, size_t count, int dtype, int peer, mccsComm_t comm, hipStream_t stream);
+mccsResult_t mccsRecv(void *recvbuff, size_t count, int dtype, int peer, mccsComm_t comm, hipStream_t stream);
 /* PreMulSum, SumPostDiv and the average: the three reducing ring collectives
  * with an op argument.  The reference declares both ops (mccsDevPreMulSum = 4,
  * mccsDevSumPostDiv = 5, collectives.h:28-32; DECL2(AllReduce, PreMulSum /
@@ -644,6 +684,18 @@ mccsResult_t mccs_host_ring_all_to_all_v_tables(int nranks, const void *const *s
  * rdispls) for `peer` in a size table of nranks ranks, as the kernel and the
  * host-thread ring compute it; -1 for an argument out of range. */
 long long mccs_a2avd_index(int row, int nranks, int peer);
+/* The Send/Recv schedule (mccsSend / mccsRecv) on host threads over host
+ * memory.  Op i is a send (op_is_send[i] != 0) or a receive of op_bytes[i]
+ * bytes at op_buf[i], issued by rank op_rank[i] with rank op_peer[i]; each
+ * rank's ops, in list order, form one group.  The elements are built by the
+ * planner's own pairing rule and walked as mccs_host_ring_all_to_all_v walks
+ * its elements.  A relay route is refused (mccsInvalidUsage).  Seeing all
+ * ranks, it refuses with mccsInvalidArgument what the device path cannot
+ * detect: a send without its receive or of another size; and fewer than two
+ * ranks, a rank or peer out of range, peer == rank, a NULL buffer with bytes. */
+mccsResult_t mccs_host_ring_send_recv(int nranks, int nops, const int *op_rank, const int *op_is_send,
+                                      const int *op_peer, void *const *op_buf, const size_t *op_bytes, int nchannels,
+                                      int nthreads_ref, int buff_size, const int *rings);
 /* The three reducing schedules with an op argument (mccsAllReduceOpArg,
  * mccsReduceScatterOpArg, mccsReduceOpArg): all six ops, the same argument
  * rules, pre and post applied where the kernels apply them and rounded as they

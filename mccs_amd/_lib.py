@@ -123,6 +123,11 @@ SIGNATURES: dict[str, tuple] = {
     "mccs_a2avd_index": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
     "mccs_host_ring_all_to_all_v_tables": (
         _c_int, [_c_int, _P(_c_void_p), _P(_c_void_p), _P(_c_void_p), _c_int, _c_int, _c_int, _P(_c_int), _c_int]),
+    "mccsSend": (_c_int, [_c_void_p, _c_size_t, _c_int, _c_int, _c_void_p, _c_void_p]),
+    "mccsRecv": (_c_int, [_c_void_p, _c_size_t, _c_int, _c_int, _c_void_p, _c_void_p]),
+    "mccs_host_ring_send_recv": (
+        _c_int, [_c_int, _c_int, _P(_c_int), _P(_c_int), _P(_c_int), _P(_c_void_p), _P(_c_size_t), _c_int, _c_int,
+                 _c_int, _P(_c_int)]),
     "mccsAllReduceOpArg": (
         _c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_int, ctypes.c_uint64, _c_void_p, _c_void_p]),
     "mccsReduceScatterOpArg": (

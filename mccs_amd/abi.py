@@ -14,6 +14,10 @@ MCCS_MAX_NCHANNELS = 32
 MCCS_WORK_SIZE = 512
 MCCS_MAX_WORK_ELEMENTS = 10
 MCCS_BUFFER_SLOTS = 8
+# Function ids the library adds past the reference's mccsDevFunc_t (ring_cfg.h).  The reference reserves
+# SendRecv = 5, Send = 6, Recv = 7 for a P2p element on peer-indexed connectors, which this library never builds:
+# its Send/Recv runs on the ring connectors under id 11, in mccsDevWorkElem's layout.
+MCCS_FUNC_ALLTOALL, MCCS_FUNC_ALLTOALLV, MCCS_FUNC_ALLTOALLV_DEV, MCCS_FUNC_SENDRECV = 8, 9, 10, 11
 
 
 class mccsDevConnInfo(C.Structure):

@@ -13,6 +13,7 @@ Mirrors the reference application API (src/libmccs/src/lib.rs:19-27):
   (none: no all-to-all)                         all_to_all(comm, send, recv, nbytes, stream)
   (none)                                        all_to_all_v(comm, send, scounts, sdispls, recv, rcounts, rdispls, stream)
   (none)                                        all_to_all_v_dev(comm, send, recv, table, stream): sizes on the device
+  (none: SendRecv ids reserved, no kernel)      send / recv(comm, buf, count, dtype, peer, stream), batch_send_recv
   (none: Broadcast and Reduce are declared,     broadcast(comm, send, recv, nbytes, root, stream)
    devcomm.h:11-12, and have no kernel)         reduce(comm, send, recv, count, dtype, op, root, stream)
   AllReduceDataType {Float16, Int32}            AllReduceDataType (+ Float32: the one API delta,
@@ -230,6 +231,12 @@ class Communicator:
 
     def exchange_counts(self, table, stream=None) -> None:
         exchange_counts(self, table, stream)
+
+    def send(self, buf, count: int, data_type=AllReduceDataType.Uint8, peer: int = 0, stream=None) -> None:
+        send(self, buf, count, data_type, peer, stream)
+
+    def recv(self, buf, count: int, data_type=AllReduceDataType.Uint8, peer: int = 0, stream=None) -> None:
+        recv(self, buf, count, data_type, peer, stream)
 
     def all_to_all_route(self) -> dict:
         """The comm's AllToAll route (mccsCommAllToAllRoute): hops (1: every
@@ -482,6 +489,31 @@ def all_to_all_single(comm: Communicator, output, input, output_split_sizes=None
     all_to_all_v(comm, input, sc, packed(sc), output, rc, packed(rc), stream)
 
 
+def send(comm: Communicator, buf, count: int, dtype=AllReduceDataType.Uint8, peer: int = 0, stream=None) -> None:
+    """mccsSend: count elements of dtype from buf to rank peer.  One-hop
+    AllToAll routes only.  The k-th send of a pair matches its k-th recv;
+    sends and receives inside one group() form one launch, and ranks that
+    exchange with each other issue those calls in one group each."""
+    _lib.check(_sig().mccsSend(_ptr(buf), int(count), int(dtype), int(peer), comm._h, _stream(stream)), "mccsSend")
+
+
+def recv(comm: Communicator, buf, count: int, dtype=AllReduceDataType.Uint8, peer: int = 0, stream=None) -> None:
+    """mccsRecv: count elements of dtype from rank peer into buf (see send)."""
+    _lib.check(_sig().mccsRecv(_ptr(buf), int(count), int(dtype), int(peer), comm._h, _stream(stream)), "mccsRecv")
+
+
+def batch_send_recv(comm: Communicator, ops, stream=None) -> None:
+    """torch's batch_isend_irecv in one launch: ops is a list of ("send" |
+    "recv", tensor_or_ptr, nbytes_or_count, dtype, peer), issued in order
+    inside one group().  dtype None counts bytes."""
+    with group():
+        for kind, buf, count, dtype, peer in ops:
+            if kind not in ("send", "recv"):
+                raise ValueError(f"op kind {kind!r} is neither 'send' nor 'recv'")
+            (send if kind == "send" else recv)(comm, buf, count, AllReduceDataType.Uint8 if dtype is None else dtype,
+                                               peer, stream)
+
+
 def avg_op(data_type, nranks: int) -> tuple[AllReduceOpType, int]:
     """mccsAvgOp: the (op, op_arg) that averages over nranks.  Floating types:
     PreMulSum with 1/nranks in the type's bits; integer types: SumPostDiv with
@@ -692,6 +724,28 @@ def host_ring_all_to_all_v_tables(sendbufs, recvbufs, tables, channels: int = 1,
     _lib.check(rc, "mccs_host_ring_all_to_all_v_tables")
 
 
+def host_ring_send_recv(nranks: int, ops, channels: int = 1, nthreads: int = 544, buffer_size: int = 1 << 22,
+                        rings=None) -> None:
+    """The Send/Recv schedule on host threads over host memory (no GPU).  ops
+    is a list of (rank, "send" | "recv", peer, buf, nbytes): buf a numpy array,
+    a raw host pointer or None (nbytes 0).  Each rank's ops, in list order,
+    form one group.  A ring set whose route is not one hop is refused."""
+    k = len(ops)
+    ints = lambda v: (_ci * max(1, k))(*v)
+    ro = None
+    if rings is not None:
+        flat = [int(v) for r in rings for v in r]
+        ro = (_ci * len(flat))(*flat)
+    for o in ops:
+        if o[1] not in ("send", "recv"):
+            raise ValueError(f"op kind {o[1]!r} is neither 'send' nor 'recv'")
+    rc = _sig().mccs_host_ring_send_recv(nranks, k, ints([int(o[0]) for o in ops]),
+                                         ints([1 if o[1] == "send" else 0 for o in ops]),
+                                         ints([int(o[2]) for o in ops]), _host_ptrs([o[3] for o in ops]),
+                                         _sizes([o[4] for o in ops]), channels, nthreads, buffer_size, ro)
+    _lib.check(rc, "mccs_host_ring_send_recv")
+
+
 def ring_profile(device: int = 0, reset: bool = True) -> dict:
     """Per-slice timing of the ring kernels on `device` (MCCS_RING_PROFILE=1
     set before communicator init): slices, mean µs waiting for peer flags,
@@ -748,6 +802,7 @@ __all__ = ["AllReduceDataType", "AllReduceOpType", "CommConfig", "Communicator",
            "alltoall_route", "host_ring_all_to_all",
            "all_to_all_v", "all_to_all_single", "host_ring_all_to_all_v",
            "all_to_all_v_dev", "exchange_counts", "host_ring_all_to_all_v_tables",
+           "send", "recv", "batch_send_recv", "host_ring_send_recv",
            "avg_op", "red_op_arg", "all_reduce_avg", "reduce_scatter_avg", "reduce_avg",
            "group", "default_rings", "task_schema",
            "direct_defaults", "ll_default", "ring_walk",

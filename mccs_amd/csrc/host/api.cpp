@@ -391,6 +391,47 @@ static mccsResult_t launch_a2av_dev(Comm* c, const void* send, void* recv, const
   return mccsSuccess;
 }
 
+// mccsSend / mccsRecv: the argument rules of mccs_hip.h; the call then joins
+// its comm's pending group (plan.cpp pairs a group's calls into elements when
+// it launches).  Outside a group the call is a group of its own.
+static mccsResult_t launch_sendrecv(Comm* c, bool is_send, void* buf, size_t count, int dtype, int peer,
+                                    hipStream_t stream) {
+  if (g_group.depth == 0) err_clear();
+  const char* const name = is_send ? "mccsSend" : "mccsRecv";
+  if (!c || !c->connected) return reject_call(mccsInvalidUsage, "the communicator is not connected");
+  if (c->failed) return reject_call(mccsRemoteError, "the communicator failed earlier (watchdog or abort): destroy it");
+  {
+    StepScope st(name);  // names the call in every diagnosis
+    char why[128];
+    if (c->nranks == 1) return reject_call(mccsInvalidArgument, "a communicator of one rank has no peer");
+    if (peer < 0 || peer >= c->nranks) {
+      std::snprintf(why, sizeof(why), "peer %d outside 0..%d", peer, c->nranks - 1);
+      return reject_call(mccsInvalidArgument, why);
+    }
+    if (peer == c->rank) return reject_call(mccsInvalidArgument, "peer is the calling rank (a self send is out of scope)");
+    if (dtype < 0 || dtype >= mccsNumTypes) return reject_call(mccsInvalidArgument, "unknown dtype");
+    if (!buf && count) return reject_call(mccsInvalidArgument, "null buffer with a non-zero count");
+    if (a2av_needs_relay(c)) return reject_relay(c);
+    if (std::find(g_group.comms.begin(), g_group.comms.end(), c) == g_group.comms.end()) {
+      g_group.comms.push_back(c);
+      g_group.streams.push_back(stream);
+    }
+    const mccsResult_t er = plan_enqueue_sendrecv(c, is_send, buf, count * (size_t)elem_bytes(dtype), peer);
+    if (er != mccsSuccess) {
+      if (g_group.depth == 0) group_discard();
+      else if (g_group.error == mccsSuccess) g_group.error = er;
+      return er;
+    }
+  }
+  if (g_group.depth == 0) {
+    StepScope st(std::string(name) + " launch");
+    const mccsResult_t r = plan_launch_group(g_group.comms, g_group.streams);
+    group_discard();
+    return r;
+  }
+  return mccsSuccess;
+}
+
 }  // namespace mccs
 
 using namespace mccs;
@@ -789,6 +830,16 @@ extern "C" mccsResult_t mccsAllToAllv(const void* sendbuff, const size_t* sendco
 extern "C" mccsResult_t mccsAllToAllvDev(const void* sendbuff, void* recvbuff, const uint64_t* table, mccsComm_t comm,
                                          hipStream_t stream) {
   return launch_a2av_dev((Comm*)comm, sendbuff, recvbuff, table, stream);
+}
+
+extern "C" mccsResult_t mccsSend(const void* sendbuff, size_t count, int dtype, int peer, mccsComm_t comm,
+                                 hipStream_t stream) {
+  return launch_sendrecv((Comm*)comm, true, const_cast<void*>(sendbuff), count, dtype, peer, stream);
+}
+
+extern "C" mccsResult_t mccsRecv(void* recvbuff, size_t count, int dtype, int peer, mccsComm_t comm,
+                                 hipStream_t stream) {
+  return launch_sendrecv((Comm*)comm, false, recvbuff, count, dtype, peer, stream);
 }
 
 // The word of a size table (ring_walk.h a2avd_index), for the tests' own table builder.

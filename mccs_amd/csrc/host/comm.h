@@ -183,6 +183,22 @@ struct ChannelSchedule {  // plan.rs ChanWorkSchedule
   }
 };
 
+// Send/Recv (ring_cfg.h MCCS_FUNC_SENDRECV): one call of a group, in issue
+// order, and one work element as the pairing rule builds it (plan.cpp
+// sendrecv_elements).
+struct SrOp {
+  bool is_send;
+  int peer;
+  void* buf;  // a send's buffer is only read
+  size_t bytes;
+};
+struct SrElem {
+  const void* send = nullptr;
+  size_t S = 0;  // bytes to the channel's successor
+  void* recv = nullptr;
+  size_t R = 0;  // bytes from the channel's predecessor
+};
+
 // Entries of a comm's graph work arena held by captured launches.  A
 // captured launch takes a contiguous range, which returns when the graph that
 // holds it is destroyed (rt().GraphOnDestroy), so graphs captured again and
@@ -300,6 +316,9 @@ struct Comm {
     void* recv;
     size_t count;
   } direct{};
+  // Send/Recv: the group's calls on this comm in issue order; they become work
+  // elements when the group launches (plan_flush_sendrecv)
+  std::vector<SrOp> sr_ops;
   int share = 1;         // ranks of this communicator on this rank's GPU (co-residency of spinning launches)
   // operator / test overrides read once at creation (make_comm), not per
   // launch: MCCS_INLINE_WORKS=0 (works always through the work FIFO) and
@@ -373,6 +392,21 @@ mccsResult_t plan_enqueue_a2av(Comm* c, const void* send, const size_t* sendcoun
                                const size_t* recvcounts, const size_t* rdispls);
 // AllToAllvDev: per channel the FIFO element and the self element, both naming the size table.
 mccsResult_t plan_enqueue_a2av_dev(Comm* c, const void* send, void* recv, const uint64_t* table);
+// Send/Recv: how one rank's calls of one group become work elements, stated
+// once for the planner and the host-thread ring (as ring_walk.h states the
+// chunk walk).  next[c] / prev[c] are the rank's successor and predecessor on
+// channel c of a one-hop route.  A send to t joins the send queue of every
+// channel with next[c] == t, a receive from p the receive queue of every
+// channel with prev[c] == p, both in issue order, zero-byte calls included.
+// Element k of a channel holds its k-th send (S = 0, no buffer: none) and its
+// k-th receive (R = 0: none); each of the pair's m channels carries the whole
+// buffer and cuts its part by bid / recv_bid, as an AllToAllv pair's block is
+// cut.  A channel with no call gets one all-zero element, so out[c] is never
+// empty and every launch has every channel.
+void sendrecv_elements(int nch, const int* next, const int* prev, const SrOp* ops, int nops,
+                       std::vector<std::vector<SrElem>>* out);
+// One Send or Recv of a group joins the comm's pending calls (the caller checked the arguments and the route).
+mccsResult_t plan_enqueue_sendrecv(Comm* c, bool is_send, void* buf, size_t bytes, int peer);
 mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_t>& user_streams);
 // ring.hip
 const void* ring_kernel_ptr(int func, int dtype, int op);

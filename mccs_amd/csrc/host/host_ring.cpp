@@ -27,6 +27,7 @@
 #include <thread>
 #include <vector>
 
+#include "comm.h"  // SrOp, SrElem, sendrecv_elements: the planner's pairing rule
 #include "dtypes.h"
 #include "half_bits.h"
 #include "mccs_devcomm.h"
@@ -205,6 +206,8 @@ struct Ctx {
   const size_t* v_sdispls = nullptr;  // [r * n + t]
   const size_t* v_rdispls = nullptr;  // [r * n + s]
   const uint64_t* const* v_tables = nullptr;  // or: each rank's size table (ring_cfg.h MCCS_FUNC_ALLTOALLV_DEV)
+  // Send/Recv: each (rank, channel)'s elements, [r * nch + ch] (plan.cpp sendrecv_elements)
+  const std::vector<std::vector<mccs::SrElem>>* sr_elems = nullptr;
   size_t es, count;
   const void* const* send;
   void* const* recv;
@@ -409,6 +412,24 @@ void walk_alltoall(RankChannel& k) {
   }
 }
 
+// One v element (ring_walk.h a2av_next): a send walk of S bytes from k.input
+// and a receive walk of R bytes into k.output.  false: the ring failed.
+bool walk_v_elem(RankChannel& k, int64_t S, int64_t R, int64_t sbid, int64_t rbid) {
+  const RingWalk<int64_t>& w = k.w;
+  const int64_t ncalls = mccs::a2av_loops(S, w.loopSize) + mccs::a2av_loops(R, w.loopSize);
+  int64_t g = 0;
+  int side = mccs::a2av_first(S);
+  for (int64_t call = 0; call < ncalls; ++call) {
+    const bool recv = side == mccs::kA2AvRecv;
+    const int64_t size = recv ? R : S;
+    const int64_t rcs = mccs::a2av_chunk_size(w, size, g, k.parts);
+    const int64_t off = mccs::block_chunk_offset(g, recv ? rbid : sbid, rcs);
+    if (!k.op(recv, !recv, !recv, recv, off, off, mccs::chunk_nelem(size, off, rcs))) return false;  // <= 0: an empty call
+    side = mccs::a2av_next(S, R, w.loopSize, &g, side);
+  }
+  return true;
+}
+
 // AllToAllv (ring_walk.h a2av_next): the channel's send walk
 // over the bytes for its successor and its receive walk over the bytes of its
 // predecessor, each of its own length; the self block is a local copy
@@ -434,26 +455,29 @@ void walk_alltoallv(RankChannel& k) {
     self = {cnt[(size_t)r * n + r], sd[r], 0, rd[r]};
   }
   if (k.ch == 0 && self.S) std::memcpy(k.output + self.recvOff, k.input + self.sendOff, self.S);
-  const int64_t S = (int64_t)e.S, R = (int64_t)e.R;
   k.input += e.sendOff;
   k.output += e.recvOff;
-  const int64_t ncalls = mccs::a2av_loops(S, w.loopSize) + mccs::a2av_loops(R, w.loopSize);
-  int64_t g = 0;
-  int side = mccs::a2av_first(S);
-  for (int64_t call = 0; call < ncalls; ++call) {
-    const bool recv = side == mccs::kA2AvRecv;
-    const int64_t size = recv ? R : S;
-    const int64_t rcs = mccs::a2av_chunk_size(w, size, g, k.parts);
-    const int64_t off = mccs::block_chunk_offset(g, recv ? rbid : sbid, rcs);
-    if (!k.op(recv, !recv, !recv, recv, off, off, mccs::chunk_nelem(size, off, rcs))) return;  // <= 0: an empty call
-    side = mccs::a2av_next(S, R, w.loopSize, &g, side);
+  walk_v_elem(k, (int64_t)e.S, (int64_t)e.R, sbid, rbid);
+}
+
+// Send/Recv (plan.cpp sendrecv_elements): the channel's
+// elements in order, each an AllToAllv element on the calls' own buffers; the
+// connection's steps carry over from one element to the next.
+void walk_sendrecv(RankChannel& k) {
+  const int r = k.rank;
+  const int64_t sbid = k.c->a2a_send_bid[r * k.c->nch + k.ch], rbid = k.c->a2a_recv_bid[r * k.c->nch + k.ch];
+  for (const mccs::SrElem& e : (*k.c->sr_elems)[(size_t)r * k.c->nch + k.ch]) {
+    k.input = (const char*)e.send;
+    k.output = (char*)e.recv;
+    if (!walk_v_elem(k, (int64_t)e.S, (int64_t)e.R, sbid, rbid)) return;
   }
 }
 
 // one (rank, channel) thread
 void run_rank_channel(Ctx* c, int rank, int ch) {
   RankChannel k(c, rank, ch);
-  if (c->func == MCCS_FUNC_ALLTOALLV) walk_alltoallv(k);
+  if (c->func == MCCS_FUNC_SENDRECV) walk_sendrecv(k);
+  else if (c->func == MCCS_FUNC_ALLTOALLV) walk_alltoallv(k);
   else if (c->func == MCCS_FUNC_ALLTOALL) walk_alltoall(k);
   else if (c->func == mccsFuncReduceScatter) walk_reduce_scatter(k);
   else if (c->func == mccsFuncBoadcast || c->func == mccsFuncReduce) walk_rooted(k);
@@ -750,6 +774,89 @@ extern "C" mccsResult_t mccs_host_ring_all_to_all_v_tables(int nranks, const voi
   if (!tables) return mccsInvalidArgument;
   return host_ring_a2av(nranks, sendbufs, recvbufs, nullptr, nullptr, nullptr, tables, nchannels, nthreads_ref,
                         buff_size, rings, force_relay);
+}
+
+// Send/Recv on host threads (mccsSend / mccsRecv): op i is a send or a receive
+// of op_bytes[i] bytes at op_buf[i] that rank op_rank[i] issues with
+// op_peer[i]; each rank's ops, in list order, form one group.  The elements
+// come from the planner's pairing rule (plan.cpp sendrecv_elements) and are
+// walked as AllToAllv's.  One hop only.  This entry point sees every rank, so
+// unlike the device path it refuses a send without its receive, or of another
+// size (mccsInvalidArgument), instead of stalling.
+extern "C" mccsResult_t mccs_host_ring_send_recv(int nranks, int nops, const int* op_rank, const int* op_is_send,
+                                                 const int* op_peer, void* const* op_buf, const size_t* op_bytes,
+                                                 int nchannels, int nthreads_ref, int buff_size, const int* rings) {
+  if (nranks < 2 || nranks > 64 || nops < 0 || (nops && (!op_rank || !op_is_send || !op_peer || !op_buf || !op_bytes)) ||
+      nchannels < 1 || nchannels > MCCS_MAX_NCHANNELS || nthreads_ref <= WARP_SIZE || buff_size < 8192 || buff_size % 8192)
+    return mccsInvalidArgument;
+  if (rings)
+    for (int ch = 0; ch < nchannels; ++ch) {
+      uint64_t seen = 0;
+      for (int i = 0; i < nranks; ++i)
+        if (rings[ch * nranks + i] >= 0 && rings[ch * nranks + i] < nranks) seen |= 1ull << rings[ch * nranks + i];
+      if (seen != (nranks == 64 ? ~0ull : (1ull << nranks) - 1)) return mccsInvalidArgument;  // not a permutation
+    }
+  std::vector<std::vector<mccs::SrOp>> ops((size_t)nranks);
+  // per ordered pair (s, t) the sizes of its sends and of its receives, in order: they must agree
+  std::vector<std::vector<size_t>> sent((size_t)nranks * nranks), rcvd((size_t)nranks * nranks);
+  for (int i = 0; i < nops; ++i) {
+    const int r = op_rank[i], p = op_peer[i];
+    if (r < 0 || r >= nranks || p < 0 || p >= nranks || p == r || (!op_buf[i] && op_bytes[i])) return mccsInvalidArgument;
+    ops[r].push_back(mccs::SrOp{op_is_send[i] != 0, p, op_buf[i], op_bytes[i]});
+    (op_is_send[i] ? sent[(size_t)r * nranks + p] : rcvd[(size_t)p * nranks + r]).push_back(op_bytes[i]);
+  }
+  if (sent != rcvd) return mccsInvalidArgument;
+  std::vector<int> ident;
+  if (!rings) {
+    for (int ch = 0; ch < nchannels; ++ch)
+      for (int i = 0; i < nranks; ++i) ident.push_back(i);
+    rings = ident.data();
+  }
+  std::vector<int> sb((size_t)nranks * nchannels), rb((size_t)nranks * nchannels);
+  int hops = 0, m = 0;
+  mccs::alltoall_route(nranks, nchannels, rings, false, &hops, &m, sb.data(), rb.data());
+  if (hops != 1 || m < 1) return mccsInvalidUsage;  // a relay: a message would need ranks that are not its two ends
+  std::vector<std::vector<mccs::SrElem>> elems((size_t)nranks * nchannels), one;
+  for (int r = 0; r < nranks; ++r) {
+    int next[MCCS_MAX_NCHANNELS], prev[MCCS_MAX_NCHANNELS];
+    for (int ch = 0; ch < nchannels; ++ch)
+      for (int i = 0; i < nranks; ++i)
+        if (rings[ch * nranks + i] == r) {
+          next[ch] = rings[ch * nranks + (i + 1) % nranks];
+          prev[ch] = rings[ch * nranks + (i + nranks - 1) % nranks];
+        }
+    mccs::sendrecv_elements(nchannels, next, prev, ops[r].data(), (int)ops[r].size(), &one);
+    for (int ch = 0; ch < nchannels; ++ch) elems[(size_t)r * nchannels + ch] = one[ch];
+  }
+  const std::vector<const void*> no_send((size_t)nranks, nullptr);
+  const std::vector<void*> no_recv((size_t)nranks, nullptr);
+  HostRingPool& pool = HostRingPool::get();
+  std::lock_guard<std::mutex> call(pool.call_mu);
+  std::vector<HostConn>& conns = pool.fifos((size_t)nchannels * nranks, (size_t)buff_size);
+  Ctx c;
+  c.func = MCCS_FUNC_SENDRECV;
+  c.n = nranks;
+  c.nch = nchannels;
+  c.dt = mccsInt8;
+  c.op = mccsDevSum;
+  c.op_arg = 0;
+  c.nthreads_ref = nthreads_ref;
+  c.buff_size = buff_size;
+  c.es = 1;
+  c.count = 0;  // each walk has its own size
+  c.send = no_send.data();  // every element names its own buffers
+  c.recv = no_recv.data();
+  c.rings = rings;
+  c.root = 0;
+  c.conns = &conns;
+  c.timeout_s = 60.0;
+  c.a2a_hops = 1;
+  c.walk_nch = m;
+  c.a2a_send_bid = sb.data();
+  c.a2a_recv_bid = rb.data();
+  c.sr_elems = &elems;
+  pool.run(&c, nranks * nchannels);
+  return c.failed.load() ? mccsTimeout : mccsSuccess;
 }
 
 // The three reducing collectives with an op argument: all six ops, PreMulSum's

@@ -296,8 +296,87 @@ mccsResult_t plan_enqueue_a2av_dev(Comm* c, const void* send, void* recv, const 
   return mccsSuccess;
 }
 
+// Send/Recv: the pairing rule (comm.h).  Pairing by queue index cannot
+// deadlock: DESIGN.md §3.2 has the argument.
+void sendrecv_elements(int nch, const int* next, const int* prev, const SrOp* ops, int nops,
+                       std::vector<std::vector<SrElem>>* out) {
+  out->resize((size_t)nch);  // (a caller's vector keeps its capacity from launch to launch)
+  for (auto& q : *out) q.clear();
+  size_t nsend[MCCS_MAX_NCHANNELS] = {}, nrecv[MCCS_MAX_NCHANNELS] = {};  // nch <= MCCS_MAX_NCHANNELS
+  for (int i = 0; i < nops; ++i) {
+    const SrOp& o = ops[i];
+    for (int ch = 0; ch < nch; ++ch) {
+      if ((o.is_send ? next[ch] : prev[ch]) != o.peer) continue;
+      std::vector<SrElem>& q = (*out)[ch];
+      const size_t k = o.is_send ? nsend[ch]++ : nrecv[ch]++;
+      if (k == q.size()) q.emplace_back();
+      if (o.is_send) {
+        q[k].send = o.buf;
+        q[k].S = o.bytes;
+      } else {
+        q[k].recv = o.buf;
+        q[k].R = o.bytes;
+      }
+    }
+  }
+  for (auto& q : *out)
+    if (q.empty()) q.emplace_back();  // an idle channel: no call, no step, but in the launch
+}
+
+mccsResult_t plan_enqueue_sendrecv(Comm* c, bool is_send, void* buf, size_t bytes, int peer) {
+  if (c->plan_pending && c->plan_func != MCCS_FUNC_SENDRECV)
+    MCCS_FAIL(mccsInvalidUsage, "a group mixes collectives of different function / dtype / op on one communicator");
+  c->sr_ops.push_back(SrOp{is_send, peer, buf, bytes});
+  c->plan_pending = true;
+  c->plan_func = MCCS_FUNC_SENDRECV;
+  c->plan_dtype = mccsInt8;
+  c->plan_op = mccsDevSum;
+  return mccsSuccess;
+}
+
+// The group is complete: the comm's Send/Recv calls become elements, on every
+// channel of the comm (fused rank slots share one channel mask).  An element
+// is an AllToAllv element with hops = 1 whose buffers are the calls' own; the
+// thread count is the schema's largest, for AllToAllv's reason.  A group whose
+// calls are all empty launches nothing.
+static mccsResult_t plan_flush_sendrecv(Comm* c) {
+  bool any = false;
+  for (const SrOp& o : c->sr_ops) any = any || o.bytes > 0;
+  if (!any) {
+    plan_discard(c);
+    return mccsSuccess;
+  }
+  if (c->a2a_hops != 1 || c->a2a_m < 1) return mccsInternalError;  // api.cpp refused it
+  const int n = c->nranks, r = c->rank;
+  int next[MCCS_MAX_NCHANNELS], prev[MCCS_MAX_NCHANNELS];
+  for (int ch = 0; ch < c->nch; ++ch) {
+    const std::vector<int>& ring = c->rings[ch];
+    const int pos = (int)(std::find(ring.begin(), ring.end(), r) - ring.begin());
+    next[ch] = ring[(pos + 1) % n];
+    prev[ch] = ring[(pos + n - 1) % n];
+  }
+  static thread_local std::vector<std::vector<SrElem>> elems;  // kept per thread: an eager launch allocates nothing
+  sendrecv_elements(c->nch, next, prev, c->sr_ops.data(), (int)c->sr_ops.size(), &elems);
+  c->sr_ops.clear();
+  for (int ch = 0; ch < c->nch; ++ch)
+    for (const SrElem& s : elems[ch]) {
+      WorkElemHost e{};
+      e.nWarps = (uint8_t)((kSimpleMaxThreads + WARP_SIZE) / WARP_SIZE);
+      e.send = s.send;
+      e.recv = s.recv;
+      e.count = s.S;
+      e.op_arg = (uint64_t)s.R;
+      e.bid = c->a2a_send_bid[ch];
+      e.nChannels = (uint8_t)c->a2a_m;
+      e.root = MCCS_A2A_ROUTE(1, c->a2a_recv_bid[ch], 0, 0);
+      enqueue_elem(c->sched[ch], e, 0, 1);
+    }
+  return mccsSuccess;
+}
+
 void plan_discard(Comm* c) {
   for (auto& s : c->sched) s.reset();
+  c->sr_ops.clear();
   c->plan_pending = false;
   c->plan_direct = false;
 }
@@ -634,13 +713,14 @@ int coresident_ring_blocks(int block, int device) {
   int ncu = 0;
   if (rt().CuCount(&ncu, device) != hipSuccess) return 0;
   int best = 1 << 30;
-  const void* fns[5 + 3 * mccsNumTypes * mccsNumDevRedOps];
+  const void* fns[6 + 3 * mccsNumTypes * mccsNumDevRedOps];
   int nf = 0;
   fns[nf++] = ring_multi_kernel_ptr(mccsFuncAllGather, mccsInt8, 0);
   fns[nf++] = ring_multi_kernel_ptr(mccsFuncBoadcast, mccsInt8, 0);
   fns[nf++] = ring_multi_kernel_ptr(MCCS_FUNC_ALLTOALL, mccsInt8, 0);
   fns[nf++] = ring_multi_kernel_ptr(MCCS_FUNC_ALLTOALLV, mccsInt8, 0);
   fns[nf++] = ring_multi_kernel_ptr(MCCS_FUNC_ALLTOALLV_DEV, mccsInt8, 0);
+  fns[nf++] = ring_multi_kernel_ptr(MCCS_FUNC_SENDRECV, mccsInt8, 0);
   for (int dt = 0; dt < mccsNumTypes; ++dt)
     for (int op = 0; op < mccsNumDevRedOps; ++op) {
       if (op == mccsDevSumPostDiv && !is_integer_dtype(dt)) continue;  // no such kernel
@@ -846,6 +926,8 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
   // thread: an eager launch allocates nothing)
   static thread_local std::vector<int> order, idx;
   order.clear();
+  for (Comm* c : comms)  // a group's Send/Recv calls are paired into elements now that it is complete
+    if (c->plan_pending && c->plan_func == MCCS_FUNC_SENDRECV && !c->sr_ops.empty()) MCCS_CHECK(plan_flush_sendrecv(c));
   for (int i = 0; i < (int)comms.size(); ++i) {
     if (!comms[i]->plan_pending) continue;
     order.push_back(i);

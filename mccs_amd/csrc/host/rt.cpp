@@ -429,6 +429,9 @@ class FakeRuntime final : public DeviceRuntime {
         // AllToAllvDev: the same record under its own key (count is the size table's address)
         if (fn == ring_multi_kernel_ptr(MCCS_FUNC_ALLTOALLV_DEV, mccsInt8, mccsDevSum))
           extra += " a2avd=" + a2a_routes(ma, grid.y, true);
+        // Send/Recv: the v record plus nWarps, ';' between a slot's channels
+        if (fn == ring_multi_kernel_ptr(MCCS_FUNC_SENDRECV, mccsInt8, mccsDevSum))
+          extra += " sr=" + a2a_routes(ma, grid.y, true, true);
       }
     }
     note("launch dev=" + std::to_string(cur_) + " grid=" + std::to_string(grid.x) + "x" + std::to_string(grid.y) +
@@ -472,20 +475,24 @@ class FakeRuntime final : public DeviceRuntime {
   // element, '/' between rank slots, ',' between elements.
   // An AllToAllv launch (v): route word (hex), bid, nChannels, count,
   // redOpArg (the receive walk's bytes) and both buffers (hex), ':' between.
-  static std::string a2a_routes(const mccsMultiLaunchArgs* ma, unsigned nslots, bool v = false) {
+  // A Send/Recv launch (sr): the v record with ":nWarps" appended, and ';'
+  // instead of ',' where a slot's next channel begins (a channel may hold
+  // several elements, or chained works).
+  static std::string a2a_routes(const mccsMultiLaunchArgs* ma, unsigned nslots, bool v = false, bool sr = false) {
     std::string out;
     const int nch = __builtin_popcountll(ma->channelMask);
     for (unsigned k = 0; k < nslots; ++k) {
       if (k) out += "/";
-      bool first = true;
+      bool first = true, chan_start = false;
       auto elem = [&](const mccsDevWorkElem& e) {
         if (v) {
-          char buf[160];
-          std::snprintf(buf, sizeof(buf), "%x:%u:%u:%llu:%llu:%llx:%llx", (unsigned)e.root, (unsigned)e.bid,
-                        (unsigned)e.nChannels, (unsigned long long)e.count, (unsigned long long)e.redOpArg,
-                        (unsigned long long)(uintptr_t)e.sendbuff, (unsigned long long)(uintptr_t)e.recvbuff);
-          out += (first ? "" : ",") + std::string(buf);
-          first = false;
+          char buf[176];
+          int len = std::snprintf(buf, sizeof(buf), "%x:%u:%u:%llu:%llu:%llx:%llx", (unsigned)e.root, (unsigned)e.bid,
+                                  (unsigned)e.nChannels, (unsigned long long)e.count, (unsigned long long)e.redOpArg,
+                                  (unsigned long long)(uintptr_t)e.sendbuff, (unsigned long long)(uintptr_t)e.recvbuff);
+          if (sr) std::snprintf(buf + len, sizeof(buf) - (size_t)len, ":%u", (unsigned)e.nWarps);
+          out += (first ? "" : sr && chan_start ? ";" : ",") + std::string(buf);
+          first = chan_start = false;
           return;
         }
         out += (first ? "" : ",") + std::to_string(MCCS_A2A_HOPS(e.root)) + ":" + std::to_string(e.bid) + ":" +
@@ -493,6 +500,7 @@ class FakeRuntime final : public DeviceRuntime {
         first = false;
       };
       for (int i = 0; i < nch; ++i) {
+        chan_start = true;
         if (ma->inline_works) {
           elem(ma->inline_work[k * nch + i].elem);
           continue;

@@ -5,7 +5,8 @@
 // ring_rs_{sum,prod,max,min}.hip, the forty Reduce kernels in
 // ring_rd_{sum,prod,max,min}.hip, the Broadcast kernel in ring_bc.hip and the
 // AllToAll kernel in ring_a2a.hip, the AllToAllv kernel in ring_a2av.hip,
-// the AllToAllvDev kernel (sizes read on the device) in ring_a2avd.hip.
+// the AllToAllvDev kernel (sizes read on the device) in ring_a2avd.hip, the
+// Send/Recv kernel in ring_sr.hip.
 // PreMulSum (ten types) and SumPostDiv (the six integer types) add
 // ring_{ar,rs,rd}_{premulsum,sumpostdiv}.hip: 48 more kernels.
 #include "ring_kernel.h"
@@ -52,6 +53,7 @@ const void* ring_bc_kernel();
 const void* ring_a2a_kernel();
 const void* ring_a2av_kernel();
 const void* ring_a2avd_kernel();
+const void* ring_sr_kernel();
 hipError_t ring_tu_rd_sum_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_rd_prod_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_rd_max_read_profile(unsigned long long* out, bool reset);
@@ -60,6 +62,7 @@ hipError_t ring_tu_bc_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_a2a_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_a2av_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_a2avd_read_profile(unsigned long long* out, bool reset);
+hipError_t ring_tu_sr_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_rs_sum_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_rs_prod_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_tu_rs_max_read_profile(unsigned long long* out, bool reset);
@@ -137,6 +140,7 @@ const void* ring_multi_kernel_ptr(int func, int dtype, int op) {
   if (func == MCCS_FUNC_ALLTOALL) return ring_a2a_kernel();
   if (func == MCCS_FUNC_ALLTOALLV) return ring_a2av_kernel();
   if (func == MCCS_FUNC_ALLTOALLV_DEV) return ring_a2avd_kernel();
+  if (func == MCCS_FUNC_SENDRECV) return ring_sr_kernel();
   if (func != mccsFuncAllReduce) return nullptr;
   return ar_kernel(dtype, op, true);
 }
@@ -172,7 +176,7 @@ hipError_t ring_read_profile(unsigned long long* out, bool reset) {
       ring_tu_rd_min_read_profile, ring_tu_bc_read_profile, ring_tu_ar_premulsum_read_profile,
       ring_tu_ar_sumpostdiv_read_profile, ring_tu_rs_premulsum_read_profile, ring_tu_rs_sumpostdiv_read_profile,
       ring_tu_rd_premulsum_read_profile, ring_tu_rd_sumpostdiv_read_profile, ring_tu_a2a_read_profile,
-      ring_tu_a2av_read_profile, ring_tu_a2avd_read_profile};
+      ring_tu_a2av_read_profile, ring_tu_a2avd_read_profile, ring_tu_sr_read_profile};
   for (auto rd : readers) {
     hipError_t e = rd(out, reset);
     if (e != hipSuccess) return e;

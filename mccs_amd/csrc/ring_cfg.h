@@ -136,6 +136,21 @@ struct mccsLaunchGuard {
 #define MCCS_A2AVD_NEXT(route) MCCS_A2A_PART(route)
 #define MCCS_A2AVD_PREV(route) MCCS_A2A_PARTS(route)
 
+// ---- Send/Recv (ring_sr.hip, host/plan.cpp sendrecv_elements) ---------------
+// Grouped point-to-point on the one-hop route.  The reference reserves
+// mccsFuncSendRecv = 5, mccsFuncSend = 6 and mccsFuncRecv = 7 with a P2p work
+// element (mccsDevWorkElemP2p) that presumes peer-indexed connectors; this
+// library builds ring connectors only, so Send/Recv runs on them under an id
+// of its own, with mccsDevWorkTypeColl works of the usual element layout.
+#define MCCS_FUNC_SENDRECV 11
+// A Send/Recv work element is an AllToAllv element with hops = 1 and no
+// displacement: sendbuff = a send's buffer and count = its bytes S, for the
+// channel's successor (part bid of the pair's m channels); recvbuff = a
+// receive's buffer and redOpArg = its bytes R, from the channel's predecessor
+// (part recv_bid of the route word).  S = 0 or R = 0: that side makes no call
+// and takes no step.  Which call of a group lands in which element of which
+// channel is the pairing rule of host/plan.cpp sendrecv_elements.
+
 // Per-device ring profile counters (s_memrealtime ticks, 100 MHz), summed
 // over every slice of every workgroup while mccsRingKernelCfg.profile is set.
 #define MCCS_PROF_SLICES 0  // slices executed

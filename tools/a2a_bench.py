@@ -11,6 +11,7 @@ here only its extra FIFO copies.
   python tools/a2a_bench.py [--n 8] [--sizes-kib 64 1024] [--out FILE.jsonl]
   python tools/a2a_bench.py --v [--out FILE.jsonl]
   python tools/a2a_bench.py --v --dev [--out FILE.jsonl]
+  python tools/a2a_bench.py --p2p [--out FILE.jsonl]
 
 --v: AllToAllv beside AllToAll.  Per size one process alternates a
 uniform-count AllToAllv with an AllToAll of the same bytes, five repeats of
@@ -27,6 +28,13 @@ Uniform counts; per size one process alternates the yardstick, the eager Dev
 call and a replayed graph holding exchange_counts and the Dev call, five
 repeats of each, and reports the three ranges, the ratios of the medians and the
 yardstick's own spread (max / min), the margin the ratios are read against.
+
+--p2p: Send/Recv beside AllToAllv.  The pattern is a ring shift: every rank
+sends one message to rank + 1 and receives one from rank - 1, as one group per
+call.  The yardstick is mccsAllToAllv with the same sparse matrix (what a
+caller had to use before).  Per message size one process alternates the two,
+five repeats of each, and reports both ranges, the ratio of the medians and the
+yardstick's own spread (max / min), the margin the ratio is read against.
 
 Every (n, size, mode) step runs in a fresh child process under its own time
 limit; the first step that fails or runs out of time ends the run.
@@ -213,6 +221,70 @@ def step_dev(n, kib, iters, repeats=5):
     print(json.dumps(out), flush=True)
 
 
+def step_p2p(n, kib, iters, repeats=5):
+    """One --p2p step: a ring shift as one Send/Recv group per call, and the
+    AllToAllv of the same sparse matrix (the yardstick), alternating."""
+    import statistics
+
+    import torch
+
+    from mccs_amd import comm as C
+
+    comms = C.init_all([0] * n, C.CommConfig(direct_bytes=-1, oneshot_bytes=-1, ll_bytes=-1))
+    B = kib << 10
+    xs = [torch.randint(0, 255, (B,), dtype=torch.uint8, device="cuda") for _ in range(n)]
+    ys = [torch.empty(B, dtype=torch.uint8, device="cuda") for _ in range(n)]
+    xp, yp = [x.data_ptr() for x in xs], [y.data_ptr() for y in ys]
+    sz = lambda v: (ctypes.c_size_t * n)(*v)  # marshalled once: the loop times the library, not the wrapper
+    zero = sz([0] * n)
+    sc = [sz([B if t == (r + 1) % n else 0 for t in range(n)]) for r in range(n)]
+    rc = [sz([B if s == (r - 1) % n else 0 for s in range(n)]) for r in range(n)]
+    u8 = int(C.AllReduceDataType.Uint8)
+    # looked up once, like the sizes: the wrapper's default-stream lookup costs as much per call as the library
+    # does, and the shift makes two calls per rank where the yardstick makes one
+    st = torch.cuda.current_stream().cuda_stream
+    torch.cuda.synchronize()
+
+    def shift(r):
+        C.send(comms[r], xp[r], B, u8, (r + 1) % n, stream=st)
+        C.recv(comms[r], yp[r], B, u8, (r - 1) % n, stream=st)
+
+    calls = {"alltoallv_sparse": lambda r: C.all_to_all_v(comms[r], xp[r], sc[r], zero, yp[r], rc[r], zero, stream=st),
+             "sendrecv_shift": shift}
+
+    def run(call, k):
+        for _ in range(k):
+            with C.group():
+                for r in range(n):
+                    call(r)
+        for c in comms:
+            c.sync()
+        torch.cuda.synchronize()
+
+    for call in calls.values():
+        run(call, 2)
+        for r in range(n):
+            assert torch.equal(ys[r], xs[(r - 1) % n]), r
+            ys[r].zero_()
+    times = {k: [] for k in calls}
+    for _ in range(repeats):
+        for name, call in calls.items():  # alternating, in one process
+            t0 = time.perf_counter()
+            run(call, iters)
+            times[name].append(round((time.perf_counter() - t0) / iters * 1e6, 1))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    out = {"bench": "sendrecv", "pattern": "ring shift", "n": n, "KiB_per_message": kib, "lanes": comms[0].lanes,
+           "channels": comms[0].nchannels, "iters": iters, "repeats": repeats, **comms[0].all_to_all_route()}
+    for k, v in times.items():
+        out[k + "_us"] = [min(v), med[k], max(v)]  # min, median, max of the repeats
+    out["sendrecv_over_alltoallv"] = round(med["sendrecv_shift"] / med["alltoallv_sparse"], 3)
+    out["alltoallv_spread"] = round(max(times["alltoallv_sparse"]) / min(times["alltoallv_sparse"]), 3)
+    torch.cuda.synchronize()
+    for c in comms:
+        c.destroy()
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[8])
@@ -222,23 +294,27 @@ def main():
     ap.add_argument("--out", default=None, help="also append the result lines to this file")
     ap.add_argument("--v", action="store_true", help="AllToAllv beside AllToAll (one hop only)")
     ap.add_argument("--dev", action="store_true", help="with --v: AllToAllvDev beside the host-count AllToAllv")
+    ap.add_argument("--p2p", action="store_true", help="a Send/Recv ring shift beside the sparse AllToAllv")
     ap.add_argument("--step", type=int, nargs=2, default=None, help=argparse.SUPPRESS)  # child: n KiB
     args = ap.parse_args()
     if args.dev and not args.v:
         ap.error("--dev goes with --v")
+    if args.p2p and args.v:
+        ap.error("--p2p is a mode of its own")
     if args.step:
-        (step_dev if args.v and args.dev else step_v if args.v else step)(args.step[0], args.step[1], args.iters)
+        (step_p2p if args.p2p else step_dev if args.v and args.dev else step_v if args.v else step)(
+            args.step[0], args.step[1], args.iters)
         return 0
     for n in args.n:
         for kib in args.sizes_kib:
-            for relay in ((False,) if args.v else (False, True)):
+            for relay in ((False,) if args.v or args.p2p else (False, True)):
                 env = dict(os.environ)
                 env.pop("MCCS_ALLTOALL_HOPS", None)
                 if relay:
                     env["MCCS_ALLTOALL_HOPS"] = "relay"
                 cmd = ["timeout", "-k", "10", str(args.step_timeout), sys.executable, os.path.abspath(__file__),
                        "--step", str(n), str(kib), "--iters", str(args.iters)] + (["--v"] if args.v else []) + \
-                      (["--dev"] if args.v and args.dev else [])
+                      (["--dev"] if args.v and args.dev else []) + (["--p2p"] if args.p2p else [])
                 r = subprocess.run(cmd, capture_output=True, text=True, env=env)
                 lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
                 if r.returncode != 0 or not lines:
