@@ -329,8 +329,11 @@ mccsResult_t mccsReduce(const void *sendbuff, void *recvbuff, size_t count, int 
  * route lives in the captured work list); the watchdog and mccsCommAbort end a
  * stuck kernel; several AllToAlls of one comm in one group are batched into one
  * launch, and mixing it with another function on one comm in a group is refused
- * with mccsInvalidUsage at mccsGroupEnd.  Always the ring (mccsCommLastAlgo
- * reports MCCS_ALGO_RING), whatever the direct / one-shot / LL thresholds. */
+ * with mccsInvalidUsage at mccsGroupEnd.  The ring (mccsCommLastAlgo reports
+ * MCCS_ALGO_RING) whatever the direct / one-shot / LL thresholds, unless the
+ * communicator opted in to the LL all-to-all (mccsCommSetAllToAllLL, below):
+ * then a call of at most that limit per peer which is its communicator's only
+ * call of the launch takes the LL kernel (MCCS_ALGO_LL), on any route. */
 mccsResult_t mccsAllToAll(const void *sendbuff, void *recvbuff, size_t bytes_per_peer, mccsComm_t comm,
                           hipStream_t stream);
 /* The comm's AllToAll route: info2[0] hops (1: one hop; nranks - 1: relay; 0
@@ -361,7 +364,9 @@ mccsResult_t mccsCommAllToAllRoute(mccsComm_t comm, int *info2);
  * send segment of non-zero length (the call is out of place).  Send segments
  * may overlap each other: the same bytes may go to two peers.
  * All counts zero: success, nothing is launched.  nranks == 1: the self copy
- * only.  Always the ring: no direct threshold applies.  Every element runs
+ * only.  The ring, and no direct threshold applies, unless the communicator
+ * opted in to the LL all-to-all for the v calls (mccsCommSetAllToAllLL, below,
+ * which changes four of the rules above).  Every ring element runs
  * with the schema's largest thread count (a pair's two ends know no common
  * byte total to derive a smaller one from).  Graph capture: counts and
  * displacements are baked into the captured work elements, and a replay
@@ -399,7 +404,9 @@ mccsResult_t mccsAllToAllv(const void *sendbuff, const size_t *sendcounts, const
  * turns out to be zero (a zero count makes no FIFO call and takes no step on
  * that side).  Its works always go through the work FIFO or, in a capture, the
  * graph work arena, never in the launch arguments.  nranks == 1: the self copy,
- * its size and both offsets read from the table.  Always the ring.
+ * its size and both offsets read from the table.  The ring, unless the
+ * communicator opted in to the LL all-to-all for the v calls
+ * (mccsCommSetAllToAllLL, below).
  * Graph capture: the captured elements hold the table's address and the two
  * base pointers, and every replay reads the table anew, so a graph captured once
  * moves each step's own sizes (write the table, or have a kernel write it,
@@ -408,6 +415,50 @@ mccsResult_t mccsAllToAllv(const void *sendbuff, const size_t *sendcounts, const
  * refused as for mccsAllToAll.  Otherwise as mccsAllToAllv. */
 mccsResult_t mccsAllToAllvDev(const void *sendbuff, void *recvbuff, const uint64_t *table, mccsComm_t comm,
                               hipStream_t stream);
+/* The LL all-to-all: mccsAllToAll, mccsAllToAllv and mccsAllToAllvDev at small
+ * sizes through the flag-carrying 16-byte lines of the LL one-shot (DESIGN.md
+ * §3.4) instead of the ring FIFOs.  Opt-in per communicator; both limits
+ * default to 0 = off, and with both off every call plans exactly as without
+ * this entry point.  MCCS_A2A_LL_BYTES / MCCS_A2AV_LL_BYTES in the environment
+ * set them when the communicator is created (clamped to the maximum below).
+ * mccsCommAllToAllLLMax: the most bytes one ordered pair can move in one
+ * launch, ll_slot / 2 - 8 with ll_slot = 2 x ll_bytes (a header line, then 8
+ * data bytes per 16-byte line); 0 where the lines cannot be used: no LL slots
+ * (ll_bytes < 0, nranks outside 2..8), a cached FIFO arena, system-scope
+ * fences.
+ * mccsCommSetAllToAllLL: a value above that maximum is refused with
+ * mccsInvalidArgument; a call while the communicator has a group open or a
+ * call pending, with mccsInvalidUsage.  EVERY RANK MUST SET THE SAME TWO
+ * VALUES: ranks that disagree pick different kernels for one call and stall
+ * until the watchdog; like disagreeing roots this is not detected.
+ * bytes_per_peer > 0: an mccsAllToAll of at most that many bytes per peer that
+ * is its communicator's only call of the launch takes the LL kernel
+ * (mccsCommLastAlgo reports MCCS_ALGO_LL); a larger one, or one sharing a
+ * group with a second call of the communicator, takes the ring as before.
+ * Every rank knows the size, so every rank decides alike.  No route is needed:
+ * 6 ranks and MCCS_ALLTOALL_HOPS=relay take it too.
+ * v_bytes_per_peer > 0 is the caller's PROMISE that no count of any
+ * mccsAllToAllv / mccsAllToAllvDev call on any rank of the communicator exceeds
+ * it (a rank sees only its own row and column, so it cannot decide from its
+ * counts): for example a MoE capacity bound.  Then
+ *   - every v / Dev call that is its communicator's only call of the launch
+ *     takes the LL kernel, whatever its counts;
+ *   - it always launches, also with every count zero: the peers wait for this
+ *     rank's header lines;
+ *   - the relay-route refusal does not apply to it;
+ *   - a host count above the limit is refused with mccsInvalidArgument
+ *     (mccsGetLastErrorString names the peer); a Dev count above it is clamped
+ *     in the kernel, on both sides, to the maximum above: the bytes are
+ *     truncated and nothing is written past a slot;
+ *   - every other argument rule stays;
+ *   - a v call sharing a group with a second call of its communicator falls
+ *     back to the ring, under the ring's rules (the relay refusal included).
+ * Ranks sharing a GPU are fused into one launch as always; their counts may
+ * differ.  A captured launch bakes host counts and displacements in; a Dev
+ * launch re-reads its table at every replay.  The node gate does not cover
+ * this path. */
+mccsResult_t mccsCommSetAllToAllLL(mccsComm_t comm, size_t bytes_per_peer, size_t v_bytes_per_peer);
+mccsResult_t mccsCommAllToAllLLMax(mccsComm_t comm, size_t *cap);
 /* Send / Recv: grouped point-to-point (torch's batch_isend_irecv; the pieces of
  * a Gather or Scatter).  mccsSend moves count * elem_bytes(dtype) bytes from
  * sendbuff to rank `peer`, mccsRecv receives as many from rank `peer` into

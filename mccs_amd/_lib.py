@@ -109,6 +109,8 @@ SIGNATURES: dict[str, tuple] = {
     "mccsReduce": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_int, _c_int, _c_void_p, _c_void_p]),
     "mccsAllToAll": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_void_p, _c_void_p]),
     "mccsCommAllToAllRoute": (_c_int, [_c_void_p, _P(_c_int)]),
+    "mccsCommSetAllToAllLL": (_c_int, [_c_void_p, _c_size_t, _c_size_t]),
+    "mccsCommAllToAllLLMax": (_c_int, [_c_void_p, _P(_c_size_t)]),
     "mccs_alltoall_route": (
         _c_int, [_c_int, _c_int, _P(_c_int), _c_int, _P(_c_int), _P(_c_int), _P(_c_int), _P(_c_int)]),
     "mccs_host_ring_all_to_all": (

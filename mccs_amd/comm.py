@@ -238,6 +238,26 @@ class Communicator:
     def recv(self, buf, count: int, data_type=AllReduceDataType.Uint8, peer: int = 0, stream=None) -> None:
         recv(self, buf, count, data_type, peer, stream)
 
+    def set_all_to_all_ll(self, bytes_per_peer: int = 0, v_bytes_per_peer: int = 0) -> None:
+        """mccsCommSetAllToAllLL: opts the communicator in to the LL all-to-all
+        (0 = off, the default).  bytes_per_peer: an all_to_all of at most that
+        many bytes per peer that is the communicator's only call of its launch
+        takes the LL kernel (last_algo() == "ll").  v_bytes_per_peer: the
+        caller's promise that no count of any all_to_all_v / all_to_all_v_dev
+        call on any rank exceeds it; every such single call then takes the LL
+        kernel, on any route, and always launches.  Every rank must set the
+        same two values, each at most all_to_all_ll_max()."""
+        rc = _sig().mccsCommSetAllToAllLL(self._h, int(bytes_per_peer), int(v_bytes_per_peer))
+        _lib.check(rc, "mccsCommSetAllToAllLL")
+
+    def all_to_all_ll_max(self) -> int:
+        """mccsCommAllToAllLLMax: the most bytes one pair can move through its
+        LL slot in one launch (ll_bytes - 8); 0 where the LL lines cannot be
+        used (no LL slots, a cached arena, system-scope fences)."""
+        cap = ctypes.c_size_t(0)
+        _lib.check(_sig().mccsCommAllToAllLLMax(self._h, ctypes.byref(cap)), "mccsCommAllToAllLLMax")
+        return int(cap.value)
+
     def all_to_all_route(self) -> dict:
         """The comm's AllToAll route (mccsCommAllToAllRoute): hops (1: every
         block goes straight to its ring successor; nranks - 1: relayed along the
@@ -396,7 +416,9 @@ def reduce(comm: Communicator, send_buf, recv_buf, count: int, data_type=AllRedu
 def all_to_all(comm: Communicator, send_buf, recv_buf, nbytes: int, stream=None) -> None:
     """mccsAllToAll: `nbytes` bytes per peer; both buffers hold nranks * nbytes
     bytes.  Afterwards rank r's recv[s*nbytes + i] is rank s's send[r*nbytes + i].
-    Out of place only.  Always the ring connections; stream-ordered."""
+    Out of place only; stream-ordered.  The ring connections, unless the
+    communicator opted in with set_all_to_all_ll and nbytes is within its
+    limit: then the LL kernel (last_algo() == "ll")."""
     rc = _sig().mccsAllToAll(_ptr(send_buf), _ptr(recv_buf), int(nbytes), comm._h, _stream(stream))
     _lib.check(rc, "mccsAllToAll")
 
@@ -413,7 +435,9 @@ def all_to_all_v(comm: Communicator, send_buf, send_counts, send_displs, recv_bu
     """mccsAllToAllv: per-peer byte counts and displacements (nranks entries
     each, in bytes).  Rank r sends send_counts[t] bytes from send + send_displs[t]
     to rank t and receives recv_counts[s] bytes from rank s at recv +
-    recv_displs[s].  One-hop AllToAll routes only (all_to_all_route); out of
+    recv_displs[s].  One-hop AllToAll routes only (all_to_all_route), unless
+    set_all_to_all_ll(v_bytes_per_peer=...) sends the v calls through the LL
+    kernel, which needs no route and refuses a count above that limit; out of
     place only; a buffer may be None when all its counts are 0.  A caller whose
     sizes repeat may pass ctypes c_size_t arrays, which are used as they are."""
     n = comm.nranks
@@ -450,7 +474,9 @@ def all_to_all_v_dev(comm: Communicator, send_buf, recv_buf, table, stream=None)
     replay.  The host checks none of the sizes: the table must be complete
     earlier on the stream, stay unmodified until the call completes, agree
     with the peers' tables, and keep every segment inside its buffer.  Always
-    launches; one-hop routes only."""
+    launches; one-hop routes only, unless set_all_to_all_ll(v_bytes_per_peer=...)
+    sends the v calls through the LL kernel (any route; a count above the
+    limit is clamped on the device)."""
     rc = _sig().mccsAllToAllvDev(_ptr(send_buf), _ptr(recv_buf), _table_ptr(comm, table), comm._h, _stream(stream))
     _lib.check(rc, "mccsAllToAllvDev")
 
@@ -458,7 +484,9 @@ def all_to_all_v_dev(comm: Communicator, send_buf, recv_buf, table, stream=None)
 def exchange_counts(comm: Communicator, table, stream=None) -> None:
     """Fills row 2 of a size table (receive counts) from the peers' row 0
     (send counts) on the device: the uniform all_to_all of 8 bytes per peer.
-    Issue it on every rank, before all_to_all_v_dev on the same stream."""
+    Issue it on every rank, before all_to_all_v_dev on the same stream.  Being
+    an all_to_all of 8 bytes, it takes the LL kernel by itself once
+    set_all_to_all_ll set a uniform limit (any bytes_per_peer >= 8)."""
     p = _table_ptr(comm, table)
     if not p:
         raise ValueError("exchange_counts needs a size table")

@@ -284,8 +284,8 @@ static mccsResult_t reject_call(mccsResult_t e, const char* why) {
   return e;
 }
 
-// The v calls run on the one-hop AllToAll route only.
-static bool a2av_needs_relay(const Comm* c) { return c->nranks > 1 && (c->a2a_hops != 1 || c->a2a_m < 1); }
+// The v calls' ring path runs on the one-hop AllToAll route only (a2av_needs_relay, plan.cpp); a
+// call the LL kernel takes (a2av_takes_ll) needs no route.
 static mccsResult_t reject_relay(const Comm* c) {
   char why[256];
   std::snprintf(why, sizeof(why),
@@ -302,7 +302,8 @@ static mccsResult_t a2av_check_and_plan(Comm* c, const void* send, const size_t*
   if (!sendcounts || !sdispls || !recvcounts || !rdispls)
     return reject_call(mccsInvalidArgument, "null count or displacement array");
   const int n = c->nranks, r = c->rank;
-  if (a2av_needs_relay(c)) return reject_relay(c);
+  const bool ll = a2av_takes_ll(c);
+  if (!ll && a2av_needs_relay(c)) return reject_relay(c);
   size_t any_send = 0, any_recv = 0;
   for (int i = 0; i < n; ++i) {
     any_send |= sendcounts[i];
@@ -324,7 +325,18 @@ static mccsResult_t a2av_check_and_plan(Comm* c, const void* send, const size_t*
                            "a receive segment overlaps a send segment (the call is out of place only)");
     }
   }
-  if (!any_send && !any_recv) return mccsSuccess;  // nothing moves: nothing is launched
+  // the LL limit is the caller's promise for every count on every rank: a count above it is refused
+  if (c->a2av_ll_bytes > 0)
+    for (int i = 0; i < n; ++i)
+      if (sendcounts[i] > c->a2av_ll_bytes || recvcounts[i] > c->a2av_ll_bytes) {
+        char why[160];
+        std::snprintf(why, sizeof(why), "%s[%d] = %zu is above the AllToAllv LL limit of %zu bytes per peer",
+                      sendcounts[i] > c->a2av_ll_bytes ? "sendcounts" : "recvcounts", i,
+                      sendcounts[i] > c->a2av_ll_bytes ? sendcounts[i] : recvcounts[i], c->a2av_ll_bytes);
+        return reject_call(mccsInvalidArgument, why);
+      }
+  // nothing moves: nothing is launched -- except on the LL path, where the peers wait for this rank's headers
+  if (!any_send && !any_recv && !ll) return mccsSuccess;
   if (std::find(g_group.comms.begin(), g_group.comms.end(), c) == g_group.comms.end()) {
     g_group.comms.push_back(c);
     g_group.streams.push_back(stream);
@@ -370,7 +382,7 @@ static mccsResult_t launch_a2av_dev(Comm* c, const void* send, void* recv, const
     if (!table) return reject_call(mccsInvalidArgument, "null size table");
     if ((uintptr_t)table % 8) return reject_call(mccsInvalidArgument, "the size table is not 8-byte aligned");
     if (!send || !recv) return reject_call(mccsInvalidArgument, "null buffer (the host knows no count to excuse it)");
-    if (a2av_needs_relay(c)) return reject_relay(c);
+    if (!a2av_takes_ll(c) && a2av_needs_relay(c)) return reject_relay(c);
     if (std::find(g_group.comms.begin(), g_group.comms.end(), c) == g_group.comms.end()) {
       g_group.comms.push_back(c);
       g_group.streams.push_back(stream);
@@ -846,6 +858,33 @@ extern "C" mccsResult_t mccsRecv(void* recvbuff, size_t count, int dtype, int pe
 extern "C" long long mccs_a2avd_index(int row, int nranks, int peer) {
   if (row < 0 || row >= kA2AvdRows || nranks < 1 || peer < 0 || peer >= nranks) return -1;
   return (long long)a2avd_index(row, nranks, peer);
+}
+
+extern "C" mccsResult_t mccsCommAllToAllLLMax(mccsComm_t comm, size_t* cap) {
+  err_clear();
+  const Comm* c = (const Comm*)comm;
+  if (!c || !cap) MCCS_FAIL(mccsInvalidArgument, "mccsCommAllToAllLLMax: null communicator or output");
+  *cap = c->connected ? a2a_ll_cap(c) : 0;
+  return mccsSuccess;
+}
+
+extern "C" mccsResult_t mccsCommSetAllToAllLL(mccsComm_t comm, size_t bytes_per_peer, size_t v_bytes_per_peer) {
+  err_clear();
+  StepScope st("mccsCommSetAllToAllLL");
+  Comm* c = (Comm*)comm;
+  if (!c || !c->connected) MCCS_FAIL(mccsInvalidUsage, "the communicator is not connected");
+  if (g_group.depth > 0 || c->plan_pending)
+    MCCS_FAIL(mccsInvalidUsage, "the communicator has a group open or a call pending: set the limits between launches");
+  const size_t cap = a2a_ll_cap(c);
+  if (bytes_per_peer > cap || v_bytes_per_peer > cap)
+    MCCS_FAIL(mccsInvalidArgument, "%s %zu is above the %zu bytes one pair can move through its LL slot%s",
+              bytes_per_peer > cap ? "bytes_per_peer" : "v_bytes_per_peer",
+              bytes_per_peer > cap ? bytes_per_peer : v_bytes_per_peer, cap,
+              cap ? "" : " (no LL slots, a cached arena or system-scope fences: the LL path is closed here)");
+  c->a2a_ll_bytes = bytes_per_peer;
+  c->a2av_ll_bytes = v_bytes_per_peer;
+  a2a_ll_prepare(c);
+  return mccsSuccess;
 }
 
 extern "C" mccsResult_t mccsCommAllToAllRoute(mccsComm_t comm, int* info2) {

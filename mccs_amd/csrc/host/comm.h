@@ -316,6 +316,23 @@ struct Comm {
     void* recv;
     size_t count;
   } direct{};
+  // LL all-to-all (direct_a2a.h).  The opt-in limits (mccsCommSetAllToAllLL;
+  // MCCS_A2A_LL_BYTES / MCCS_A2AV_LL_BYTES at creation), both 0 = off: a
+  // uniform AllToAll of at most a2a_ll_bytes per peer, and every AllToAllv /
+  // AllToAllvDev once a2av_ll_bytes > 0 (the caller's promise that no count on
+  // any rank exceeds it), take the LL kernel when they are their comm's only
+  // call of the launch.  The pending call is held like `direct`: its four rows
+  // (a copy: a demotion to the ring needs them after the caller's arrays may
+  // be gone), or the Dev call's table.
+  size_t a2a_ll_bytes = 0, a2av_ll_bytes = 0;
+  bool plan_a2all = false;
+  int plan_calls = 0;  // collective calls queued on this comm since its last launch (plan_discard clears it)
+  struct {
+    const void* send;
+    void* recv;
+    const uint64_t* table;  // AllToAllvDev (plan_func says which call it is)
+    uint64_t rows[MCCS_A2A_LL_ROWS][MCCS_DIRECT_MAX_RANKS];
+  } a2all{};
   // Send/Recv: the group's calls on this comm in issue order; they become work
   // elements when the group launches (plan_flush_sendrecv)
   std::vector<SrOp> sr_ops;
@@ -407,6 +424,16 @@ void sendrecv_elements(int nch, const int* next, const int* prev, const SrOp* op
                        std::vector<std::vector<SrElem>>* out);
 // One Send or Recv of a group joins the comm's pending calls (the caller checked the arguments and the route).
 mccsResult_t plan_enqueue_sendrecv(Comm* c, bool is_send, void* buf, size_t bytes, int peer);
+// LL all-to-all: the most bytes one pair can move in a launch (0 where the LL lines can never be
+// used: no LL slots -- ll_bytes < 0 or nranks outside 2..8 --, a cached arena, system-scope fences)
+size_t a2a_ll_cap(const Comm* c);
+// reads MCCS_A2A_LL_BYTES / MCCS_A2AV_LL_BYTES into the comm's limits, clamped to a2a_ll_cap
+void a2a_ll_read_env(Comm* c);
+void a2a_ll_prepare(const Comm* c);  // after the limits changed: probes the LL kernel's co-residency once
+// whether an AllToAllv / AllToAllvDev issued now would be held for the LL kernel
+bool a2av_takes_ll(const Comm* c);
+// whether the v calls' ring path is closed to this comm (its route is not one hop)
+bool a2av_needs_relay(const Comm* c);
 mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_t>& user_streams);
 // ring.hip
 const void* ring_kernel_ptr(int func, int dtype, int op);
@@ -414,6 +441,8 @@ const void* ring_multi_kernel_ptr(int func, int dtype, int op);
 int coresident_ring_blocks(int block, int device);
 // direct.hip
 const void* direct_kernel_ptr(int dtype, int op);
+// direct_a2a.hip
+const void* a2a_ll_kernel_ptr();
 hipError_t ring_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_flush_caches(hipStream_t st);
 

@@ -190,10 +190,8 @@ static mccsResult_t a2a_enqueue(Comm* c, const void* send, void* recv, size_t co
 // The thread count is the schema's largest for every element of every rank:
 // the granule it sets cuts a pair's block, and the two ends of a connection
 // know no common byte total to derive a smaller one from.
-mccsResult_t plan_enqueue_a2av(Comm* c, const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
-                               const size_t* recvcounts, const size_t* rdispls) {
-  if (c->plan_pending && c->plan_func != MCCS_FUNC_ALLTOALLV)
-    MCCS_FAIL(mccsInvalidUsage, "a group mixes collectives of different function / dtype / op on one communicator");
+static mccsResult_t a2av_ring_enqueue(Comm* c, const void* send, const size_t* sendcounts, const size_t* sdispls,
+                                      void* recv, const size_t* recvcounts, const size_t* rdispls) {
   const int n = c->nranks, r = c->rank;
   const uint8_t nwarps = (uint8_t)((kSimpleMaxThreads + WARP_SIZE) / WARP_SIZE);
   const size_t self = sendcounts[r];
@@ -255,9 +253,7 @@ mccsResult_t plan_enqueue_a2av(Comm* c, const void* send, const size_t* sendcoun
 // enqueue_elem gets 0 (esize 0): a Dev call does not move the channels' loads.
 // One rank: the self element on every channel of the comm, cut by bid /
 // nChannels as any one-rank call.
-mccsResult_t plan_enqueue_a2av_dev(Comm* c, const void* send, void* recv, const uint64_t* table) {
-  if (c->plan_pending && c->plan_func != MCCS_FUNC_ALLTOALLV_DEV)
-    MCCS_FAIL(mccsInvalidUsage, "a group mixes collectives of different function / dtype / op on one communicator");
+static mccsResult_t a2av_dev_ring_enqueue(Comm* c, const void* send, void* recv, const uint64_t* table) {
   const int n = c->nranks, r = c->rank;
   const uint8_t nwarps = (uint8_t)((kSimpleMaxThreads + WARP_SIZE) / WARP_SIZE);
   if (n > 1 && (c->a2a_hops != 1 || c->a2a_m < 1)) return mccsInternalError;  // api.cpp refused it
@@ -293,6 +289,102 @@ mccsResult_t plan_enqueue_a2av_dev(Comm* c, const void* send, void* recv, const 
   c->plan_func = MCCS_FUNC_ALLTOALLV_DEV;
   c->plan_dtype = mccsInt8;
   c->plan_op = mccsDevSum;
+  return mccsSuccess;
+}
+
+// ---- LL all-to-all (direct_a2a.h): the planner path ---------------------------
+// The LL lines need what the LL one-shot needs (ll_fits): LL slots in an
+// uncached arena and no system-scope fences.
+size_t a2a_ll_cap(const Comm* c) {
+  if (c->layout.ll_slot == 0 || !c->own_arena_uncached || c->kcfg.fence_mode == MCCS_FENCE_SYSTEM) return 0;
+  return (size_t)MCCS_A2A_LL_CAP(c->layout.ll_slot);
+}
+
+void a2a_ll_read_env(Comm* c) {
+  const size_t cap = a2a_ll_cap(c);
+  auto read = [&](const char* name) {
+    const char* v = std::getenv(name);
+    const long long x = v ? std::atoll(v) : 0;
+    return x > 0 ? std::min((size_t)x, cap) : (size_t)0;
+  };
+  c->a2a_ll_bytes = read("MCCS_A2A_LL_BYTES");
+  c->a2av_ll_bytes = read("MCCS_A2AV_LL_BYTES");
+  a2a_ll_prepare(c);
+}
+
+bool a2av_needs_relay(const Comm* c) { return c->nranks > 1 && (c->a2a_hops != 1 || c->a2a_m < 1); }
+
+// The comm's first call since its last launch, with the v limit set and the
+// lines usable: every rank sees the same three facts, so every rank decides
+// alike (plan_calls, not plan_pending: a rank whose first call moved nothing
+// must still send its second one to the ring, as its peers do).
+bool a2av_takes_ll(const Comm* c) {
+  return c->a2av_ll_bytes > 0 && c->plan_calls == 0 && c->a2av_ll_bytes <= a2a_ll_cap(c);
+}
+
+static void hold_a2all(Comm* c, int func, const void* send, void* recv, const uint64_t* table) {
+  c->plan_a2all = true;
+  c->a2all.send = send;
+  c->a2all.recv = recv;
+  c->a2all.table = table;
+  c->plan_pending = true;
+  c->plan_func = func;
+  c->plan_dtype = mccsInt8;
+  c->plan_op = mccsDevSum;
+}
+
+// A pending LL all-to-all goes to the ring after all: the group holds a
+// second call of this comm, or the device's fused launch cannot run it.  A v
+// call then meets the ring path's rules, the relay refusal included; one that
+// moves nothing launches nothing there.
+static mccsResult_t demote_a2all(Comm* c) {
+  if (!c->plan_a2all) return mccsSuccess;
+  c->plan_a2all = false;
+  c->plan_pending = false;
+  const auto& h = c->a2all;
+  if (c->plan_func == MCCS_FUNC_ALLTOALL) return a2a_enqueue(c, h.send, h.recv, (size_t)h.rows[kA2AvdSendCounts][0]);
+  if (a2av_needs_relay(c))
+    MCCS_FAIL(mccsInvalidUsage, "an AllToAllv call shares its launch with another call of its communicator, so it takes "
+              "the ring, and the AllToAll route is not one hop (hops = %d over %d channels of %d ranks)", c->a2a_hops,
+              c->nch, c->nranks);
+  if (c->plan_func == MCCS_FUNC_ALLTOALLV_DEV) return a2av_dev_ring_enqueue(c, h.send, h.recv, h.table);
+  size_t rows[MCCS_A2A_LL_ROWS][MCCS_DIRECT_MAX_RANKS];
+  size_t any = 0;
+  for (int t = 0; t < c->nranks; ++t) {
+    for (int row = 0; row < MCCS_A2A_LL_ROWS; ++row) rows[row][t] = (size_t)h.rows[row][t];
+    any |= rows[kA2AvdSendCounts][t] | rows[kA2AvdRecvCounts][t];
+  }
+  if (!any) return mccsSuccess;
+  return a2av_ring_enqueue(c, h.send, rows[kA2AvdSendCounts], rows[kA2AvdSendDispls], h.recv, rows[kA2AvdRecvCounts],
+                           rows[kA2AvdRecvDispls]);
+}
+
+mccsResult_t plan_enqueue_a2av(Comm* c, const void* send, const size_t* sendcounts, const size_t* sdispls, void* recv,
+                               const size_t* recvcounts, const size_t* rdispls) {
+  if (c->plan_pending && c->plan_func != MCCS_FUNC_ALLTOALLV)
+    MCCS_FAIL(mccsInvalidUsage, "a group mixes collectives of different function / dtype / op on one communicator");
+  MCCS_CHECK(demote_a2all(c));
+  const bool ll = a2av_takes_ll(c);
+  ++c->plan_calls;
+  if (!ll) return a2av_ring_enqueue(c, send, sendcounts, sdispls, recv, recvcounts, rdispls);
+  for (int t = 0; t < c->nranks; ++t) {
+    c->a2all.rows[kA2AvdSendCounts][t] = sendcounts[t];
+    c->a2all.rows[kA2AvdSendDispls][t] = sdispls[t];
+    c->a2all.rows[kA2AvdRecvCounts][t] = recvcounts[t];
+    c->a2all.rows[kA2AvdRecvDispls][t] = rdispls[t];
+  }
+  hold_a2all(c, MCCS_FUNC_ALLTOALLV, send, recv, nullptr);
+  return mccsSuccess;
+}
+
+mccsResult_t plan_enqueue_a2av_dev(Comm* c, const void* send, void* recv, const uint64_t* table) {
+  if (c->plan_pending && c->plan_func != MCCS_FUNC_ALLTOALLV_DEV)
+    MCCS_FAIL(mccsInvalidUsage, "a group mixes collectives of different function / dtype / op on one communicator");
+  MCCS_CHECK(demote_a2all(c));
+  const bool ll = a2av_takes_ll(c);
+  ++c->plan_calls;
+  if (!ll) return a2av_dev_ring_enqueue(c, send, recv, table);
+  hold_a2all(c, MCCS_FUNC_ALLTOALLV_DEV, send, recv, table);
   return mccsSuccess;
 }
 
@@ -379,6 +471,8 @@ void plan_discard(Comm* c) {
   c->sr_ops.clear();
   c->plan_pending = false;
   c->plan_direct = false;
+  c->plan_a2all = false;
+  c->plan_calls = 0;
 }
 
 // A pending direct AllReduce goes back to the ring after all: the group holds
@@ -403,6 +497,20 @@ mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send
     // pre_launch_schedule batches same func/dtype/op only (plan.rs:122-141)
     MCCS_FAIL(mccsInvalidUsage, "a group mixes collectives of different function / dtype / op on one communicator");
   MCCS_CHECK(demote_direct(c));
+  MCCS_CHECK(demote_a2all(c));
+  // One uniform AllToAll of at most the opt-in limit per peer is held for the
+  // LL kernel (direct_a2a.h).  Every rank knows the count, so every rank
+  // decides alike; it needs no route (n = 6 and the forced relay included).
+  const bool first = c->plan_calls++ == 0;
+  if (first && func == MCCS_FUNC_ALLTOALL && c->a2a_ll_bytes > 0 && count <= c->a2a_ll_bytes &&
+      count <= a2a_ll_cap(c)) {
+    for (int t = 0; t < c->nranks; ++t) {
+      c->a2all.rows[kA2AvdSendCounts][t] = c->a2all.rows[kA2AvdRecvCounts][t] = count;
+      c->a2all.rows[kA2AvdSendDispls][t] = c->a2all.rows[kA2AvdRecvDispls][t] = (uint64_t)t * count;
+    }
+    hold_a2all(c, MCCS_FUNC_ALLTOALL, send, recv, nullptr);
+    return mccsSuccess;
+  }
   // One AllReduce that fits the direct region (every rank decides alike: same
   // call, same config) is held for the direct kernel; the launch may still
   // send it to the ring (plan_launch_group).
@@ -912,6 +1020,121 @@ static mccsResult_t build_direct(std::vector<Comm*>& comms, const std::vector<in
   return mccsSuccess;
 }
 
+// Workgroups of the LL all-to-all kernel the device holds at once: its launch
+// spins on peers' lines like a direct launch.  Probed only on this path.
+static int coresident_a2all_blocks(int device, int* ncu_out) {
+  static std::mutex mu;
+  static std::map<std::pair<unsigned, int>, std::pair<int, int>> cache;  // (runtime, device) -> (blocks, CUs)
+  const auto key = std::make_pair(rt_generation(), device);
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cache.find(key);
+    if (it != cache.end()) {
+      *ncu_out = it->second.second;
+      return it->second.first;
+    }
+  }
+  DeviceGuard g(device);
+  int ncu = 0, per_cu = 0;
+  if (rt().CuCount(&ncu, device) != hipSuccess) return 0;
+  if (rt().BlocksPerCu(&per_cu, a2a_ll_kernel_ptr(), MCCS_DIRECT_THREADS) != hipSuccess) return 0;  // not cached
+  std::lock_guard<std::mutex> lk(mu);
+  cache[key] = {per_cu * ncu, ncu};
+  *ncu_out = ncu;
+  return per_cu * ncu;
+}
+
+// The co-residency probe runs when a comm opts in, not at its first LL launch:
+// that launch may be one a stream is capturing.
+void a2a_ll_prepare(const Comm* c) {
+  int ncu = 0;
+  if (c->a2a_ll_bytes > 0 || c->a2av_ll_bytes > 0) (void)coresident_a2all_blocks(c->device, &ncu);
+}
+
+// Every comm of the device group holds one LL all-to-all of the same function
+// and mode over the same regions (one region table for every slot); the
+// counts may differ from slot to slot.
+static bool a2all_group(std::vector<Comm*>& comms, const std::vector<int>& idx) {
+  const Comm* c0 = comms[idx[0]];
+  for (size_t k = 0; k < idx.size(); ++k) {
+    const Comm* ck = comms[idx[k]];
+    if (!ck->plan_a2all || ck->plan_func != c0->plan_func || ck->nranks != c0->nranks ||
+        ck->layout.direct_slot != c0->layout.direct_slot || ck->layout.oneshot_slot != c0->layout.oneshot_slot ||
+        ck->layout.ll_slot != c0->layout.ll_slot || ck->peer_arena != c0->peer_arena || a2a_ll_cap(ck) == 0)
+      return false;
+  }
+  return idx.size() <= MCCS_DIRECT_MAX_RANKS;
+}
+
+// The LL all-to-all launch's arguments: every rank slot's buffers and its four
+// rows (or its table), and G from the slot with the most words on its larger
+// side, one word per thread, capped as build_direct caps the LL launch.
+static mccsResult_t build_a2all(std::vector<Comm*>& comms, const std::vector<int>& idx, mccsA2aLLArgs* la,
+                                unsigned* grid_x) {
+  const Comm* c0 = comms[idx[0]];
+  std::memset(la, 0, sizeof(*la));
+  const int n = c0->nranks;
+  la->nranks = (uint32_t)n;
+  la->slot_bytes = c0->layout.direct_slot;
+  la->oslot_bytes = c0->layout.oneshot_slot;
+  la->ll_slot_bytes = c0->layout.ll_slot;
+  la->fence_mode = c0->kcfg.fence_mode;
+  la->timeout_ticks = c0->kcfg.timeout_ticks;
+  la->table_mode = c0->plan_func == MCCS_FUNC_ALLTOALLV_DEV;
+  const uint64_t cap = MCCS_A2A_LL_CAP(la->ll_slot_bytes);
+  auto words = [&](uint64_t bytes) { return (std::min(bytes, cap) + 7) / 8; };
+  uint64_t most = 1;
+  for (size_t k = 0; k < idx.size(); ++k) {
+    const Comm* ck = comms[idx[k]];
+    mccsA2aLLRank& r = la->r[k];
+    r.send = ck->a2all.send;
+    r.recv = ck->a2all.recv;
+    r.table = la->table_mode ? ck->a2all.table : nullptr;
+    for (int t = 0; t < n; ++t) {
+      if (!ck->peer_arena[t]) return mccsInternalError;
+      if (k == 0) la->region[t] = ck->peer_arena[t] + ck->layout.direct_off();
+      else if (la->region[t] != ck->peer_arena[t] + ck->layout.direct_off()) return mccsInternalError;  // a2all_group
+    }
+    r.comm = (mccsDevComm*)ck->d_comm;
+    r.abort_flag = ck->d_abort;
+    r.rank = (uint32_t)ck->rank;
+    r.err_line = 1;
+    uint64_t sent = 0, recvd = 0;
+    if (la->table_mode) {
+      // the host knows no count: every block as large as the caller's promise allows
+      sent = recvd = (uint64_t)n * words(ck->a2av_ll_bytes);
+    } else {
+      for (int t = 0; t < n; ++t) {
+        for (int row = 0; row < MCCS_A2A_LL_ROWS; ++row) r.rows[row][t] = ck->a2all.rows[row][t];
+        sent += words(r.rows[kA2AvdSendCounts][t]);  // the own block is copied in the send phase
+        if (t != ck->rank) recvd += words(r.rows[kA2AvdRecvCounts][t]);
+      }
+    }
+    most = std::max(most, std::max(sent, recvd));
+    if (ck->kcfg.fence_mode == MCCS_FENCE_UNCACHED_RELEASE) la->fence_mode = MCCS_FENCE_UNCACHED_RELEASE;
+    la->timeout_ticks = (la->timeout_ticks == 0 || ck->kcfg.timeout_ticks == 0)
+                            ? 0
+                            : std::max(la->timeout_ticks, ck->kcfg.timeout_ticks);
+  }
+  int ncu = 0;
+  const int rescap = coresident_a2all_blocks(c0->device, &ncu);
+  if (ncu <= 0) ncu = rescap;
+  long g = std::min<long>((long)((most + MCCS_DIRECT_THREADS - 1) / MCCS_DIRECT_THREADS), c0->direct_blocks);
+  if (idx.size() > 1) g = std::min<long>(g, std::min(rescap, ncu) / (long)idx.size());  // one fused launch
+  else if (c0->share > 1) g = std::min<long>(g, std::min(rescap / 2, ncu) / c0->share);  // separate processes
+  g = std::max<long>(g, 1);
+  if (g * (long)idx.size() > rescap)
+    MCCS_FAIL(mccsInvalidUsage, "LL all-to-all launch of %zu ranks x %ld workgroups exceeds the %d co-resident ones of "
+              "device %d", idx.size(), g, rescap, c0->device);
+  *grid_x = (unsigned)g;
+  for (size_t k = 0; k < idx.size(); ++k) {
+    Comm* ck = comms[idx[k]];
+    ck->plan_a2all = false;
+    ck->plan_pending = false;
+  }
+  return mccsSuccess;
+}
+
 // Launch every pending plan.  By default a comm launches on the caller's
 // stream (stream order equals libmccs's bridge).  With bridge_streams = 1 it
 // launches on its own stream, bridged to the caller's with events like
@@ -941,10 +1164,21 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
     if (idx.size() > MCCS_MULTI_MAX_RANKS)
       MCCS_FAIL(mccsInvalidUsage, "%zu ranks share one device (at most %d)", idx.size(), (int)MCCS_MULTI_MAX_RANKS);
     DeviceGuard g(dev);
-    const bool direct = direct_group(comms, idx);
+    const bool a2all = a2all_group(comms, idx);
+    if (!a2all) {
+      bool dropped = false;
+      for (int i : idx) {
+        MCCS_CHECK(demote_a2all(comms[i]));
+        dropped = dropped || !comms[i]->plan_pending;  // a v call that moves nothing: the ring launches nothing
+      }
+      if (dropped) idx.erase(std::remove_if(idx.begin(), idx.end(), [&](int i) { return !comms[i]->plan_pending; }),
+                             idx.end());
+      if (idx.empty()) continue;
+    }
+    const bool direct = !a2all && direct_group(comms, idx);
     if (!direct)
       for (int i : idx) MCCS_CHECK(demote_direct(comms[i]));
-    if (!direct && idx.size() > 1) {  // checked before any work is uploaded, so the comms stay usable
+    if (!direct && !a2all && idx.size() > 1) {  // checked before any work is uploaded, so the comms stay usable
       const Comm* c0 = comms[idx[0]];
       const int cap = coresident_ring_blocks(c0->block_threads, dev);
       const long need = (long)c0->nch * c0->lanes * (long)idx.size();
@@ -963,11 +1197,19 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
     LaunchDesc lds[MCCS_MULTI_MAX_RANKS];
     mccsMultiLaunchArgs ma;
     mccsDirectArgs da;
+    mccsA2aLLArgs la;
     const void* fn = nullptr;
     void* args[1] = {nullptr};
     unsigned grid = 0, block = 0;
     Comm* c0 = comms[idx[0]];
-    if (direct) {
+    if (a2all) {
+      MCCS_CHECK(build_a2all(comms, idx, &la, &grid));
+      fn = a2a_ll_kernel_ptr();
+      block = MCCS_DIRECT_THREADS;
+      la.guard_order = guard_order(comms, idx);
+      for (int i : idx) la.no_guard |= comms[i]->kcfg.no_guard;
+      args[0] = &la;
+    } else if (direct) {
       MCCS_CHECK(build_direct(comms, idx, &da, &grid));
       fn = c0->plan_func == mccsFuncAllGather ? direct_kernel_ptr(mccsInt8, mccsDevSum)
                                               : direct_kernel_ptr(c0->plan_dtype, c0->plan_op);
@@ -1087,7 +1329,8 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
         // fused rank slots without their own record wait on the launching comm's event
         comms[idx[k]]->sync_owner = (k > 0 && !record && stop_on_launch) ? c0 : nullptr;
       }
-      comms[idx[k]]->last_algo = !direct                            ? MCCS_ALGO_RING
+      comms[idx[k]]->last_algo = a2all                              ? MCCS_ALGO_LL
+                                 : !direct                          ? MCCS_ALGO_RING
                                  : da.mode == MCCS_DIRECT_TWO_SHOT ? MCCS_ALGO_DIRECT
                                  : da.mode == MCCS_DIRECT_LL_ONE_SHOT || da.mode == MCCS_DIRECT_LL_AG ? MCCS_ALGO_LL
                                                                    : MCCS_ALGO_ONESHOT;

@@ -400,8 +400,35 @@ class FakeRuntime final : public DeviceRuntime {
     bool direct = false;
     for (int dt = 0; dt < mccsNumTypes && fn; ++dt)
       for (int op = 0; op < 4; ++op) direct = direct || fn == direct_kernel_ptr(dt, op);
+    const bool a2all = fn && fn == a2a_ll_kernel_ptr();
     if (fn && args && grid.y >= 1 && grid.y <= MCCS_MULTI_MAX_RANKS) {
-      if (direct) {  // mccsDirectArgs: the walk it reproduces
+      if (a2all) {
+        // mccsA2aLLArgs: per rank slot the rank and its four rows (sendcounts | sdispls | recvcounts |
+        // rdispls, ',' between peers), or the size table's address; '/' between rank slots
+        const mccsA2aLLArgs* la = (const mccsA2aLLArgs*)args[0];
+        for (unsigned k = 0; k < grid.y && k < MCCS_DIRECT_MAX_RANKS; ++k) on_dev = on_dev && dev_of(la->r[k].comm) == cur_;
+        extra = " mode=ll-a2a n=" + std::to_string(la->nranks) + " gx=" + std::to_string(grid.x) +
+                " llslot=" + std::to_string(la->ll_slot_bytes) + " fence=" + std::to_string(la->fence_mode) +
+                " table=" + std::to_string(la->table_mode) + " guard_order=" + std::to_string(la->guard_order) +
+                " no_guard=" + std::to_string(la->no_guard) + " slots=";
+        for (unsigned k = 0; k < grid.y && k < MCCS_DIRECT_MAX_RANKS; ++k) {
+          const mccsA2aLLRank& r = la->r[k];
+          char hex[64];
+          std::snprintf(hex, sizeof(hex), "%llx:%llx", (unsigned long long)(uintptr_t)r.send,
+                        (unsigned long long)(uintptr_t)r.recv);
+          extra += (k ? "/" : "") + std::to_string(r.rank) + ":" + hex + ":";
+          if (la->table_mode) {
+            std::snprintf(hex, sizeof(hex), "table=%llx", (unsigned long long)(uintptr_t)r.table);
+            extra += hex;
+            continue;
+          }
+          for (int row = 0; row < MCCS_A2A_LL_ROWS; ++row) {
+            if (row) extra += "|";
+            for (unsigned t = 0; t < la->nranks && t < MCCS_DIRECT_MAX_RANKS; ++t)
+              extra += (t ? "," : "") + std::to_string(r.rows[row][t]);
+          }
+        }
+      } else if (direct) {  // mccsDirectArgs: the walk it reproduces
         const mccsDirectArgs* da = (const mccsDirectArgs*)args[0];
         for (unsigned k = 0; k < grid.y; ++k) on_dev = on_dev && dev_of(da->r[k].comm) == cur_;
         extra = " count=" + std::to_string(da->count) + " nch=" + std::to_string(da->nch) +
@@ -437,7 +464,7 @@ class FakeRuntime final : public DeviceRuntime {
     note("launch dev=" + std::to_string(cur_) + " grid=" + std::to_string(grid.x) + "x" + std::to_string(grid.y) +
          " block=" + std::to_string(block.x) + " stream=" + sid(s) + " comms_on_dev=" + (on_dev ? "1" : "0") +
          " inline_works=" + std::to_string(inl) + " stop_event=" + std::to_string((uintptr_t)stop_) +
-         " kind=" + (direct ? "direct" : "ring") + extra);
+         " kind=" + (direct || a2all ? "direct" : "ring") + extra);
     return hipSuccess;
   }
   // redOpArg of every work element a ring launch carries, as the kernels would
@@ -522,6 +549,7 @@ class FakeRuntime final : public DeviceRuntime {
     for (int dt = 0; dt < mccsNumTypes; ++dt)
       for (int op = 0; op < 4; ++op)
         if (fn == direct_kernel_ptr(dt, op)) return;
+    if (fn == a2a_ll_kernel_ptr()) return;
     const mccsMultiLaunchArgs* ma = (const mccsMultiLaunchArgs*)args[0];
     if (ma->inline_works) return;
     const int nch = __builtin_popcountll(ma->channelMask);

@@ -310,3 +310,48 @@ struct mccsDirectArgs {
 #ifdef __cplusplus
 static_assert(sizeof(mccsDirectArgs) <= 4096, "direct launch arguments must stay within 4 KiB");
 #endif
+
+// ---- LL AllToAll / AllToAllv / AllToAllvDev (direct_a2a.h) -------------------
+// The three all-to-all calls at small sizes, through the LL slots above and
+// under the same launch count and parity as the LL AllReduce / AllGather.
+// Nothing fans out: sender s writes the block for receiver t only into t's
+// region, at llbase(parity) + s x ll_slot_bytes:
+//   line 0      header {count lo32, flag, count hi32, flag}: the bytes s sends
+//               t in this launch
+//   line 1 + w  data word w of the block
+// so a block of c bytes takes 16 x (1 + ceil(c / 8)) bytes and a pair moves at
+// most MCCS_A2A_LL_CAP(ll_slot_bytes) bytes per launch.  The header goes out
+// for EVERY ordered pair in EVERY launch, zero counts included, and every
+// receiver waits for every peer's: the parity-reuse argument above needs every
+// pair to hand off in every launch (without it a pair with a zero count would
+// let the sender run two launches ahead and overwrite lines a slow receiver
+// still polls for the older flag).  A receiver takes its length from its own
+// count; the header's value is there for a later size check.
+#define MCCS_A2A_LL_CAP(ll_slot_bytes) ((ll_slot_bytes) >= 32 ? (ll_slot_bytes) / 2 - 8 : 0)
+#define MCCS_A2A_LL_ROWS 4  // ring_walk.h kA2AvdRows: sendcounts, sdispls, recvcounts, rdispls
+struct mccsA2aLLRank {      // one rank slot of an LL all-to-all launch (blockIdx.y)
+  const void* send;
+  void* recv;
+  struct mccsDevComm* comm;
+  uint32_t* abort_flag;
+  uint32_t rank;
+  uint32_t err_line;
+  const uint64_t* table;  // table mode: the AllToAllvDev size table, re-read at every launch
+  uint64_t rows[MCCS_A2A_LL_ROWS][MCCS_DIRECT_MAX_RANKS];  // host mode: the call's four rows, in bytes
+};
+struct mccsA2aLLArgs {
+  // fused rank slots are ranks of one communicator (n <= 8) in one process
+  struct mccsA2aLLRank r[MCCS_DIRECT_MAX_RANKS];
+  char* region[MCCS_DIRECT_MAX_RANKS];  // as mccsDirectArgs.region
+  uint64_t slot_bytes, oslot_bytes;     // the two-shot / one-shot slots the LL slots lie behind
+  uint64_t ll_slot_bytes;
+  uint64_t timeout_ticks;
+  uint64_t guard_order;
+  uint32_t nranks;
+  uint32_t fence_mode;
+  uint32_t table_mode;  // 1: sizes from r[k].table (clamped to the capacity on both sides), 0: r[k].rows
+  uint32_t no_guard;
+};
+#ifdef __cplusplus
+static_assert(sizeof(mccsA2aLLArgs) <= 4096, "LL all-to-all launch arguments must stay within 4 KiB");
+#endif

@@ -12,6 +12,7 @@ here only its extra FIFO copies.
   python tools/a2a_bench.py --v [--out FILE.jsonl]
   python tools/a2a_bench.py --v --dev [--out FILE.jsonl]
   python tools/a2a_bench.py --p2p [--out FILE.jsonl]
+  python tools/a2a_bench.py --ll [--n 4 6 8] [--sizes-kib 1 8 64] [--out FILE.jsonl]
 
 --v: AllToAllv beside AllToAll.  Per size one process alternates a
 uniform-count AllToAllv with an AllToAll of the same bytes, five repeats of
@@ -35,6 +36,15 @@ call.  The yardstick is mccsAllToAllv with the same sparse matrix (what a
 caller had to use before).  Per message size one process alternates the two,
 five repeats of each, and reports both ranges, the ratio of the medians and the
 yardstick's own spread (max / min), the margin the ratio is read against.
+
+--ll: the LL all-to-all (mccsCommSetAllToAllLL) beside the ring.  Per size one
+process alternates the ring AllToAll (the yardstick) and the LL AllToAll on the
+same communicators, eagerly and as replayed one-launch graphs, and then a
+skewed AllToAllvDev (a circulant of weights 1 3 0 1 0 2 0 1 ... times a third
+of the size, zeros included) as a replayed graph, ring beside LL (6 ranks have
+no one-hop route: LL only); five repeats of each.  It reports every range, the
+ratios of the medians and the ring AllToAll's own spread (max / min), the
+margin the ratios are read against.
 
 Every (n, size, mode) step runs in a fresh child process under its own time
 limit; the first step that fails or runs out of time ends the run.
@@ -285,6 +295,110 @@ def step_p2p(n, kib, iters, repeats=5):
     print(json.dumps(out), flush=True)
 
 
+def step_ll(n, kib, iters, repeats=5):
+    """One --ll step: ring and LL AllToAll, eager and replayed, and the skewed Dev replay, alternating."""
+    import statistics
+
+    import torch
+
+    from mccs_amd import comm as C
+
+    comms = C.init_all([0] * n, C.CommConfig(direct_bytes=-1, oneshot_bytes=-1))  # ll_bytes: the default
+    B = kib << 10
+    cap = comms[0].all_to_all_ll_max()
+    assert B <= cap, (B, cap)
+    one_hop = comms[0].all_to_all_route()["hops"] == 1
+    xs = [torch.randint(0, 255, (n * B,), dtype=torch.uint8, device="cuda") for _ in range(n)]
+    ys = [torch.empty(n * B, dtype=torch.uint8, device="cuda") for _ in range(n)]
+    xp, yp = [x.data_ptr() for x in xs], [y.data_ptr() for y in ys]
+    weights = ([1, 3, 0, 1, 0, 2, 0, 1] * n)[:n]
+    skew = [[B // 3 * weights[(t - s) % n] for t in range(n)] for s in range(n)]
+    packed = lambda c: [sum(c[:i]) for i in range(n)]
+    tabs = []
+    for r in range(n):
+        col = [skew[s][r] for s in range(n)]
+        tabs.append(torch.tensor(skew[r] + packed(skew[r]) + col + packed(col), dtype=torch.int64, device="cuda"))
+    tptr = [t.data_ptr() for t in tabs]
+    torch.cuda.synchronize()
+
+    def limits(uniform, v):
+        for c in comms:
+            c.set_all_to_all_ll(bytes_per_peer=uniform, v_bytes_per_peer=v)
+
+    def grouped(call):
+        with C.group():
+            for r in range(n):
+                call(r)
+
+    # (the current stream is looked up per call: inside a capture it is the capturing one)
+    a2a = lambda r: C.all_to_all(comms[r], xp[r], yp[r], B)
+    dev = lambda r: C.all_to_all_v_dev(comms[r], xp[r], yp[r], tptr[r])
+
+    def capture(call, uniform, v, algo):
+        limits(uniform, v)
+        grouped(call)  # once eagerly
+        assert comms[0].last_algo() == algo, (comms[0].last_algo(), algo)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            grouped(call)
+        return g
+
+    def eager(uniform, algo):
+        def run_one():
+            grouped(a2a)
+        return (uniform, algo, run_one)
+
+    graphs = {"alltoall_ring_graph": capture(a2a, 0, 0, "ring"), "alltoall_ll_graph": capture(a2a, cap, 0, "ll"),
+              "a2avd_skewed_ll_graph": capture(dev, 0, cap, "ll")}
+    if one_hop:
+        graphs["a2avd_skewed_ring_graph"] = capture(dev, 0, 0, "ring")
+    want = [y.clone() for y in ys]  # the skewed ring (or LL) result, to hold the LL replay to
+    calls = {"alltoall_ring": eager(0, "ring"), "alltoall_ll": eager(cap, "ll")}
+    calls.update({k: (None, None, g.replay) for k, g in graphs.items()})
+
+    def run(name, k):
+        uniform, algo, call = calls[name]
+        if uniform is not None:
+            limits(uniform, 0)
+        for _ in range(k):
+            call()
+        if algo is not None:
+            assert comms[0].last_algo() == algo, (name, comms[0].last_algo())
+        for c in comms:
+            c.sync()
+        torch.cuda.synchronize()
+
+    for name in calls:
+        run(name, 2)
+    run("a2avd_skewed_ll_graph", 1)
+    for r in range(n):
+        assert torch.equal(ys[r], want[r]), r
+    times = {k: [] for k in calls}
+    for _ in range(repeats):
+        for name in calls:  # alternating, in one process
+            t0 = time.perf_counter()
+            run(name, iters)
+            times[name].append(round((time.perf_counter() - t0) / iters * 1e6, 1))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    out = {"bench": "a2a_ll", "n": n, "KiB_per_peer": kib, "ll_cap": cap, "lanes": comms[0].lanes,
+           "channels": comms[0].nchannels, "iters": iters, "repeats": repeats, **comms[0].all_to_all_route()}
+    for k, v in times.items():
+        out[k + "_us"] = [min(v), med[k], max(v)]  # min, median, max of the repeats
+    out["ll_over_ring"] = round(med["alltoall_ll"] / med["alltoall_ring"], 3)
+    out["ll_graph_over_ring_graph"] = round(med["alltoall_ll_graph"] / med["alltoall_ring_graph"], 3)
+    if one_hop:
+        out["dev_ll_graph_over_ring_graph"] = round(med["a2avd_skewed_ll_graph"] / med["a2avd_skewed_ring_graph"], 3)
+    out["ring_spread"] = round(max(times["alltoall_ring"]) / min(times["alltoall_ring"]), 3)
+    out["ring_graph_spread"] = round(max(times["alltoall_ring_graph"]) / min(times["alltoall_ring_graph"]), 3)
+    graphs.clear()
+    calls.clear()
+    torch.cuda.synchronize()
+    for c in comms:
+        c.destroy()
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[8])
@@ -295,26 +409,32 @@ def main():
     ap.add_argument("--v", action="store_true", help="AllToAllv beside AllToAll (one hop only)")
     ap.add_argument("--dev", action="store_true", help="with --v: AllToAllvDev beside the host-count AllToAllv")
     ap.add_argument("--p2p", action="store_true", help="a Send/Recv ring shift beside the sparse AllToAllv")
+    ap.add_argument("--ll", action="store_true", help="the LL all-to-all beside the ring (n 4 6 8, 1 8 64 KiB)")
     ap.add_argument("--step", type=int, nargs=2, default=None, help=argparse.SUPPRESS)  # child: n KiB
     args = ap.parse_args()
     if args.dev and not args.v:
         ap.error("--dev goes with --v")
-    if args.p2p and args.v:
-        ap.error("--p2p is a mode of its own")
+    if (args.p2p or args.ll) and args.v or args.p2p and args.ll:
+        ap.error("--p2p and --ll are modes of their own")
+    if args.ll and not args.step:
+        if args.n == [8]:
+            args.n = [4, 6, 8]
+        if args.sizes_kib == [64, 1024]:
+            args.sizes_kib = [1, 8, 64]
     if args.step:
-        (step_p2p if args.p2p else step_dev if args.v and args.dev else step_v if args.v else step)(
+        (step_ll if args.ll else step_p2p if args.p2p else step_dev if args.v and args.dev else step_v if args.v else step)(
             args.step[0], args.step[1], args.iters)
         return 0
     for n in args.n:
         for kib in args.sizes_kib:
-            for relay in ((False,) if args.v or args.p2p else (False, True)):
+            for relay in ((False,) if args.v or args.p2p or args.ll else (False, True)):
                 env = dict(os.environ)
                 env.pop("MCCS_ALLTOALL_HOPS", None)
                 if relay:
                     env["MCCS_ALLTOALL_HOPS"] = "relay"
                 cmd = ["timeout", "-k", "10", str(args.step_timeout), sys.executable, os.path.abspath(__file__),
                        "--step", str(n), str(kib), "--iters", str(args.iters)] + (["--v"] if args.v else []) + \
-                      (["--dev"] if args.v and args.dev else []) + (["--p2p"] if args.p2p else [])
+                      (["--dev"] if args.v and args.dev else []) + (["--p2p"] if args.p2p else []) + (["--ll"] if args.ll else [])
                 r = subprocess.run(cmd, capture_output=True, text=True, env=env)
                 lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
                 if r.returncode != 0 or not lines:

@@ -55,7 +55,7 @@ def main():
     if args[:1] == ["--diff"]:
         diff = json.load(open(args[1]))
         args = args[2:]
-    srcs = sorted(glob.glob(os.path.join(CSRC, "ring*.hip"))) + [os.path.join(CSRC, "direct.hip")]
+    srcs = sorted(glob.glob(os.path.join(CSRC, "ring*.hip"))) + sorted(glob.glob(os.path.join(CSRC, "direct*.hip")))
     with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(8) as ex:
         res = {}
         for r in ex.map(lambda s: compile_tu(s, args, tmp), srcs):
