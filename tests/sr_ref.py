@@ -1,8 +1,10 @@
-"""Expected bytes and models for the Send/Recv tests (numpy only, no library code).
+"""Expected bytes and models for the Send/Recv tests (numpy only, no library
+code; random_group() alone takes its engine draws, and with them the library's
+default rings, from tests/test_gpu_all_to_all_v_fuzz.py).
 
-A case is a list of Op(rank, kind, peer, nbytes, off): each rank's ops, in list
-order, are the calls of one group; off is how many bytes the op's buffer starts
-past 16-byte alignment.
+A case is a list of Op(rank, kind, peer, nbytes, off, code): each rank's ops, in
+list order, are the calls of one group; off is how many bytes the op's buffer
+starts past 16-byte alignment.
 
 matches():   per ordered pair (s, t) the k-th send of s to t meets the k-th
              receive of t from s (NCCL's rule).
@@ -18,6 +20,13 @@ elements():  the per-channel work elements of one rank, written from the
 patterns():  the named pattern lists (a)-(h) at n ranks.  Sizes come from
              a2av_ref.values(m): {0, 1, 15, 4099, C, C + 1, 2C + 999, 3C} at
              buffer_size = a2av_ref.BUFF, C one loop of a pair.
+random_group(): a seeded group under a seeded engine configuration: up to
+             three messages on every ordered pair, sometimes a pair with more
+             than one or two works of them, a rank's calls shuffled across its
+             peers, typed counts.  chained(): the two hand-built groups with
+             more than MAX_WORK_ELEMENTS elements on a channel.  An op's
+             `code` is the element type its call names (the bytes are what
+             counts: count = nbytes / ESIZE[code]).
 """
 from __future__ import annotations
 
@@ -32,15 +41,19 @@ SENTINEL = V.SENTINEL
 BUFF = V.BUFF
 NWARPS = (512 + 32) // 32  # the schema's largest thread count, in reference warps of 32
 
-Op = namedtuple("Op", "rank kind peer nbytes off", defaults=(0,))
+ESIZE = (1, 1, 4, 4, 8, 8, 2, 4, 8, 2)  # bytes per element of the ten type codes (int8, uint8, ... bfloat16)
+U8 = 1
+MAX_WORK_ELEMENTS = 10  # elements of one work (MCCS_MAX_WORK_ELEMENTS); a channel's further ones chain a work
+
+Op = namedtuple("Op", "rank kind peer nbytes off code", defaults=(0, U8))
 
 
-def S(rank, peer, nbytes, off=0):
-    return Op(rank, "send", peer, nbytes, off)
+def S(rank, peer, nbytes, off=0, code=U8):
+    return Op(rank, "send", peer, nbytes, off, code)
 
 
-def R(rank, peer, nbytes, off=0):
-    return Op(rank, "recv", peer, nbytes, off)
+def R(rank, peer, nbytes, off=0, code=U8):
+    return Op(rank, "recv", peer, nbytes, off, code)
 
 
 # ---- matching and expected bytes -------------------------------------------
@@ -209,3 +222,130 @@ def patterns(n: int, m: int, rings) -> dict:
 def shift_matrix(n: int, nbytes: int) -> list[list[int]]:
     """The AllToAllv count matrix of a ring shift: s sends nbytes to s + 1."""
     return [[nbytes if t == (s + 1) % n else 0 for t in range(n)] for s in range(n)]
+
+
+# ---- queues and works ---------------------------------------------------------------
+def queues(ops) -> dict:
+    """(rank, kind, peer) -> that queue's op indices in issue order."""
+    out = {}
+    for i, o in enumerate(ops):
+        out.setdefault((o.rank, o.kind, o.peer), []).append(i)
+    return out
+
+
+def works(ops, r: int, rings) -> list[int]:
+    """Works per channel of rank r: MAX_WORK_ELEMENTS elements each, the last one the rest."""
+    return [-(-len(es) // MAX_WORK_ELEMENTS) for es in elements(ops, r, rings)]
+
+
+# ---- seeded groups ------------------------------------------------------------------
+MAX_OPS = 249  # payload()'s limit
+MAX_SENT = 8 << 20  # bytes a group sends in all
+HEAVY = (11, 12, 21, 23)  # messages of a heavy pair: two works, and three works of ten
+PAIR_COUNTS, PAIR_P = (0, 1, 2, 3), (0.4, 0.3, 0.15, 0.15)
+
+
+def sizes(m: int) -> list[int]:
+    return sorted(set(V.values(m)) | set(V.boundary_values(m)))
+
+
+def interleave(rng, qs: list[list]) -> list:
+    """A uniformly random interleaving of the lists qs that keeps each list's order."""
+    left = [len(q) for q in qs]
+    out = []
+    while sum(left):
+        k = int(rng.choice(len(qs), p=np.array(left) / sum(left)))
+        out.append(qs[k][len(qs[k]) - left[k]])
+        left[k] -= 1
+    return out
+
+
+def random_group(seed: int) -> dict:
+    """n, cfg, slice2, fifo_works, relabelled, rings, m: the engine draws of
+    test_gpu_all_to_all_v_fuzz (which names the library's constants and default
+    rings).  ops: the group.  Every ordered pair of the ranks present draws 0-3
+    messages; with probability 0.4 one pair is heavy (HEAVY messages, each of at
+    most one loop); with probability 0.3 at n > 3 one rank is absent.  A size is
+    one of sizes(m), or 0 one time in ten; the first message of the first pair
+    has bytes.  The caps hold by construction: a pair gets no more messages
+    than MAX_OPS leaves, a message no more bytes than MAX_SENT leaves (the
+    largest size that fits).  Each rank's calls are a random interleaving of
+    its (peer, direction) queues."""
+    import test_gpu_all_to_all_v_fuzz as F
+
+    rng = np.random.default_rng(seed)
+    g = F.engine_case(rng)
+    n, m = g["n"], g["m"]
+    pool = sizes(m)
+    assert pool[0] == 0
+    absent = int(rng.integers(0, n)) if n > 3 and rng.random() < 0.3 else None
+    live = [r for r in range(n) if r != absent]
+    pairs = [(s, t) for s in live for t in live if s != t]
+    first = pairs[int(rng.integers(0, len(pairs)))]
+    heavy = pairs[int(rng.integers(0, len(pairs)))] if rng.random() < 0.4 else None
+    nheavy = int(rng.choice(HEAVY))
+    rest = [p for p in pairs if p not in (first, heavy)]
+    order = [first] + ([heavy] if heavy not in (None, first) else [])
+    order += [rest[int(k)] for k in rng.permutation(len(rest))]
+    msgs_left, bytes_left = MAX_OPS // 2, MAX_SENT
+    msgs = {}
+    for p in order:
+        k = nheavy if p == heavy else int(rng.choice(PAIR_COUNTS, p=PAIR_P))
+        k = min(max(k, 1 if p == first else 0), msgs_left)
+        msgs_left -= k
+        own = [v for v in pool if v <= V.loop_bytes(m)] if p == heavy else pool
+        msgs[p] = []
+        for j in range(k):
+            v = own[int(rng.integers(1, len(own)))]
+            if rng.random() < 0.1 and not (p == first and j == 0):
+                v = 0
+            v = max(x for x in own if x <= min(v, bytes_left))
+            bytes_left -= v
+            code = int(rng.integers(0, len(ESIZE)))
+            code = code if v % ESIZE[code] == 0 else U8
+            msgs[p].append((v, code, int(rng.integers(0, 16)), int(rng.integers(0, 16))))
+    ops = []
+    for r in live:
+        qs = [[S(r, t, v, so, code) for v, code, so, _ in msgs[(r, t)]] for t in live if t != r]
+        qs += [[R(r, s, v, ro, code) for v, code, _, ro in msgs[(s, r)]] for s in live if s != r]
+        ops += interleave(rng, qs)
+    assert len(ops) <= MAX_OPS and any(o.nbytes for o in ops)
+    assert sum(o.nbytes for o in ops if o.kind == "send") <= MAX_SENT
+    return dict(seed=seed, **g, ops=ops, absent=absent, heavy=heavy)
+
+
+# ---- the chained groups ---------------------------------------------------------------
+def chain_sizes(k: int, m: int) -> list[int]:
+    """k message sizes of one pair: a walk through the boundary values up to
+    one loop, 2C + 999 in the middle, and zero bytes at positions 0, 9, 10 and
+    last: the last element of a full work and the first of the chained one."""
+    C = V.loop_bytes(m)
+    walk = [v for v in V.boundary_values(m) if v <= C]
+    out = [walk[(3 * j) % len(walk)] for j in range(k)]
+    out[k // 2] = 2 * C + 999
+    for j in (0, MAX_WORK_ELEMENTS - 1, MAX_WORK_ELEMENTS, k - 1):
+        out[j] = 0
+    return out
+
+
+def chained(n: int, m: int) -> list:
+    """n = 2: 23 messages 0 -> 1 and 12 messages 1 -> 0; every channel joins
+    the pair, so each holds three works one way and two the other.  Rank 0
+    issues its sends and then its receives, rank 1 takes them in turns.
+    n = 4: 12 messages 0 -> 1, one of 3C 2 -> 3 and one 1 -> 2; rank 0 makes no
+    call to 2 or 3, rank 1 issues its 12 receives before its single send."""
+    C = V.loop_bytes(m)
+    if n == 2:
+        a, b = chain_sizes(23, m), chain_sizes(12, m)
+        ops = [S(0, 1, v, j % 16) for j, v in enumerate(a)] + [R(0, 1, v, (5 + j) % 16) for j, v in enumerate(b)]
+        for j, v in enumerate(a):
+            ops.append(R(1, 0, v, (3 * j) % 16))
+            if j < len(b):
+                ops.append(S(1, 0, b[j], (7 * j + 1) % 16))
+        return ops
+    assert n == 4
+    a = chain_sizes(12, m)
+    ops = [S(0, 1, v, j % 16) for j, v in enumerate(a)]
+    ops += [R(1, 0, v, (3 * j) % 16) for j, v in enumerate(a)] + [S(1, 2, C + 1, 9)]
+    ops += [R(2, 1, C + 1, 2), S(2, 3, 3 * C), R(3, 2, 3 * C, 13)]
+    return ops

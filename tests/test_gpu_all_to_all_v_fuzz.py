@@ -27,10 +27,10 @@ NS = (2, 3, 4, 5, 7, 8)
 ENV = ("MCCS_SLICE_STEPS", "MCCS_INLINE_WORKS", "MCCS_ALLTOALL_HOPS")
 
 
-def v_case(seed):
-    """A dict: n, cfg (CommConfig keywords), slice2, fifo_works, relabelled,
-    rings, m, cnt (the matrix), layout."""
-    rng = np.random.default_rng(seed)
+def engine_case(rng):
+    """The engine draws of one case from rng: n, cfg (CommConfig keywords),
+    slice2, fifo_works, relabelled, rings, m.  (tests/sr_ref.random_group
+    takes the same draws.)"""
     n = int(rng.choice(NS))
     cfg = {}
     if rng.random() < 0.5:
@@ -53,13 +53,20 @@ def v_case(seed):
         cfg["rings"] = rings
         cfg["channel_count"] = len(rings)
     m = a2a_ref.route(n, rings)["m"]
+    return dict(n=n, cfg=cfg, slice2=slice2, fifo_works=fifo_works, relabelled=relabelled, rings=rings, m=m)
+
+
+def v_case(seed):
+    """A dict: the keys of engine_case, then cnt (the matrix) and layout."""
+    rng = np.random.default_rng(seed)
+    e = engine_case(rng)
+    n, m = e["n"], e["m"]
     vals = V.values(m)
     cnt = [[int(vals[int(rng.integers(0, len(vals)))]) for _ in range(n)] for _ in range(n)]
     for r in range(n):
         cnt[r][r] = int(rng.choice([0, 1, 15, 4099, V.loop_bytes(m) + 1]))
     layout = V.LAYOUTS[int(rng.integers(0, len(V.LAYOUTS)))]
-    return dict(seed=seed, n=n, cfg=cfg, slice2=slice2, fifo_works=fifo_works, relabelled=relabelled, rings=rings, m=m,
-                cnt=cnt, layout=layout)
+    return dict(seed=seed, **e, cnt=cnt, layout=layout)
 
 
 def cases(count=NCASES):

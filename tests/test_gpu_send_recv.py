@@ -51,8 +51,9 @@ class SRStaged:
     def issue_rank(self, comm, r, stream=None):
         for i, o in enumerate(self.ops):
             if o.rank == r:
+                assert o.nbytes % SR.ESIZE[o.code] == 0  # the call counts elements of the op's type (uint8 by default)
                 (C.send if o.kind == "send" else C.recv)(comm, self.dev[i].data_ptr() + self.host[i][1].start,
-                                                         o.nbytes, U8, o.peer, stream=stream)
+                                                         o.nbytes // SR.ESIZE[o.code], o.code, o.peer, stream=stream)
 
     def issue(self, comms, stream=None):
         with C.group():
