@@ -244,8 +244,10 @@ mccsResult_t mccsAllGather(const void *sendbuff, void *recvbuff, size_t sendbyte
  * functions, dtypes or ops on one comm in a group is refused with
  * mccsInvalidUsage at mccsGroupEnd); ranks sharing a GPU run as one fused
  * launch; the call may be captured into a HIP graph; the watchdog and
- * mccsCommAbort end a stuck kernel.  Always the ring (mccsCommLastAlgo reports
- * MCCS_ALGO_RING), whatever the size: the direct / LL variants do not take it.
+ * mccsCommAbort end a stuck kernel.  The ring (mccsCommLastAlgo reports
+ * MCCS_ALGO_RING) at every size, unless the communicator opted in to the direct
+ * ReduceScatter (mccsCommSetReduceScatterDirect, below): a small block then
+ * takes one exchange instead of n-1 hops, with the ring's result bit for bit.
  * In place means recvbuff == sendbuff + rank * recvcount (in elements) and is
  * supported; no other overlap of the two buffers is.  Out of place, sendbuff
  * is never written.  Nothing outside [recvbuff, recvbuff + recvcount) is
@@ -459,6 +461,38 @@ mccsResult_t mccsAllToAllvDev(const void *sendbuff, void *recvbuff, const uint64
  * this path. */
 mccsResult_t mccsCommSetAllToAllLL(mccsComm_t comm, size_t bytes_per_peer, size_t v_bytes_per_peer);
 mccsResult_t mccsCommAllToAllLLMax(mccsComm_t comm, size_t *cap);
+/* The direct ReduceScatter: every rank writes each foreign block of its input
+ * once, straight into the owner's slot of the direct region, and every owner
+ * reduces its own block -- one exchange instead of the ring's n-1 hops, the
+ * same link bytes.  The result is the ring's, bit for bit:
+ * the same channels, chunks and summation order.  Opt-in per communicator;
+ * both limits are bytes PER BLOCK (recvcount x element size), default to 0 =
+ * off, and with both off every call plans exactly as without this entry
+ * point.  MCCS_RS_DIRECT_BYTES / MCCS_RS_LL_BYTES in the environment set them
+ * when the communicator is created (clamped to the maxima below).
+ * mccsCommReduceScatterDirectMax: *cap, the largest block of the count-based
+ * variant (one one-shot slot: oneshot_bytes rounded up to 64 KiB; 0 without
+ * one-shot slots -- oneshot_bytes < 0, nranks outside 2..8 -- or without peer
+ * atomics); *ll_cap, the largest block of the LL variant (ll_slot / 2 =
+ * ll_bytes rounded up to 8; 0 where the lines cannot be used: no LL slots, a
+ * cached FIFO arena, system-scope fences).
+ * mccsCommSetReduceScatterDirect: a value above its maximum is refused with
+ * mccsInvalidArgument; a call while the communicator has a group open or a
+ * call pending, with mccsInvalidUsage.  EVERY RANK MUST SET THE SAME TWO
+ * VALUES: ranks that disagree pick different kernels for one call and stall
+ * until the watchdog; like disagreeing roots this is not detected.
+ * A mccsReduceScatter of Sum / Prod / Max / Min whose block is within
+ * ll_block_bytes takes the LL variant (mccsCommLastAlgo reports MCCS_ALGO_LL),
+ * else one within block_bytes the count-based variant (MCCS_ALGO_ONESHOT),
+ * when it is its communicator's only call of the launch; a larger one, one
+ * sharing a group with a second call of the communicator, and every
+ * PreMulSum / SumPostDiv (mccsReduceScatterOpArg, the average) take the ring
+ * as before.  In place (recvbuff == sendbuff + rank * recvcount) is
+ * supported.  Ranks sharing a GPU are fused into one launch as always; the
+ * call may be captured into a HIP graph.  The node gate does not cover this
+ * path. */
+mccsResult_t mccsCommSetReduceScatterDirect(mccsComm_t comm, size_t block_bytes, size_t ll_block_bytes);
+mccsResult_t mccsCommReduceScatterDirectMax(mccsComm_t comm, size_t *cap, size_t *ll_cap);
 /* Send / Recv: grouped point-to-point (torch's batch_isend_irecv; the pieces of
  * a Gather or Scatter).  mccsSend moves count * elem_bytes(dtype) bytes from
  * sendbuff to rank `peer`, mccsRecv receives as many from rank `peer` into

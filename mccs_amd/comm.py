@@ -258,6 +258,28 @@ class Communicator:
         _lib.check(_sig().mccsCommAllToAllLLMax(self._h, ctypes.byref(cap)), "mccsCommAllToAllLLMax")
         return int(cap.value)
 
+    def set_reduce_scatter_direct(self, block_bytes: int = 0, ll_block_bytes: int = 0) -> None:
+        """mccsCommSetReduceScatterDirect: opts the communicator in to the direct
+        ReduceScatter (0 = off, the default).  Both limits are bytes per block
+        (recv_count x element size).  A reduce_scatter of Sum / Prod / Max / Min
+        that is the communicator's only call of its launch takes the LL kernel
+        when its block is within ll_block_bytes (last_algo() == "ll"), else the
+        count-based one within block_bytes ("oneshot"); the result is the
+        ring's bit for bit.  Every rank must set the same two values, each at
+        most its reduce_scatter_direct_max()."""
+        rc = _sig().mccsCommSetReduceScatterDirect(self._h, int(block_bytes), int(ll_block_bytes))
+        _lib.check(rc, "mccsCommSetReduceScatterDirect")
+
+    def reduce_scatter_direct_max(self) -> tuple[int, int]:
+        """mccsCommReduceScatterDirectMax: (cap, ll_cap), the largest block in
+        bytes of the count-based and of the LL variant; 0 where one cannot be
+        used (no slots or no peer atomics; no LL slots, a cached arena,
+        system-scope fences)."""
+        cap, ll_cap = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        _lib.check(_sig().mccsCommReduceScatterDirectMax(self._h, ctypes.byref(cap), ctypes.byref(ll_cap)),
+                   "mccsCommReduceScatterDirectMax")
+        return int(cap.value), int(ll_cap.value)
+
     def all_to_all_route(self) -> dict:
         """The comm's AllToAll route (mccsCommAllToAllRoute): hops (1: every
         block goes straight to its ring successor; nranks - 1: relayed along the
@@ -377,8 +399,10 @@ def reduce_scatter(comm: Communicator, send_buf, recv_buf, recv_count: int, data
                    op_type=AllReduceOpType.Sum, stream=None, op_arg: int | None = None) -> None:
     """mccsReduceScatter: send holds nranks * recv_count elements (block D at
     element D * recv_count); recv gets recv_count elements, the reduction of
-    this rank's block over all ranks.  Always the ring; stream-ordered.
-    op_arg as for all_reduce (mccsReduceScatterOpArg)."""
+    this rank's block over all ranks.  The ring, unless the communicator opted
+    in with set_reduce_scatter_direct and the block is within a limit (then
+    one direct exchange, same bits); stream-ordered.  op_arg as for all_reduce
+    (mccsReduceScatterOpArg; PreMulSum / SumPostDiv always take the ring)."""
     if op_arg is None:
         rc = _sig().mccsReduceScatter(_ptr(send_buf), _ptr(recv_buf), int(recv_count), int(data_type),
                                       int(op_type), comm._h, _stream(stream))

@@ -887,6 +887,36 @@ extern "C" mccsResult_t mccsCommSetAllToAllLL(mccsComm_t comm, size_t bytes_per_
   return mccsSuccess;
 }
 
+extern "C" mccsResult_t mccsCommReduceScatterDirectMax(mccsComm_t comm, size_t* cap, size_t* ll_cap) {
+  err_clear();
+  const Comm* c = (const Comm*)comm;
+  if (!c || !cap || !ll_cap) MCCS_FAIL(mccsInvalidArgument, "mccsCommReduceScatterDirectMax: null communicator or output");
+  *cap = c->connected ? rs_direct_cap(c) : 0;
+  *ll_cap = c->connected ? rs_ll_cap(c) : 0;
+  return mccsSuccess;
+}
+
+extern "C" mccsResult_t mccsCommSetReduceScatterDirect(mccsComm_t comm, size_t block_bytes, size_t ll_block_bytes) {
+  err_clear();
+  StepScope st("mccsCommSetReduceScatterDirect");
+  Comm* c = (Comm*)comm;
+  if (!c || !c->connected) MCCS_FAIL(mccsInvalidUsage, "the communicator is not connected");
+  if (g_group.depth > 0 || c->plan_pending)
+    MCCS_FAIL(mccsInvalidUsage, "the communicator has a group open or a call pending: set the limits between launches");
+  const size_t cap = rs_direct_cap(c), ll_cap = rs_ll_cap(c);
+  if (block_bytes > cap)
+    MCCS_FAIL(mccsInvalidArgument, "block_bytes %zu is above the %zu bytes of a one-shot slot%s", block_bytes, cap,
+              cap ? "" : " (no one-shot slots or no peer atomics: the count-based path is closed here)");
+  if (ll_block_bytes > ll_cap)
+    MCCS_FAIL(mccsInvalidArgument, "ll_block_bytes %zu is above the %zu bytes one block can move through an LL slot%s",
+              ll_block_bytes, ll_cap,
+              ll_cap ? "" : " (no LL slots, a cached arena or system-scope fences: the LL path is closed here)");
+  c->rs_direct_bytes = block_bytes;
+  c->rs_ll_bytes = ll_block_bytes;
+  rs_direct_prepare(c);
+  return mccsSuccess;
+}
+
 extern "C" mccsResult_t mccsCommAllToAllRoute(mccsComm_t comm, int* info2) {
   const Comm* c = (const Comm*)comm;
   if (!c || !info2) return mccsInvalidArgument;

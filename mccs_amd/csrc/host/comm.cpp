@@ -573,6 +573,7 @@ mccsResult_t comm_build_device(Comm* c) {
   MCCS_HIP(rt().Memcpy(c->d_view, views, sizeof(views), hipMemcpyHostToDevice));
   MCCS_CHECK(comm_set_kernel_cfg(c));
   a2a_ll_read_env(c);  // the LL all-to-all limits (the arena's kind and the fence mode are known now)
+  rs_direct_read_env(c);  // and the direct ReduceScatter's
   {
     std::lock_guard<std::mutex> lk(g_live_mu);
     g_live_fifo_slots[c->d_comm] = c->cfg.fifo_slots;

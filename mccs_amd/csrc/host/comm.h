@@ -316,6 +316,13 @@ struct Comm {
     void* recv;
     size_t count;
   } direct{};
+  // Direct ReduceScatter (direct_rs.h).  The opt-in limits in bytes per block
+  // (mccsCommSetReduceScatterDirect; MCCS_RS_DIRECT_BYTES / MCCS_RS_LL_BYTES at
+  // creation), both 0 = off: a ReduceScatter of Sum / Prod / Max / Min whose
+  // block is within one of them, and which is its comm's only call of the
+  // launch, is held in `direct` like an AllReduce and runs direct_rs_kernel
+  // (LL where both fit).  Every rank must set the same values.
+  size_t rs_direct_bytes = 0, rs_ll_bytes = 0;
   // LL all-to-all (direct_a2a.h).  The opt-in limits (mccsCommSetAllToAllLL;
   // MCCS_A2A_LL_BYTES / MCCS_A2AV_LL_BYTES at creation), both 0 = off: a
   // uniform AllToAll of at most a2a_ll_bytes per peer, and every AllToAllv /
@@ -434,6 +441,13 @@ void a2a_ll_prepare(const Comm* c);  // after the limits changed: probes the LL 
 bool a2av_takes_ll(const Comm* c);
 // whether the v calls' ring path is closed to this comm (its route is not one hop)
 bool a2av_needs_relay(const Comm* c);
+// Direct ReduceScatter: the largest block in bytes of the count-based variant (layout.oneshot_slot; 0
+// unless direct_ok) and of the LL variant (ll_slot / 2; 0 where the LL lines can never be used, as a2a_ll_cap)
+size_t rs_direct_cap(const Comm* c);
+size_t rs_ll_cap(const Comm* c);
+// reads MCCS_RS_DIRECT_BYTES / MCCS_RS_LL_BYTES into the comm's limits, clamped to the caps
+void rs_direct_read_env(Comm* c);
+void rs_direct_prepare(const Comm* c);  // after the limits changed: probes the kernels' co-residency once
 mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_t>& user_streams);
 // ring.hip
 const void* ring_kernel_ptr(int func, int dtype, int op);
@@ -443,6 +457,8 @@ int coresident_ring_blocks(int block, int device);
 const void* direct_kernel_ptr(int dtype, int op);
 // direct_a2a.hip
 const void* a2a_ll_kernel_ptr();
+// direct_rs.hip
+const void* direct_rs_kernel_ptr(int dtype, int op);
 hipError_t ring_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_flush_caches(hipStream_t st);
 

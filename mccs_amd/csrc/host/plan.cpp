@@ -491,6 +491,36 @@ static bool ll_fits(const Comm* c, size_t bytes) {
          bytes <= (size_t)c->cfg.ll_bytes && 2 * ((bytes + 7) & ~(size_t)7) <= c->layout.ll_slot;
 }
 
+// ---- direct ReduceScatter (direct_rs.h): the planner path -----------------------
+// The count-based variant needs what the one-shot needs (its slots and peer
+// atomics), the LL variant what the LL one-shot needs (ll_fits' arena and
+// fence conditions); a block fills at most one slot / half an LL slot.
+size_t rs_direct_cap(const Comm* c) { return c->direct_ok ? c->layout.oneshot_slot : 0; }
+
+size_t rs_ll_cap(const Comm* c) {
+  if (c->layout.ll_slot == 0 || !c->own_arena_uncached || c->kcfg.fence_mode == MCCS_FENCE_SYSTEM) return 0;
+  return c->layout.ll_slot / 2;
+}
+
+void rs_direct_read_env(Comm* c) {
+  auto read = [&](const char* name, size_t cap) {
+    const char* v = std::getenv(name);
+    const long long x = v ? std::atoll(v) : 0;
+    return x > 0 ? std::min((size_t)x, cap) : (size_t)0;
+  };
+  c->rs_direct_bytes = read("MCCS_RS_DIRECT_BYTES", rs_direct_cap(c));
+  c->rs_ll_bytes = read("MCCS_RS_LL_BYTES", rs_ll_cap(c));
+  rs_direct_prepare(c);
+}
+
+// Which variant a ReduceScatter block of `bytes` takes on this comm: LL where
+// both fit.  Every rank sees the same limits and the same call, so every rank
+// decides alike.
+static bool rs_takes_ll(const Comm* c, size_t bytes) { return bytes <= c->rs_ll_bytes && bytes <= rs_ll_cap(c); }
+static bool rs_takes_oneshot(const Comm* c, size_t bytes) {
+  return bytes <= c->rs_direct_bytes && bytes <= rs_direct_cap(c);
+}
+
 mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send, void* recv, size_t count,
                           int root, uint64_t op_arg) {
   if (c->plan_pending && (c->plan_func != func || c->plan_dtype != dtype || c->plan_op != op))
@@ -521,10 +551,26 @@ mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send
   const bool twoshot = func == mccsFuncAllReduce && c->layout.direct_slot > 0 && bytes <= (size_t)c->cfg.direct_bytes;
   const bool ll = ll_fits(c, bytes);
   // (the LL one-shot makes no remote atomics: it runs without peer atomics,
-  // the count-based variants need them).  A ReduceScatter, Broadcast or
-  // Reduce always takes the ring: the direct variants are AllReduce /
-  // AllGather only.  So does a PreMulSum or SumPostDiv of any function and
-  // size: direct_kernel.h knows neither the pre nor the post step.
+  // the count-based variants need them).  A Broadcast or Reduce always takes
+  // the ring, and so does a ReduceScatter unless its comm opted in (below):
+  // the default direct variants are AllReduce / AllGather only.  So does a
+  // PreMulSum or SumPostDiv of any function and size: the direct kernels know
+  // neither the pre nor the post step.
+  // One ReduceScatter whose block is within an opt-in limit (both 0: never)
+  // is held for direct_rs_kernel, as the comm's first and only call of the
+  // launch; a second call demotes it (demote_direct above).
+  if (first && !c->plan_pending && func == mccsFuncReduceScatter && op <= mccsDevMin &&
+      (rs_takes_ll(c, bytes) || rs_takes_oneshot(c, bytes))) {
+    c->plan_direct = true;
+    c->direct.send = send;
+    c->direct.recv = recv;
+    c->direct.count = count;
+    c->plan_pending = true;
+    c->plan_func = func;
+    c->plan_dtype = dtype;
+    c->plan_op = op;
+    return mccsSuccess;
+  }
   if (!c->plan_pending && (func == mccsFuncAllReduce || func == mccsFuncAllGather) && op <= mccsDevMin &&
       ((c->direct_ok && (oneshot || twoshot)) || ll)) {
     c->plan_direct = true;
@@ -890,7 +936,8 @@ static bool direct_group(std::vector<Comm*>& comms, const std::vector<int>& idx)
         ck->layout.direct_slot != c0->layout.direct_slot || ck->layout.oneshot_slot != c0->layout.oneshot_slot ||
         ck->layout.ll_slot != c0->layout.ll_slot || ck->cfg.ll_bytes != c0->cfg.ll_bytes ||
         ck->cfg.oneshot_bytes != c0->cfg.oneshot_bytes || ck->cfg.direct_bytes != c0->cfg.direct_bytes ||
-        ck->nch != c0->nch || ck->peer_arena != c0->peer_arena)  // one region table for every slot
+        ck->nch != c0->nch || ck->peer_arena != c0->peer_arena ||  // one region table for every slot
+        ck->rs_direct_bytes != c0->rs_direct_bytes || ck->rs_ll_bytes != c0->rs_ll_bytes)
       return false;
   }
   return idx.size() <= MCCS_MULTI_MAX_RANKS;
@@ -1012,6 +1059,137 @@ static mccsResult_t build_direct(std::vector<Comm*>& comms, const std::vector<in
   };
   da->piece = piece(gather ? bytes : scatter);
   da->piece2 = piece(gather ? scatter : oneshot ? bytes : bytes / n + 1);
+  for (size_t k = 0; k < idx.size(); ++k) {
+    Comm* ck = comms[idx[k]];
+    ck->plan_direct = false;
+    ck->plan_pending = false;
+  }
+  return mccsSuccess;
+}
+
+// Workgroups of the direct ReduceScatter kernels the device holds at once (min
+// over the instantiations), as coresident_direct_blocks.  Probed when a comm
+// opts in (rs_direct_prepare), not at its first launch: that launch may be
+// one a stream is capturing.
+static int coresident_rs_blocks(int device, int* ncu_out) {
+  static std::mutex mu;
+  static std::map<std::pair<unsigned, int>, std::pair<int, int>> cache;  // (runtime, device) -> (blocks, CUs)
+  const auto key = std::make_pair(rt_generation(), device);
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cache.find(key);
+    if (it != cache.end()) {
+      *ncu_out = it->second.second;
+      return it->second.first;
+    }
+  }
+  DeviceGuard g(device);
+  int ncu = 0;
+  if (rt().CuCount(&ncu, device) != hipSuccess) return 0;
+  int best = 1 << 30;
+  for (int dt = 0; dt < mccsNumTypes; ++dt)
+    for (int op = 0; op < 4; ++op) {
+      int per_cu = 0;
+      const void* fn = direct_rs_kernel_ptr(dt, op);
+      if (!fn || rt().BlocksPerCu(&per_cu, fn, MCCS_DIRECT_THREADS) != hipSuccess) return 0;  // not cached
+      best = std::min(best, per_cu);
+    }
+  std::lock_guard<std::mutex> lk(mu);
+  cache[key] = {best * ncu, ncu};
+  *ncu_out = ncu;
+  return best * ncu;
+}
+
+void rs_direct_prepare(const Comm* c) {
+  int ncu = 0;
+  if (c->rs_direct_bytes > 0 || c->rs_ll_bytes > 0) (void)coresident_rs_blocks(c->device, &ncu);
+}
+
+// The direct ReduceScatter launch's arguments (direct_group checked the
+// shape): the ring walk this call would take -- the channels and thread count
+// ring_enqueue gives it (total = the n blocks that enter the ring) and each
+// channel's ring -- and every rank slot's buffers and direct regions.
+static mccsResult_t build_direct_rs(std::vector<Comm*>& comms, const std::vector<int>& idx, mccsDirectArgs* da,
+                                    unsigned* grid_x) {
+  const Comm* c0 = comms[idx[0]];
+  const size_t esize = (size_t)elem_bytes(c0->plan_dtype);
+  const int n = c0->nranks;
+  const size_t nbytes = c0->direct.count * esize;  // one block
+  int nch = 0, nthr = 0;
+  task_schema(nbytes * (size_t)n, c0->nch, &nch, &nthr);
+  int chans[MCCS_MAX_NCHANNELS];
+  const int nsel = select_channels(c0, nch, chans);
+  std::memset(da, 0, sizeof(*da));
+  da->count = c0->direct.count;
+  da->slot_bytes = c0->layout.direct_slot;
+  da->oslot_bytes = c0->layout.oneshot_slot;
+  da->ll_slot_bytes = c0->layout.ll_slot;
+  bool ll = true, oneshot = true;  // every rank slot of the launch must take it
+  for (size_t k = 0; k < idx.size(); ++k) {
+    ll = ll && rs_takes_ll(comms[idx[k]], nbytes);
+    oneshot = oneshot && rs_takes_oneshot(comms[idx[k]], nbytes);
+  }
+  if (!ll && !oneshot) return mccsInternalError;  // plan_enqueue held it for one of them
+  da->mode = ll ? MCCS_DIRECT_RS_LL : MCCS_DIRECT_RS_ONE_SHOT;
+  da->nranks = (uint32_t)n;
+  da->nch = (uint32_t)nsel;
+  da->nthr_ref = (uint32_t)nthr;
+  da->buff_size = (uint32_t)c0->cfg.buffer_size;
+  da->fence_mode = c0->kcfg.fence_mode;
+  da->timeout_ticks = c0->kcfg.timeout_ticks;
+  for (int bid = 0; bid < nsel; ++bid) {
+    const std::vector<int>& ring = c0->rings[chans[bid]];
+    const int pos0 = (int)(std::find(ring.begin(), ring.end(), 0) - ring.begin());
+    for (int k = 0; k < n; ++k) da->idx2rank[bid][k] = (uint8_t)ring[(pos0 + k) % n];
+  }
+  for (size_t k = 0; k < idx.size(); ++k) {
+    const Comm* ck = comms[idx[k]];
+    mccsDirectRank& r = da->r[k];
+    r.send = ck->direct.send;
+    r.recv = ck->direct.recv;
+    for (int t = 0; t < n; ++t) {
+      if (!ck->peer_arena[t]) return mccsInternalError;
+      if (k == 0) da->region[t] = ck->peer_arena[t] + ck->layout.direct_off();
+      else if (da->region[t] != ck->peer_arena[t] + ck->layout.direct_off()) return mccsInternalError;  // direct_group
+    }
+    r.comm = (mccsDevComm*)ck->d_comm;
+    r.abort_flag = ck->d_abort;
+    r.rank = (uint32_t)ck->rank;
+    r.err_line = 1;
+    // safest hand-off of the group, as for the ring (SYSTEM > UNCACHED_RELEASE > UNCACHED)
+    if (ck->kcfg.fence_mode == MCCS_FENCE_SYSTEM) da->fence_mode = MCCS_FENCE_SYSTEM;
+    else if (ck->kcfg.fence_mode == MCCS_FENCE_UNCACHED_RELEASE && da->fence_mode == MCCS_FENCE_UNCACHED)
+      da->fence_mode = MCCS_FENCE_UNCACHED_RELEASE;
+    da->timeout_ticks = (da->timeout_ticks == 0 || ck->kcfg.timeout_ticks == 0)
+                            ? 0
+                            : std::max(da->timeout_ticks, ck->kcfg.timeout_ticks);
+  }
+  // Workgroups from phase 1, the n-1 foreign blocks: ~4 KiB each
+  // (build_direct's MCCS_DIRECT_WG_BYTES default), or (LL) one 8-byte word
+  // per thread; capped by co-residency as build_direct caps its launches.
+  const size_t scatter = nbytes * (size_t)(n - 1);
+  int ncu = 0;
+  const int cap = coresident_rs_blocks(c0->device, &ncu);
+  if (ncu <= 0) ncu = cap;
+  long g = std::min<long>((long)((scatter + 4095) / 4096), c0->direct_blocks);
+  if (ll)
+    g = std::min<long>((long)(((size_t)(n - 1) * ((nbytes + 7) / 8) + MCCS_DIRECT_THREADS - 1) / MCCS_DIRECT_THREADS),
+                       c0->direct_blocks);
+  if (idx.size() > 1) g = std::min<long>(g, std::min(cap, ncu) / (long)idx.size());  // one fused launch
+  else if (c0->share > 1) g = std::min<long>(g, std::min(cap / 2, ncu) / c0->share);  // separate processes
+  g = std::max<long>(g, 1);
+  if (g * (long)idx.size() > cap)
+    MCCS_FAIL(mccsInvalidUsage, "direct ReduceScatter launch of %zu ranks x %ld workgroups exceeds the %d co-resident "
+              "ones of device %d", idx.size(), g, cap, c0->device);
+  *grid_x = (unsigned)g;
+  // pieces: each phase's bytes over the workgroups, in 4 KiB steps, 4..64 KiB
+  auto piece = [&](size_t phase_bytes) {
+    size_t p = (phase_bytes + (size_t)g - 1) / (size_t)g;
+    p = std::min<size_t>(std::max<size_t>((p + 4095) & ~(size_t)4095, 4096), 65536);
+    return (uint32_t)(p / esize);
+  };
+  da->piece = piece(scatter);
+  da->piece2 = piece(nbytes);
   for (size_t k = 0; k < idx.size(); ++k) {
     Comm* ck = comms[idx[k]];
     ck->plan_direct = false;
@@ -1210,9 +1388,14 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
       for (int i : idx) la.no_guard |= comms[i]->kcfg.no_guard;
       args[0] = &la;
     } else if (direct) {
-      MCCS_CHECK(build_direct(comms, idx, &da, &grid));
-      fn = c0->plan_func == mccsFuncAllGather ? direct_kernel_ptr(mccsInt8, mccsDevSum)
-                                              : direct_kernel_ptr(c0->plan_dtype, c0->plan_op);
+      if (c0->plan_func == mccsFuncReduceScatter) {
+        MCCS_CHECK(build_direct_rs(comms, idx, &da, &grid));
+        fn = direct_rs_kernel_ptr(c0->plan_dtype, c0->plan_op);
+      } else {
+        MCCS_CHECK(build_direct(comms, idx, &da, &grid));
+        fn = c0->plan_func == mccsFuncAllGather ? direct_kernel_ptr(mccsInt8, mccsDevSum)
+                                                : direct_kernel_ptr(c0->plan_dtype, c0->plan_op);
+      }
       if (!fn) return mccsInvalidArgument;
       block = MCCS_DIRECT_THREADS;
       da.guard_order = guard_order(comms, idx);
@@ -1332,8 +1515,10 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
       comms[idx[k]]->last_algo = a2all                              ? MCCS_ALGO_LL
                                  : !direct                          ? MCCS_ALGO_RING
                                  : da.mode == MCCS_DIRECT_TWO_SHOT ? MCCS_ALGO_DIRECT
-                                 : da.mode == MCCS_DIRECT_LL_ONE_SHOT || da.mode == MCCS_DIRECT_LL_AG ? MCCS_ALGO_LL
-                                                                   : MCCS_ALGO_ONESHOT;
+                                 : da.mode == MCCS_DIRECT_LL_ONE_SHOT || da.mode == MCCS_DIRECT_LL_AG ||
+                                           da.mode == MCCS_DIRECT_RS_LL
+                                     ? MCCS_ALGO_LL
+                                     : MCCS_ALGO_ONESHOT;
     }
     if (!capturing) c0->event_recorded = record || stop_on_launch;
   }

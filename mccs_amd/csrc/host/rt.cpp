@@ -399,7 +399,8 @@ class FakeRuntime final : public DeviceRuntime {
     std::string extra;
     bool direct = false;
     for (int dt = 0; dt < mccsNumTypes && fn; ++dt)
-      for (int op = 0; op < 4; ++op) direct = direct || fn == direct_kernel_ptr(dt, op);
+      for (int op = 0; op < 4; ++op)
+        direct = direct || fn == direct_kernel_ptr(dt, op) || fn == direct_rs_kernel_ptr(dt, op);
     const bool a2all = fn && fn == a2a_ll_kernel_ptr();
     if (fn && args && grid.y >= 1 && grid.y <= MCCS_MULTI_MAX_RANKS) {
       if (a2all) {
@@ -437,6 +438,8 @@ class FakeRuntime final : public DeviceRuntime {
                             : da->mode == MCCS_DIRECT_AG_ONE_SHOT ? "ag-oneshot"
                             : da->mode == MCCS_DIRECT_LL_ONE_SHOT ? "ll"
                             : da->mode == MCCS_DIRECT_LL_AG       ? "ll-ag"
+                            : da->mode == MCCS_DIRECT_RS_ONE_SHOT ? "rs-oneshot"
+                            : da->mode == MCCS_DIRECT_RS_LL       ? "rs-ll"
                                                                   : "twoshot") +
                 " gx=" + std::to_string(grid.x) + " llslot=" + std::to_string(da->ll_slot_bytes) +
                 " piece=" + std::to_string(da->piece) + " piece2=" + std::to_string(da->piece2) +
@@ -444,6 +447,16 @@ class FakeRuntime final : public DeviceRuntime {
                 " owned=";
         for (unsigned t = 0; t < da->nranks && t < MCCS_DIRECT_MAX_RANKS; ++t)
           extra += (t ? "," : "") + std::to_string(da->owned[t]);
+        // a direct ReduceScatter also names its rank slots: rank:send:recv (hex), '/' between them
+        if (da->mode == MCCS_DIRECT_RS_ONE_SHOT || da->mode == MCCS_DIRECT_RS_LL) {
+          extra += " slots=";
+          for (unsigned k = 0; k < grid.y; ++k) {
+            char hex[64];
+            std::snprintf(hex, sizeof(hex), "%u:%llx:%llx", da->r[k].rank, (unsigned long long)(uintptr_t)da->r[k].send,
+                          (unsigned long long)(uintptr_t)da->r[k].recv);
+            extra += (k ? "/" : "") + std::string(hex);
+          }
+        }
       } else {
         const mccsMultiLaunchArgs* ma = (const mccsMultiLaunchArgs*)args[0];
         for (unsigned k = 0; k < grid.y; ++k) on_dev = on_dev && dev_of(ma->comm[k]) == cur_;
@@ -548,7 +561,7 @@ class FakeRuntime final : public DeviceRuntime {
     if (!fn || !args || grid.y < 1 || grid.y > MCCS_MULTI_MAX_RANKS) return;
     for (int dt = 0; dt < mccsNumTypes; ++dt)
       for (int op = 0; op < 4; ++op)
-        if (fn == direct_kernel_ptr(dt, op)) return;
+        if (fn == direct_kernel_ptr(dt, op) || fn == direct_rs_kernel_ptr(dt, op)) return;
     if (fn == a2a_ll_kernel_ptr()) return;
     const mccsMultiLaunchArgs* ma = (const mccsMultiLaunchArgs*)args[0];
     if (ma->inline_works) return;

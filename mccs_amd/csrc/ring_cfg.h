@@ -253,6 +253,25 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 // a launch without a hand-off this rank makes in that same launch (with
 // count >= 1 some rank owns elements, and whoever it is waits, directly or
 // through its broadcast, for this rank's phase-1 count).
+//
+// Direct ReduceScatter (direct_rs.h, opt-in: mccsCommSetReduceScatterDirect)
+// uses the same region and state and adds no slot: sender s writes block t of
+// its input only into t's region, at the element offset within the block --
+//   count-based: the one-shot slot [parity seq & 1][sender s] (a block of at
+//     most oslot_bytes), then one add of recvcount to t's IN_CNT(s);
+//   LL: line w of the LL slot [parity][sender s] for the block's 8-byte word
+//     w (a block of at most ll_slot_bytes / 2), flagged like every LL line.
+// E_IN advances by recvcount per count-based launch: every sender sends every
+// receiver exactly one block, so the single word stays the running total of
+// every sender's line across any mix with one-shot / two-shot AllReduce and
+// AllGather launches (each of which also adds one common amount per sender).
+// Parity reuse is the one-shot's argument, and here it needs no case split:
+// with recvcount >= 1 EVERY ordered pair (s, t) hands off in EVERY launch (t
+// waits for s's count, or polls line 0 of s's slot), so s cannot finish
+// launch L+1 -- and start writing parity p again in L+2 -- before t made its
+// own writes of L+1; and a rank's launch L+1 starts only after its launch L
+// ended (stream order between eager launches, the launch guard between graph
+// replays), i.e. after it finished reading parity p.
 #define MCCS_DIRECT_MAX_RANKS 8
 #define MCCS_DIRECT_CTRL_BYTES 65536
 // u64, added to by sender s; a rank's own line IN_CNT(rank) counts its own
@@ -276,6 +295,9 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 #define MCCS_DIRECT_AG_ONE_SHOT 2  // AllGather: count = bytes per rank (dtype int8)
 #define MCCS_DIRECT_LL_ONE_SHOT 3  // one-shot through flag-carrying 16-byte lines (uncached arenas)
 #define MCCS_DIRECT_LL_AG 4        // AllGather through the same lines (count = bytes per rank)
+// direct ReduceScatter (direct_rs.h; count = recvcount, the elements of one block)
+#define MCCS_DIRECT_RS_ONE_SHOT 5  // through the one-shot slots, counted on IN_CNT
+#define MCCS_DIRECT_RS_LL 6        // through the LL lines
 
 struct mccsDirectRank {  // one rank slot of a direct launch (blockIdx.y)
   const void* send;
@@ -298,7 +320,7 @@ struct mccsDirectArgs {
   uint64_t timeout_ticks;  // s_memrealtime ticks; 0 = never
   uint32_t nranks, nch, nthr_ref, buff_size;  // the ring walk this launch reproduces
   uint32_t fence_mode;                        // MCCS_FENCE_*
-  uint32_t mode;                              // MCCS_DIRECT_TWO_SHOT / ONE_SHOT / AG_ONE_SHOT
+  uint32_t mode;                              // MCCS_DIRECT_* above (the RS modes: direct_rs_kernel only)
   uint32_t piece;                             // elements per piece of the scatter / gather phases
   uint32_t piece2;                            // elements per piece of the reduction phase
   uint32_t no_guard;                          // 1: skip the launch guard (test hook only)

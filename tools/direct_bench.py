@@ -9,6 +9,10 @@ direct kernel should take a bucket.
   python tools/direct_bench.py [--n 2 4 8] [--sizes-kib 32 128 ...] [--blocks 32 128]
 Per (n, size): ring / direct us per call, eager (back-to-back calls, one
 sync) and graph-replayed (20 calls per graph).
+  python tools/direct_bench.py --reduce-scatter [--n 2 4 8] [--sizes-kib 1 4 ...]
+ReduceScatter per block size (1 KiB to the caps by default): the ring (limits
+0), the direct and the LL variant (mccsCommSetReduceScatterDirect) and the
+one-shot AllGather of the same bytes per rank beside them.
 """
 import argparse
 import json
@@ -19,6 +23,87 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def _time_call(torch, once, st, calls):
+    """us per call: eager (back-to-back, one sync) and graph-replayed (20 calls per graph)."""
+    for _ in range(5):
+        once()
+    st.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(calls):
+        once()
+    st.synchronize()
+    eager = (time.perf_counter() - t0) / calls
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=st):
+        for _ in range(20):
+            once()
+    g.replay()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(5):
+        g.replay()
+    torch.cuda.synchronize()
+    graph = (time.perf_counter() - t0) / 100
+    del g
+    return round(eager * 1e6, 2), round(graph * 1e6, 2)
+
+
+def reduce_scatter_mode(args, torch, C, st, dt, code, es):
+    """--reduce-scatter: per block size (bytes per block = bytes per rank of the
+    AllGather beside it) the ring ReduceScatter (limits 0), the direct and the
+    LL ReduceScatter (mccsCommSetReduceScatterDirect at the caps) and the
+    one-shot AllGather, its partner in a sharded-optimizer step."""
+    top = 1 << 20
+    sizes = args.sizes_kib if args.sizes_kib != DEFAULT_SIZES_KIB else [1, 4, 16, 64, 256, 1024]
+    rows = []
+    for n in args.n:
+        cfg = C.CommConfig(direct_bytes=-1, oneshot_bytes=top, ll_bytes=top)
+        sets = {"rs_ring": C.init_all([0] * n, cfg), "rs_direct": C.init_all([0] * n, cfg),
+                "rs_ll": C.init_all([0] * n, cfg),
+                "ag_oneshot": C.init_all([0] * n, C.CommConfig(direct_bytes=-1, oneshot_bytes=top, ll_bytes=-1))}
+        cap, ll_cap = sets["rs_direct"][0].reduce_scatter_direct_max()
+        for c in sets["rs_direct"]:
+            c.set_reduce_scatter_direct(block_bytes=cap)
+        for c in sets["rs_ll"]:
+            c.set_reduce_scatter_direct(ll_block_bytes=ll_cap)
+        want = {"rs_ring": "ring", "rs_direct": "oneshot", "rs_ll": "ll", "ag_oneshot": "oneshot"}
+        for kib in sizes:
+            nbytes = kib << 10
+            cnt = nbytes // es
+            xs = [torch.randn(n * cnt, device="cuda").to(dt) for _ in range(n)]
+            ys = [torch.empty(n * cnt, dtype=dt, device="cuda") for _ in xs]
+            row = {"n": n, "block_bytes": nbytes, "cap": cap, "ll_cap": ll_cap}
+            for name, comms in sets.items():
+                if (name == "rs_direct" and nbytes > cap) or (name == "rs_ll" and nbytes > ll_cap) or \
+                        (name == "ag_oneshot" and nbytes > top):
+                    continue
+
+                def once():
+                    with C.group():
+                        for r in range(n):
+                            if name == "ag_oneshot":
+                                C.all_gather(comms[r], xs[r], ys[r], nbytes, stream=st)
+                            else:
+                                C.reduce_scatter(comms[r], xs[r], ys[r], cnt, code, 0, stream=st)
+
+                row[name + "_eager_us"], row[name + "_graph_us"] = _time_call(torch, once, st, args.calls)
+                assert comms[0].last_algo() == want[name], (name, comms[0].last_algo())
+                for c in comms:
+                    c.sync()
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            del xs, ys
+        torch.cuda.synchronize()
+        for comms in sets.values():
+            for c in comms:
+                c.destroy()
+    print(json.dumps({"tool": "direct_bench", "collective": "reducescatter", "dtype": args.dtype, "rows": rows}),
+          flush=True)
+
+
+DEFAULT_SIZES_KIB = [32, 128, 512, 2048, 8192, 32768]
+
+
 def main():
     import torch
 
@@ -27,7 +112,7 @@ def main():
 
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[2, 4, 8])
-    ap.add_argument("--sizes-kib", type=int, nargs="+", default=[32, 128, 512, 2048, 8192, 32768])
+    ap.add_argument("--sizes-kib", type=int, nargs="+", default=DEFAULT_SIZES_KIB)
     ap.add_argument("--blocks", type=int, nargs="+", default=[128])
     ap.add_argument("--calls", type=int, default=100)
     ap.add_argument("--dtype", default="float16")
@@ -35,12 +120,18 @@ def main():
     ap.add_argument("--algos", nargs="+", default=["ring", "direct", "oneshot", "ll"],
                     help="variants to time (rocprof passes isolate one kernel mode each)")
     ap.add_argument("--allgather", action="store_true", help="time AllGather (size = bytes per rank): ring vs one-shot")
+    ap.add_argument("--reduce-scatter", action="store_true",
+                    help="time ReduceScatter (size = bytes per block, 1 KiB to the caps): ring vs direct vs LL, and "
+                         "the one-shot AllGather of the same bytes per rank")
     args = ap.parse_args()
     dt = getattr(torch, args.dtype)
     code = {torch.float16: 6, torch.float32: 7, torch.bfloat16: 9}[dt]
     es = torch.empty(0, dtype=dt).element_size()
     rows = []
     st = side_stream(torch, 0, slot=1)
+    if args.reduce_scatter:
+        reduce_scatter_mode(args, torch, C, st, dt, code, es)
+        return
     for n in args.n:
         top = max(args.sizes_kib) << 10
         cfgs = {"ring": C.CommConfig(direct_bytes=-1, oneshot_bytes=-1, ll_bytes=-1),
