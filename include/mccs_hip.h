@@ -287,8 +287,12 @@ mccsResult_t mccsReduceScatter(const void *sendbuff, void *recvbuff, size_t recv
  * dtypes or ops on one comm in a group is refused with mccsInvalidUsage at
  * mccsGroupEnd; ranks sharing a GPU run as one fused launch; the call may be
  * captured into a HIP graph; the watchdog and mccsCommAbort end a stuck
- * kernel.  Always the ring (mccsCommLastAlgo reports MCCS_ALGO_RING), whatever
- * the size.  nbytes / count == 0 succeeds and launches nothing; a root outside
+ * kernel.  The ring (mccsCommLastAlgo reports MCCS_ALGO_RING) at every size,
+ * unless the communicator opted in to the direct Broadcast / Reduce
+ * (mccsCommSetRootedDirect, below): a small buffer then takes one exchange
+ * instead of the chain's n-1 hops, with the ring's result bit for bit; such a
+ * call takes no FIFO step, so it leaves the connections where they were.
+ * nbytes / count == 0 succeeds and launches nothing; a root outside
  * [0, nranks) is refused with mccsInvalidArgument (mccsGetLastErrorString names
  * it), as are an unknown dtype or op and a NULL buffer where the rank's role
  * uses it; nranks == 1 is a local copy.  Every rank must name the same root:
@@ -493,6 +497,45 @@ mccsResult_t mccsCommAllToAllLLMax(mccsComm_t comm, size_t *cap);
  * path. */
 mccsResult_t mccsCommSetReduceScatterDirect(mccsComm_t comm, size_t block_bytes, size_t ll_block_bytes);
 mccsResult_t mccsCommReduceScatterDirectMax(mccsComm_t comm, size_t *cap, size_t *ll_cap);
+/* The direct Broadcast and Reduce: the root writes its bytes once into every
+ * peer's slot of the direct region (Broadcast), or every rank writes its input
+ * once into the root's slot and the root folds them (Reduce) -- one exchange
+ * instead of the ring chain's n-1 serial hops.  The result is
+ * the ring's, bit for bit: Reduce keeps the ring's channels, chunks and
+ * summation order.  Opt-in per communicator; the four limits are bytes of the
+ * WHOLE BUFFER (nbytes; count x element size), two per function because their
+ * crossovers need not agree; all default to 0 = off, and with all four off
+ * every call plans exactly as without this entry point.  MCCS_BC_DIRECT_BYTES /
+ * MCCS_BC_LL_BYTES / MCCS_RD_DIRECT_BYTES / MCCS_RD_LL_BYTES in the environment
+ * set them when the communicator is created (clamped to the maxima below).
+ * mccsCommRootedDirectMax: the direct ReduceScatter's maxima, over the whole
+ * buffer: *cap, the largest buffer of the count-based variant (one one-shot
+ * slot: oneshot_bytes rounded up to 64 KiB; 0 without one-shot slots --
+ * oneshot_bytes < 0, nranks outside 2..8 -- or without peer atomics); *ll_cap,
+ * the largest buffer of the LL variant (ll_slot / 2 = ll_bytes rounded up to
+ * 8; 0 where the lines cannot be used: no LL slots, a cached FIFO arena,
+ * system-scope fences).
+ * mccsCommSetRootedDirect: a value above its maximum is refused with
+ * mccsInvalidArgument; a call while the communicator has a group open or a
+ * call pending, with mccsInvalidUsage.  EVERY RANK MUST SET THE SAME FOUR
+ * VALUES: ranks that disagree pick different kernels for one call and stall
+ * until the watchdog; like disagreeing roots this is not detected.
+ * A mccsBroadcast, or a mccsReduce of Sum / Prod / Max / Min, within its
+ * function's LL limit takes the LL variant (mccsCommLastAlgo reports
+ * MCCS_ALGO_LL), else one within its count-based limit that variant
+ * (MCCS_ALGO_ONESHOT), when it is its communicator's only call of the launch;
+ * a larger one, one sharing a group with a second call of the communicator
+ * (both keep their roots), and every PreMulSum / SumPostDiv (mccsReduceOpArg,
+ * the average) take the ring as before.  Every argument check of the two calls
+ * comes first and is unchanged.  In place on the root is supported; a
+ * non-root's recvbuff (Reduce) and sendbuff (Broadcast) are never touched and
+ * may be NULL.  A direct rooted call takes no FIFO step: the connections stay
+ * where they were.  Ranks sharing a GPU are fused into one launch as always;
+ * the call may be captured into a HIP graph.  The node gate does not cover
+ * this path. */
+mccsResult_t mccsCommSetRootedDirect(mccsComm_t comm, size_t bcast_bytes, size_t bcast_ll_bytes, size_t reduce_bytes,
+                                     size_t reduce_ll_bytes);
+mccsResult_t mccsCommRootedDirectMax(mccsComm_t comm, size_t *cap, size_t *ll_cap);
 /* Send / Recv: grouped point-to-point (torch's batch_isend_irecv; the pieces of
  * a Gather or Scatter).  mccsSend moves count * elem_bytes(dtype) bytes from
  * sendbuff to rank `peer`, mccsRecv receives as many from rank `peer` into

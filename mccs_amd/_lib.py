@@ -113,6 +113,8 @@ SIGNATURES: dict[str, tuple] = {
     "mccsCommAllToAllLLMax": (_c_int, [_c_void_p, _P(_c_size_t)]),
     "mccsCommSetReduceScatterDirect": (_c_int, [_c_void_p, _c_size_t, _c_size_t]),
     "mccsCommReduceScatterDirectMax": (_c_int, [_c_void_p, _P(_c_size_t), _P(_c_size_t)]),
+    "mccsCommSetRootedDirect": (_c_int, [_c_void_p, _c_size_t, _c_size_t, _c_size_t, _c_size_t]),
+    "mccsCommRootedDirectMax": (_c_int, [_c_void_p, _P(_c_size_t), _P(_c_size_t)]),
     "mccs_alltoall_route": (
         _c_int, [_c_int, _c_int, _P(_c_int), _c_int, _P(_c_int), _P(_c_int), _P(_c_int), _P(_c_int)]),
     "mccs_host_ring_all_to_all": (

@@ -280,6 +280,30 @@ class Communicator:
                    "mccsCommReduceScatterDirectMax")
         return int(cap.value), int(ll_cap.value)
 
+    def set_rooted_direct(self, bcast_bytes: int = 0, bcast_ll_bytes: int = 0, reduce_bytes: int = 0,
+                          reduce_ll_bytes: int = 0) -> None:
+        """mccsCommSetRootedDirect: opts the communicator in to the direct
+        Broadcast and Reduce (0 = off, the default).  The four limits are bytes
+        of the whole buffer.  A broadcast, or a reduce of Sum / Prod / Max / Min,
+        that is the communicator's only call of its launch takes the LL kernel
+        when it is within its function's LL limit (last_algo() == "ll"), else
+        the count-based one within the other ("oneshot"); the result is the
+        ring's bit for bit.  Every rank must set the same four values, each at
+        most its rooted_direct_max()."""
+        rc = _sig().mccsCommSetRootedDirect(self._h, int(bcast_bytes), int(bcast_ll_bytes), int(reduce_bytes),
+                                            int(reduce_ll_bytes))
+        _lib.check(rc, "mccsCommSetRootedDirect")
+
+    def rooted_direct_max(self) -> tuple[int, int]:
+        """mccsCommRootedDirectMax: (cap, ll_cap), the largest buffer in bytes
+        of the count-based and of the LL variant; 0 where one cannot be used
+        (no slots or no peer atomics; no LL slots, a cached arena, system-scope
+        fences)."""
+        cap, ll_cap = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        _lib.check(_sig().mccsCommRootedDirectMax(self._h, ctypes.byref(cap), ctypes.byref(ll_cap)),
+                   "mccsCommRootedDirectMax")
+        return int(cap.value), int(ll_cap.value)
+
     def all_to_all_route(self) -> dict:
         """The comm's AllToAll route (mccsCommAllToAllRoute): hops (1: every
         block goes straight to its ring successor; nranks - 1: relayed along the
@@ -416,7 +440,9 @@ def reduce_scatter(comm: Communicator, send_buf, recv_buf, recv_count: int, data
 def broadcast(comm: Communicator, send_buf, recv_buf, nbytes: int, root: int, stream=None) -> None:
     """mccsBroadcast: every rank's recv[0, nbytes) becomes the root's
     send[0, nbytes).  send is read on the root only (None elsewhere); in place
-    on the root is recv == send.  Always the ring; stream-ordered."""
+    on the root is recv == send.  The ring, unless the communicator opted in
+    with set_rooted_direct and nbytes is within a limit (then one direct
+    exchange, same bytes); stream-ordered."""
     rc = _sig().mccsBroadcast(_ptr(send_buf), _ptr(recv_buf), int(nbytes), int(root), comm._h, _stream(stream))
     _lib.check(rc, "mccsBroadcast")
 
@@ -425,8 +451,10 @@ def reduce(comm: Communicator, send_buf, recv_buf, count: int, data_type=AllRedu
            op_type=AllReduceOpType.Sum, root: int = 0, stream=None, op_arg: int | None = None) -> None:
     """mccsReduce: the root's recv[0, count) gets the reduction of every rank's
     send[0, count).  recv is used on the root only (None elsewhere); in place on
-    the root is recv == send.  Always the ring; stream-ordered.  op_arg as for
-    all_reduce (mccsReduceOpArg)."""
+    the root is recv == send.  The ring, unless the communicator opted in with
+    set_rooted_direct and the buffer is within a limit (then one direct
+    exchange, same bits); stream-ordered.  op_arg as for all_reduce
+    (mccsReduceOpArg; PreMulSum / SumPostDiv always take the ring)."""
     if op_arg is None:
         rc = _sig().mccsReduce(_ptr(send_buf), _ptr(recv_buf), int(count), int(data_type), int(op_type), int(root),
                                comm._h, _stream(stream))

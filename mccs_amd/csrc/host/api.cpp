@@ -917,6 +917,49 @@ extern "C" mccsResult_t mccsCommSetReduceScatterDirect(mccsComm_t comm, size_t b
   return mccsSuccess;
 }
 
+extern "C" mccsResult_t mccsCommRootedDirectMax(mccsComm_t comm, size_t* cap, size_t* ll_cap) {
+  err_clear();
+  const Comm* c = (const Comm*)comm;
+  if (!c || !cap || !ll_cap) MCCS_FAIL(mccsInvalidArgument, "mccsCommRootedDirectMax: null communicator or output");
+  *cap = c->connected ? rs_direct_cap(c) : 0;
+  *ll_cap = c->connected ? rs_ll_cap(c) : 0;
+  return mccsSuccess;
+}
+
+extern "C" mccsResult_t mccsCommSetRootedDirect(mccsComm_t comm, size_t bcast_bytes, size_t bcast_ll_bytes,
+                                                size_t reduce_bytes, size_t reduce_ll_bytes) {
+  err_clear();
+  StepScope st("mccsCommSetRootedDirect");
+  Comm* c = (Comm*)comm;
+  if (!c || !c->connected) MCCS_FAIL(mccsInvalidUsage, "the communicator is not connected");
+  if (g_group.depth > 0 || c->plan_pending)
+    MCCS_FAIL(mccsInvalidUsage, "the communicator has a group open or a call pending: set the limits between launches");
+  const size_t cap = rs_direct_cap(c), ll_cap = rs_ll_cap(c);
+  const struct {
+    const char* name;
+    size_t v;
+    bool ll;
+  } lim[4] = {{"bcast_bytes", bcast_bytes, false},
+              {"bcast_ll_bytes", bcast_ll_bytes, true},
+              {"reduce_bytes", reduce_bytes, false},
+              {"reduce_ll_bytes", reduce_ll_bytes, true}};
+  for (const auto& l : lim) {
+    if (!l.ll && l.v > cap)
+      MCCS_FAIL(mccsInvalidArgument, "%s %zu is above the %zu bytes of a one-shot slot%s", l.name, l.v, cap,
+                cap ? "" : " (no one-shot slots or no peer atomics: the count-based path is closed here)");
+    if (l.ll && l.v > ll_cap)
+      MCCS_FAIL(mccsInvalidArgument, "%s %zu is above the %zu bytes one buffer can move through an LL slot%s", l.name,
+                l.v, ll_cap,
+                ll_cap ? "" : " (no LL slots, a cached arena or system-scope fences: the LL path is closed here)");
+  }
+  c->bc_direct_bytes = bcast_bytes;
+  c->bc_ll_bytes = bcast_ll_bytes;
+  c->rd_direct_bytes = reduce_bytes;
+  c->rd_ll_bytes = reduce_ll_bytes;
+  rs_direct_prepare(c);
+  return mccsSuccess;
+}
+
 extern "C" mccsResult_t mccsCommAllToAllRoute(mccsComm_t comm, int* info2) {
   const Comm* c = (const Comm*)comm;
   if (!c || !info2) return mccsInvalidArgument;

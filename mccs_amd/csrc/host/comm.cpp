@@ -574,6 +574,7 @@ mccsResult_t comm_build_device(Comm* c) {
   MCCS_CHECK(comm_set_kernel_cfg(c));
   a2a_ll_read_env(c);  // the LL all-to-all limits (the arena's kind and the fence mode are known now)
   rs_direct_read_env(c);  // and the direct ReduceScatter's
+  rooted_direct_read_env(c);  // and the direct Broadcast's and Reduce's
   {
     std::lock_guard<std::mutex> lk(g_live_mu);
     g_live_fifo_slots[c->d_comm] = c->cfg.fifo_slots;

@@ -315,7 +315,16 @@ struct Comm {
     const void* send;
     void* recv;
     size_t count;
+    int root;  // a held Broadcast / Reduce: its root (else 0)
   } direct{};
+  // Direct Broadcast and Reduce (direct_rooted.h).  The four opt-in limits in
+  // bytes of the whole buffer (mccsCommSetRootedDirect; MCCS_BC_DIRECT_BYTES /
+  // MCCS_BC_LL_BYTES / MCCS_RD_DIRECT_BYTES / MCCS_RD_LL_BYTES at creation),
+  // all 0 = off: a Broadcast, or a Reduce of Sum / Prod / Max / Min, within
+  // one of its function's limits, and which is its comm's only call of the
+  // launch, is held in `direct` (with its root) and runs direct_bc_kernel /
+  // direct_rd_kernel (LL where both fit).  Every rank must set the same values.
+  size_t bc_direct_bytes = 0, bc_ll_bytes = 0, rd_direct_bytes = 0, rd_ll_bytes = 0;
   // Direct ReduceScatter (direct_rs.h).  The opt-in limits in bytes per block
   // (mccsCommSetReduceScatterDirect; MCCS_RS_DIRECT_BYTES / MCCS_RS_LL_BYTES at
   // creation), both 0 = off: a ReduceScatter of Sum / Prod / Max / Min whose
@@ -448,6 +457,9 @@ size_t rs_ll_cap(const Comm* c);
 // reads MCCS_RS_DIRECT_BYTES / MCCS_RS_LL_BYTES into the comm's limits, clamped to the caps
 void rs_direct_read_env(Comm* c);
 void rs_direct_prepare(const Comm* c);  // after the limits changed: probes the kernels' co-residency once
+// Direct Broadcast / Reduce: the caps are the direct ReduceScatter's, over the whole buffer
+// reads MCCS_BC_DIRECT_BYTES / MCCS_BC_LL_BYTES / MCCS_RD_DIRECT_BYTES / MCCS_RD_LL_BYTES, clamped to the caps
+void rooted_direct_read_env(Comm* c);
 mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_t>& user_streams);
 // ring.hip
 const void* ring_kernel_ptr(int func, int dtype, int op);
@@ -459,6 +471,9 @@ const void* direct_kernel_ptr(int dtype, int op);
 const void* a2a_ll_kernel_ptr();
 // direct_rs.hip
 const void* direct_rs_kernel_ptr(int dtype, int op);
+// direct_rooted.hip, direct_rooted_bc.hip
+const void* direct_rd_kernel_ptr(int dtype, int op);
+const void* direct_bc_kernel_ptr();
 hipError_t ring_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_flush_caches(hipStream_t st);
 

@@ -481,7 +481,9 @@ static mccsResult_t demote_direct(Comm* c) {
   if (!c->plan_direct) return mccsSuccess;
   c->plan_direct = false;
   c->plan_pending = false;
-  return ring_enqueue(c, c->plan_func, c->plan_dtype, c->plan_op, c->direct.send, c->direct.recv, c->direct.count);
+  // (a held Broadcast / Reduce goes back with its root; every other held call has root 0, the default)
+  return ring_enqueue(c, c->plan_func, c->plan_dtype, c->plan_op, c->direct.send, c->direct.recv, c->direct.count,
+                      c->direct.root);
 }
 
 // The LL one-shot needs an uncached arena: its lines are polled with
@@ -521,6 +523,31 @@ static bool rs_takes_oneshot(const Comm* c, size_t bytes) {
   return bytes <= c->rs_direct_bytes && bytes <= rs_direct_cap(c);
 }
 
+// ---- direct Broadcast / Reduce (direct_rooted.h): the planner path --------------
+// The caps and availability conditions are the direct ReduceScatter's, with
+// the whole buffer where it has a block; two limits per function.
+void rooted_direct_read_env(Comm* c) {
+  auto read = [&](const char* name, size_t cap) {
+    const char* v = std::getenv(name);
+    const long long x = v ? std::atoll(v) : 0;
+    return x > 0 ? std::min((size_t)x, cap) : (size_t)0;
+  };
+  c->bc_direct_bytes = read("MCCS_BC_DIRECT_BYTES", rs_direct_cap(c));
+  c->bc_ll_bytes = read("MCCS_BC_LL_BYTES", rs_ll_cap(c));
+  c->rd_direct_bytes = read("MCCS_RD_DIRECT_BYTES", rs_direct_cap(c));
+  c->rd_ll_bytes = read("MCCS_RD_LL_BYTES", rs_ll_cap(c));
+  rs_direct_prepare(c);
+}
+
+// Which variant a Broadcast / Reduce of `bytes` takes on this comm: LL where
+// both fit.  Every rank sees the same limits and the same call.
+static bool rooted_takes_ll(const Comm* c, int func, size_t bytes) {
+  return bytes <= (func == mccsFuncBoadcast ? c->bc_ll_bytes : c->rd_ll_bytes) && bytes <= rs_ll_cap(c);
+}
+static bool rooted_takes_oneshot(const Comm* c, int func, size_t bytes) {
+  return bytes <= (func == mccsFuncBoadcast ? c->bc_direct_bytes : c->rd_direct_bytes) && bytes <= rs_direct_cap(c);
+}
+
 mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send, void* recv, size_t count,
                           int root, uint64_t op_arg) {
   if (c->plan_pending && (c->plan_func != func || c->plan_dtype != dtype || c->plan_op != op))
@@ -551,8 +578,8 @@ mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send
   const bool twoshot = func == mccsFuncAllReduce && c->layout.direct_slot > 0 && bytes <= (size_t)c->cfg.direct_bytes;
   const bool ll = ll_fits(c, bytes);
   // (the LL one-shot makes no remote atomics: it runs without peer atomics,
-  // the count-based variants need them).  A Broadcast or Reduce always takes
-  // the ring, and so does a ReduceScatter unless its comm opted in (below):
+  // the count-based variants need them).  A Broadcast, Reduce or
+  // ReduceScatter takes the ring unless its comm opted in (below):
   // the default direct variants are AllReduce / AllGather only.  So does a
   // PreMulSum or SumPostDiv of any function and size: the direct kernels know
   // neither the pre nor the post step.
@@ -565,6 +592,23 @@ mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send
     c->direct.send = send;
     c->direct.recv = recv;
     c->direct.count = count;
+    c->direct.root = 0;
+    c->plan_pending = true;
+    c->plan_func = func;
+    c->plan_dtype = dtype;
+    c->plan_op = op;
+    return mccsSuccess;
+  }
+  // One Broadcast, or one Reduce of Sum / Prod / Max / Min, within an opt-in
+  // limit of its function (all 0: never) is held likewise, with its root, for
+  // direct_bc_kernel / direct_rd_kernel.  (A Broadcast arrives as int8 / Sum.)
+  if (first && !c->plan_pending && (func == mccsFuncBoadcast || func == mccsFuncReduce) && op <= mccsDevMin &&
+      (rooted_takes_ll(c, func, bytes) || rooted_takes_oneshot(c, func, bytes))) {
+    c->plan_direct = true;
+    c->direct.send = send;
+    c->direct.recv = recv;
+    c->direct.count = count;
+    c->direct.root = root;
     c->plan_pending = true;
     c->plan_func = func;
     c->plan_dtype = dtype;
@@ -577,6 +621,7 @@ mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send
     c->direct.send = send;
     c->direct.recv = recv;
     c->direct.count = count;
+    c->direct.root = 0;
     c->plan_pending = true;
     c->plan_func = func;
     c->plan_dtype = dtype;
@@ -937,7 +982,10 @@ static bool direct_group(std::vector<Comm*>& comms, const std::vector<int>& idx)
         ck->layout.ll_slot != c0->layout.ll_slot || ck->cfg.ll_bytes != c0->cfg.ll_bytes ||
         ck->cfg.oneshot_bytes != c0->cfg.oneshot_bytes || ck->cfg.direct_bytes != c0->cfg.direct_bytes ||
         ck->nch != c0->nch || ck->peer_arena != c0->peer_arena ||  // one region table for every slot
-        ck->rs_direct_bytes != c0->rs_direct_bytes || ck->rs_ll_bytes != c0->rs_ll_bytes)
+        ck->rs_direct_bytes != c0->rs_direct_bytes || ck->rs_ll_bytes != c0->rs_ll_bytes ||
+        ck->bc_direct_bytes != c0->bc_direct_bytes || ck->bc_ll_bytes != c0->bc_ll_bytes ||
+        ck->rd_direct_bytes != c0->rd_direct_bytes || ck->rd_ll_bytes != c0->rd_ll_bytes ||
+        ck->direct.root != c0->direct.root)  // one root for every rank slot (mccsDirectArgs.root)
       return false;
   }
   return idx.size() <= MCCS_MULTI_MAX_RANKS;
@@ -1071,10 +1119,12 @@ static mccsResult_t build_direct(std::vector<Comm*>& comms, const std::vector<in
 // over the instantiations), as coresident_direct_blocks.  Probed when a comm
 // opts in (rs_direct_prepare), not at its first launch: that launch may be
 // one a stream is capturing.
-static int coresident_rs_blocks(int device, int* ncu_out) {
+// `rooted`: the direct Broadcast / Reduce kernels (direct_rooted.h) instead,
+// cached apart, so opting in to them changes no ReduceScatter launch.
+static int coresident_rs_blocks(int device, int* ncu_out, bool rooted = false) {
   static std::mutex mu;
-  static std::map<std::pair<unsigned, int>, std::pair<int, int>> cache;  // (runtime, device) -> (blocks, CUs)
-  const auto key = std::make_pair(rt_generation(), device);
+  static std::map<std::tuple<unsigned, int, bool>, std::pair<int, int>> cache;  // (runtime, device, family) -> (blocks, CUs)
+  const auto key = std::make_tuple(rt_generation(), device, rooted);
   {
     std::lock_guard<std::mutex> lk(mu);
     auto it = cache.find(key);
@@ -1090,10 +1140,15 @@ static int coresident_rs_blocks(int device, int* ncu_out) {
   for (int dt = 0; dt < mccsNumTypes; ++dt)
     for (int op = 0; op < 4; ++op) {
       int per_cu = 0;
-      const void* fn = direct_rs_kernel_ptr(dt, op);
+      const void* fn = rooted ? direct_rd_kernel_ptr(dt, op) : direct_rs_kernel_ptr(dt, op);
       if (!fn || rt().BlocksPerCu(&per_cu, fn, MCCS_DIRECT_THREADS) != hipSuccess) return 0;  // not cached
       best = std::min(best, per_cu);
     }
+  if (rooted) {
+    int per_cu = 0;
+    if (rt().BlocksPerCu(&per_cu, direct_bc_kernel_ptr(), MCCS_DIRECT_THREADS) != hipSuccess) return 0;
+    best = std::min(best, per_cu);
+  }
   std::lock_guard<std::mutex> lk(mu);
   cache[key] = {best * ncu, ncu};
   *ncu_out = ncu;
@@ -1103,6 +1158,8 @@ static int coresident_rs_blocks(int device, int* ncu_out) {
 void rs_direct_prepare(const Comm* c) {
   int ncu = 0;
   if (c->rs_direct_bytes > 0 || c->rs_ll_bytes > 0) (void)coresident_rs_blocks(c->device, &ncu);
+  if (c->bc_direct_bytes > 0 || c->bc_ll_bytes > 0 || c->rd_direct_bytes > 0 || c->rd_ll_bytes > 0)
+    (void)coresident_rs_blocks(c->device, &ncu, /*rooted=*/true);
 }
 
 // The direct ReduceScatter launch's arguments (direct_group checked the
@@ -1181,6 +1238,105 @@ static mccsResult_t build_direct_rs(std::vector<Comm*>& comms, const std::vector
   if (g * (long)idx.size() > cap)
     MCCS_FAIL(mccsInvalidUsage, "direct ReduceScatter launch of %zu ranks x %ld workgroups exceeds the %d co-resident "
               "ones of device %d", idx.size(), g, cap, c0->device);
+  *grid_x = (unsigned)g;
+  // pieces: each phase's bytes over the workgroups, in 4 KiB steps, 4..64 KiB
+  auto piece = [&](size_t phase_bytes) {
+    size_t p = (phase_bytes + (size_t)g - 1) / (size_t)g;
+    p = std::min<size_t>(std::max<size_t>((p + 4095) & ~(size_t)4095, 4096), 65536);
+    return (uint32_t)(p / esize);
+  };
+  da->piece = piece(scatter);
+  da->piece2 = piece(nbytes);
+  for (size_t k = 0; k < idx.size(); ++k) {
+    Comm* ck = comms[idx[k]];
+    ck->plan_direct = false;
+    ck->plan_pending = false;
+  }
+  return mccsSuccess;
+}
+
+// The direct Broadcast / Reduce launch's arguments (direct_group checked the
+// shape, the root included): as build_direct_rs, with the whole buffer where
+// that has a block.  Reduce: the ring walk the call would take (ring_enqueue:
+// total = the buffer's bytes).  Broadcast moves bytes and folds nothing; it
+// carries the walk ring_enqueue would have picked all the same, for the record.
+static mccsResult_t build_direct_rooted(std::vector<Comm*>& comms, const std::vector<int>& idx, mccsDirectArgs* da,
+                                        unsigned* grid_x) {
+  const Comm* c0 = comms[idx[0]];
+  const int func = c0->plan_func;
+  const bool bc = func == mccsFuncBoadcast;
+  const size_t esize = (size_t)elem_bytes(c0->plan_dtype);  // Broadcast: int8
+  const int n = c0->nranks;
+  const size_t nbytes = c0->direct.count * esize;  // the whole buffer
+  int nch = 0, nthr = 0;
+  task_schema(nbytes, c0->nch, &nch, &nthr);
+  int chans[MCCS_MAX_NCHANNELS];
+  const int nsel = select_channels(c0, nch, chans);
+  std::memset(da, 0, sizeof(*da));
+  da->count = c0->direct.count;
+  da->root = (uint32_t)c0->direct.root;
+  da->slot_bytes = c0->layout.direct_slot;
+  da->oslot_bytes = c0->layout.oneshot_slot;
+  da->ll_slot_bytes = c0->layout.ll_slot;
+  bool ll = true, oneshot = true;  // every rank slot of the launch must take it
+  for (size_t k = 0; k < idx.size(); ++k) {
+    ll = ll && rooted_takes_ll(comms[idx[k]], func, nbytes);
+    oneshot = oneshot && rooted_takes_oneshot(comms[idx[k]], func, nbytes);
+  }
+  if (!ll && !oneshot) return mccsInternalError;  // plan_enqueue held it for one of them
+  if (c0->direct.root < 0 || c0->direct.root >= n) return mccsInternalError;  // api.cpp checked the range
+  da->mode = bc ? (ll ? MCCS_DIRECT_BC_LL : MCCS_DIRECT_BC_ONE_SHOT) : (ll ? MCCS_DIRECT_RD_LL : MCCS_DIRECT_RD_ONE_SHOT);
+  da->nranks = (uint32_t)n;
+  da->nch = (uint32_t)nsel;
+  da->nthr_ref = (uint32_t)nthr;
+  da->buff_size = (uint32_t)c0->cfg.buffer_size;
+  da->fence_mode = c0->kcfg.fence_mode;
+  da->timeout_ticks = c0->kcfg.timeout_ticks;
+  for (int bid = 0; bid < nsel; ++bid) {
+    const std::vector<int>& ring = c0->rings[chans[bid]];
+    const int pos0 = (int)(std::find(ring.begin(), ring.end(), 0) - ring.begin());
+    for (int k = 0; k < n; ++k) da->idx2rank[bid][k] = (uint8_t)ring[(pos0 + k) % n];
+  }
+  for (size_t k = 0; k < idx.size(); ++k) {
+    const Comm* ck = comms[idx[k]];
+    mccsDirectRank& r = da->r[k];
+    r.send = ck->direct.send;
+    r.recv = ck->direct.recv;
+    for (int t = 0; t < n; ++t) {
+      if (!ck->peer_arena[t]) return mccsInternalError;
+      if (k == 0) da->region[t] = ck->peer_arena[t] + ck->layout.direct_off();
+      else if (da->region[t] != ck->peer_arena[t] + ck->layout.direct_off()) return mccsInternalError;  // direct_group
+    }
+    r.comm = (mccsDevComm*)ck->d_comm;
+    r.abort_flag = ck->d_abort;
+    r.rank = (uint32_t)ck->rank;
+    r.err_line = 1;
+    // safest hand-off of the group, as for the ring (SYSTEM > UNCACHED_RELEASE > UNCACHED)
+    if (ck->kcfg.fence_mode == MCCS_FENCE_SYSTEM) da->fence_mode = MCCS_FENCE_SYSTEM;
+    else if (ck->kcfg.fence_mode == MCCS_FENCE_UNCACHED_RELEASE && da->fence_mode == MCCS_FENCE_UNCACHED)
+      da->fence_mode = MCCS_FENCE_UNCACHED_RELEASE;
+    da->timeout_ticks = (da->timeout_ticks == 0 || ck->kcfg.timeout_ticks == 0)
+                            ? 0
+                            : std::max(da->timeout_ticks, ck->kcfg.timeout_ticks);
+  }
+  // Workgroups from the busiest rank's data phase: the root's n-1 copies
+  // (Broadcast) or one buffer (a Reduce sender; the root's fold reads as
+  // much): ~4 KiB each, or (LL) one 8-byte word per thread (a Broadcast root
+  // writes a word to every peer from one thread); capped by co-residency as
+  // build_direct_rs caps its launches.
+  const size_t scatter = bc ? nbytes * (size_t)(n - 1) : nbytes;
+  int ncu = 0;
+  const int cap = coresident_rs_blocks(c0->device, &ncu, /*rooted=*/true);
+  if (ncu <= 0) ncu = cap;
+  long g = std::min<long>((long)((scatter + 4095) / 4096), c0->direct_blocks);
+  if (ll)
+    g = std::min<long>((long)(((nbytes + 7) / 8 + MCCS_DIRECT_THREADS - 1) / MCCS_DIRECT_THREADS), c0->direct_blocks);
+  if (idx.size() > 1) g = std::min<long>(g, std::min(cap, ncu) / (long)idx.size());  // one fused launch
+  else if (c0->share > 1) g = std::min<long>(g, std::min(cap / 2, ncu) / c0->share);  // separate processes
+  g = std::max<long>(g, 1);
+  if (g * (long)idx.size() > cap)
+    MCCS_FAIL(mccsInvalidUsage, "direct %s launch of %zu ranks x %ld workgroups exceeds the %d co-resident ones of "
+              "device %d", bc ? "Broadcast" : "Reduce", idx.size(), g, cap, c0->device);
   *grid_x = (unsigned)g;
   // pieces: each phase's bytes over the workgroups, in 4 KiB steps, 4..64 KiB
   auto piece = [&](size_t phase_bytes) {
@@ -1391,6 +1547,11 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
       if (c0->plan_func == mccsFuncReduceScatter) {
         MCCS_CHECK(build_direct_rs(comms, idx, &da, &grid));
         fn = direct_rs_kernel_ptr(c0->plan_dtype, c0->plan_op);
+      } else if (c0->plan_func == mccsFuncBoadcast || c0->plan_func == mccsFuncReduce) {
+        const bool bc = c0->plan_func == mccsFuncBoadcast;  // before the build clears the plan
+        const int dt = c0->plan_dtype, op = c0->plan_op;
+        MCCS_CHECK(build_direct_rooted(comms, idx, &da, &grid));
+        fn = bc ? direct_bc_kernel_ptr() : direct_rd_kernel_ptr(dt, op);
       } else {
         MCCS_CHECK(build_direct(comms, idx, &da, &grid));
         fn = c0->plan_func == mccsFuncAllGather ? direct_kernel_ptr(mccsInt8, mccsDevSum)
@@ -1516,7 +1677,8 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
                                  : !direct                          ? MCCS_ALGO_RING
                                  : da.mode == MCCS_DIRECT_TWO_SHOT ? MCCS_ALGO_DIRECT
                                  : da.mode == MCCS_DIRECT_LL_ONE_SHOT || da.mode == MCCS_DIRECT_LL_AG ||
-                                           da.mode == MCCS_DIRECT_RS_LL
+                                           da.mode == MCCS_DIRECT_RS_LL || da.mode == MCCS_DIRECT_RD_LL ||
+                                           da.mode == MCCS_DIRECT_BC_LL
                                      ? MCCS_ALGO_LL
                                      : MCCS_ALGO_ONESHOT;
     }

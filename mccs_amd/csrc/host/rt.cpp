@@ -400,7 +400,9 @@ class FakeRuntime final : public DeviceRuntime {
     bool direct = false;
     for (int dt = 0; dt < mccsNumTypes && fn; ++dt)
       for (int op = 0; op < 4; ++op)
-        direct = direct || fn == direct_kernel_ptr(dt, op) || fn == direct_rs_kernel_ptr(dt, op);
+        direct = direct || fn == direct_kernel_ptr(dt, op) || fn == direct_rs_kernel_ptr(dt, op) ||
+                 fn == direct_rd_kernel_ptr(dt, op);
+    direct = direct || (fn && fn == direct_bc_kernel_ptr());
     const bool a2all = fn && fn == a2a_ll_kernel_ptr();
     if (fn && args && grid.y >= 1 && grid.y <= MCCS_MULTI_MAX_RANKS) {
       if (a2all) {
@@ -440,6 +442,10 @@ class FakeRuntime final : public DeviceRuntime {
                             : da->mode == MCCS_DIRECT_LL_AG       ? "ll-ag"
                             : da->mode == MCCS_DIRECT_RS_ONE_SHOT ? "rs-oneshot"
                             : da->mode == MCCS_DIRECT_RS_LL       ? "rs-ll"
+                            : da->mode == MCCS_DIRECT_RD_ONE_SHOT ? "rd-oneshot"
+                            : da->mode == MCCS_DIRECT_RD_LL       ? "rd-ll"
+                            : da->mode == MCCS_DIRECT_BC_ONE_SHOT ? "bc-oneshot"
+                            : da->mode == MCCS_DIRECT_BC_LL       ? "bc-ll"
                                                                   : "twoshot") +
                 " gx=" + std::to_string(grid.x) + " llslot=" + std::to_string(da->ll_slot_bytes) +
                 " piece=" + std::to_string(da->piece) + " piece2=" + std::to_string(da->piece2) +
@@ -448,7 +454,9 @@ class FakeRuntime final : public DeviceRuntime {
         for (unsigned t = 0; t < da->nranks && t < MCCS_DIRECT_MAX_RANKS; ++t)
           extra += (t ? "," : "") + std::to_string(da->owned[t]);
         // a direct ReduceScatter also names its rank slots: rank:send:recv (hex), '/' between them
-        if (da->mode == MCCS_DIRECT_RS_ONE_SHOT || da->mode == MCCS_DIRECT_RS_LL) {
+        const bool rooted_mode = da->mode >= MCCS_DIRECT_RD_ONE_SHOT && da->mode <= MCCS_DIRECT_BC_LL;
+        if (rooted_mode) extra += " root=" + std::to_string(da->root);  // a direct Broadcast / Reduce names its root
+        if (da->mode == MCCS_DIRECT_RS_ONE_SHOT || da->mode == MCCS_DIRECT_RS_LL || rooted_mode) {
           extra += " slots=";
           for (unsigned k = 0; k < grid.y; ++k) {
             char hex[64];
@@ -561,7 +569,9 @@ class FakeRuntime final : public DeviceRuntime {
     if (!fn || !args || grid.y < 1 || grid.y > MCCS_MULTI_MAX_RANKS) return;
     for (int dt = 0; dt < mccsNumTypes; ++dt)
       for (int op = 0; op < 4; ++op)
-        if (fn == direct_kernel_ptr(dt, op) || fn == direct_rs_kernel_ptr(dt, op)) return;
+        if (fn == direct_kernel_ptr(dt, op) || fn == direct_rs_kernel_ptr(dt, op) || fn == direct_rd_kernel_ptr(dt, op))
+          return;
+    if (fn == direct_bc_kernel_ptr()) return;
     if (fn == a2a_ll_kernel_ptr()) return;
     const mccsMultiLaunchArgs* ma = (const mccsMultiLaunchArgs*)args[0];
     if (ma->inline_works) return;

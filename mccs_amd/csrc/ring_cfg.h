@@ -272,6 +272,41 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 // own writes of L+1; and a rank's launch L+1 starts only after its launch L
 // ended (stream order between eager launches, the launch guard between graph
 // replays), i.e. after it finished reading parity p.
+//
+// Direct Broadcast and Reduce (direct_rooted.h, opt-in:
+// mccsCommSetRootedDirect) use the same region and state and add no slot:
+//   Reduce: sender s != root writes its input into the root's one-shot slot
+//     [parity][sender s] at the element offset, or word w into line w of the
+//     root's LL slot [parity][sender s]; the root folds as a direct
+//     ReduceScatter owner folds its block (the whole buffer is the block);
+//   Broadcast: the root writes its bytes into every peer t's one-shot slot
+//     [parity][root], or word w into line w of t's LL slot [parity][root].
+// Data moves on n-1 of the n(n-1) ordered pairs only, and that alone would
+// break both facts the argument above rests on: the pairs without data would
+// not hand off (after a Reduce to root 0 and a Reduce to root 1 nothing would
+// stop rank 2 from overwriting a slot rank 0 is still reading), and senders
+// would have sent a receiver different amounts (the single E_IN word would no
+// longer be every line's running total).  So a rooted launch keeps both facts
+// by rule.  With the launch's common amount A (count elements for Reduce,
+// nbytes for Broadcast):
+//   count-based: EVERY rank adds A to IN_CNT(self) of EVERY peer -- summed
+//     over its workgroups' pieces where the pair carries data, by one add of
+//     workgroup 0 where it carries none; E_IN advances by A on EVERY rank; and
+//     on EVERY rank, root or not, workgroup 0 waits for E_IN + A on every
+//     peer's line before the kernel ends;
+//   LL: EVERY rank writes line 0, flagged with this launch's seq, into EVERY
+//     peer's LL slot for itself (a dummy word where the pair carries no
+//     data), and on EVERY rank global thread 0 polls line 0 of every peer's
+//     slot before the kernel ends.
+// Then every ordered pair (s, t) hands off in every launch and every sender
+// sends every receiver the same amount, and the ReduceScatter paragraph holds
+// word for word: s cannot finish launch L+1 -- and start writing parity p
+// again in L+2 -- before t made its hand-off of L+1, which t makes only after
+// its launch L ended, i.e. after it finished reading parity p; and E_IN stays
+// the running total of every line.  This holds across any mix of rooted,
+// ReduceScatter, AllReduce, AllGather and all-to-all direct launches, and
+// under every change of root between launches: the rule does not mention the
+// root.
 #define MCCS_DIRECT_MAX_RANKS 8
 #define MCCS_DIRECT_CTRL_BYTES 65536
 // u64, added to by sender s; a rank's own line IN_CNT(rank) counts its own
@@ -298,6 +333,11 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 // direct ReduceScatter (direct_rs.h; count = recvcount, the elements of one block)
 #define MCCS_DIRECT_RS_ONE_SHOT 5  // through the one-shot slots, counted on IN_CNT
 #define MCCS_DIRECT_RS_LL 6        // through the LL lines
+// direct Reduce and Broadcast (direct_rooted.h; count = the buffer's elements / bytes, root = the root)
+#define MCCS_DIRECT_RD_ONE_SHOT 7  // Reduce through the root's one-shot slots, counted on IN_CNT
+#define MCCS_DIRECT_RD_LL 8        // Reduce through the root's LL lines
+#define MCCS_DIRECT_BC_ONE_SHOT 9  // Broadcast through every peer's one-shot slot for the root
+#define MCCS_DIRECT_BC_LL 10       // Broadcast through every peer's LL lines for the root
 
 struct mccsDirectRank {  // one rank slot of a direct launch (blockIdx.y)
   const void* send;
@@ -320,11 +360,11 @@ struct mccsDirectArgs {
   uint64_t timeout_ticks;  // s_memrealtime ticks; 0 = never
   uint32_t nranks, nch, nthr_ref, buff_size;  // the ring walk this launch reproduces
   uint32_t fence_mode;                        // MCCS_FENCE_*
-  uint32_t mode;                              // MCCS_DIRECT_* above (the RS modes: direct_rs_kernel only)
+  uint32_t mode;                              // MCCS_DIRECT_* above (RS: direct_rs_kernel only; RD / BC: direct_rooted.h's kernels only)
   uint32_t piece;                             // elements per piece of the scatter / gather phases
   uint32_t piece2;                            // elements per piece of the reduction phase
   uint32_t no_guard;                          // 1: skip the launch guard (test hook only)
-  uint32_t pad2;
+  uint32_t root;                              // the RD / BC modes: the root (one for all rank slots); else 0
   uint64_t guard_order;                       // rank slots by guard address, 4 bits each (launch_guard.h)
   uint64_t owned[MCCS_DIRECT_MAX_RANKS];      // elements of the walk's chunks each rank owns
   uint8_t idx2rank[MCCS_MAX_NCHANNELS][MCCS_DIRECT_MAX_RANKS];  // rank at ring index k of channel bid

@@ -13,6 +13,12 @@ sync) and graph-replayed (20 calls per graph).
 ReduceScatter per block size (1 KiB to the caps by default): the ring (limits
 0), the direct and the LL variant (mccsCommSetReduceScatterDirect) and the
 one-shot AllGather of the same bytes per rank beside them.
+  python tools/direct_bench.py --rooted [--n 2 4 8] [--sizes-kib 1 4 ...] [--regions 5]
+Broadcast and Reduce per buffer size: the ring (limits 0) against the
+count-based and the LL variant (mccsCommSetRootedDirect at the caps), the root
+rotating on every call.  Every variant is warmed up, then timed in --regions
+regions of --calls calls each, the variants alternating region by region; a
+row holds the median and the min / max of the regions' us per call.
 """
 import argparse
 import json
@@ -101,6 +107,71 @@ def reduce_scatter_mode(args, torch, C, st, dt, code, es):
           flush=True)
 
 
+def rooted_mode(args, torch, C, st, dt, code, es):
+    """--rooted: Broadcast and Reduce of one buffer size, ring / count-based / LL."""
+    import statistics
+
+    top = 1 << 20
+    sizes = args.sizes_kib if args.sizes_kib != DEFAULT_SIZES_KIB else [1, 4, 16, 64, 256, 1024]
+    rows = []
+    for n in args.n:
+        cfg = C.CommConfig(direct_bytes=-1, oneshot_bytes=top, ll_bytes=top)
+        sets = {"ring": C.init_all([0] * n, cfg), "direct": C.init_all([0] * n, cfg), "ll": C.init_all([0] * n, cfg)}
+        cap, ll_cap = sets["direct"][0].rooted_direct_max()
+        for c in sets["direct"]:
+            c.set_rooted_direct(bcast_bytes=cap, reduce_bytes=cap)
+        for c in sets["ll"]:
+            c.set_rooted_direct(bcast_ll_bytes=ll_cap, reduce_ll_bytes=ll_cap)
+        want = {"ring": "ring", "direct": "oneshot", "ll": "ll"}
+        for kib in sizes:
+            nbytes = kib << 10
+            cnt = nbytes // es
+            xs = [torch.randn(cnt, device="cuda").to(dt) for _ in range(n)]
+            ys = [torch.empty(cnt, dtype=dt, device="cuda") for _ in xs]
+            for func in ("broadcast", "reduce"):
+                row = {"n": n, "func": func, "bytes": nbytes, "cap": cap, "ll_cap": ll_cap}
+                live = [a for a in sets if not (a == "direct" and nbytes > cap) and not (a == "ll" and nbytes > ll_cap)]
+                turn = {a: 0 for a in live}
+
+                def once(algo):
+                    root = turn[algo] % n  # the root rotates on every call
+                    turn[algo] += 1
+                    with C.group():
+                        for r, c in enumerate(sets[algo]):
+                            if func == "broadcast":
+                                C.broadcast(c, xs[r] if r == root else None, ys[r], nbytes, root, stream=st)
+                            else:
+                                C.reduce(c, xs[r], ys[r] if r == root else None, cnt, code, 0, root, stream=st)
+
+                for a in live:  # warm-up: every kernel's code object, every root
+                    for _ in range(max(5, n)):
+                        once(a)
+                    st.synchronize()
+                    assert sets[a][0].last_algo() == want[a], (a, sets[a][0].last_algo())
+                us = {a: [] for a in live}
+                for _ in range(args.regions):
+                    for a in live:  # the variants alternate region by region
+                        t0 = time.perf_counter()
+                        for _ in range(args.calls):
+                            once(a)
+                        st.synchronize()
+                        us[a].append((time.perf_counter() - t0) / args.calls * 1e6)
+                for a in live:
+                    row[a + "_us"] = round(statistics.median(us[a]), 2)
+                    row[a + "_min_us"], row[a + "_max_us"] = round(min(us[a]), 2), round(max(us[a]), 2)
+                    for c in sets[a]:
+                        c.sync()
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+            del xs, ys
+        torch.cuda.synchronize()
+        for comms in sets.values():
+            for c in comms:
+                c.destroy()
+    print(json.dumps({"tool": "direct_bench", "collective": "rooted", "dtype": args.dtype, "calls": args.calls,
+                      "regions": args.regions, "rows": rows}), flush=True)
+
+
 DEFAULT_SIZES_KIB = [32, 128, 512, 2048, 8192, 32768]
 
 
@@ -123,6 +194,9 @@ def main():
     ap.add_argument("--reduce-scatter", action="store_true",
                     help="time ReduceScatter (size = bytes per block, 1 KiB to the caps): ring vs direct vs LL, and "
                          "the one-shot AllGather of the same bytes per rank")
+    ap.add_argument("--rooted", action="store_true",
+                    help="time Broadcast and Reduce (size = the buffer, 1 KiB to the caps): ring vs count-based vs LL")
+    ap.add_argument("--regions", type=int, default=5, help="--rooted: timed regions of --calls calls per variant")
     args = ap.parse_args()
     dt = getattr(torch, args.dtype)
     code = {torch.float16: 6, torch.float32: 7, torch.bfloat16: 9}[dt]
@@ -131,6 +205,9 @@ def main():
     st = side_stream(torch, 0, slot=1)
     if args.reduce_scatter:
         reduce_scatter_mode(args, torch, C, st, dt, code, es)
+        return
+    if args.rooted:
+        rooted_mode(args, torch, C, st, dt, code, es)
         return
     for n in args.n:
         top = max(args.sizes_kib) << 10
