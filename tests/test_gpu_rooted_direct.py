@@ -9,6 +9,9 @@ a communicator that never opted in.  Every test asserts last_algo(): "oneshot"
 for the count-based variant, "ll" for the LL one.  One-shot slots of 256 KiB
 and LL slots for 128 KiB buffers, so the caps are 65536 and 32768 fp32
 elements.
+Edge values, guarded footprints and seeded configurations and sequences:
+tests/test_gpu_rooted_direct_values.py, tests/test_gpu_footprint_direct.py,
+tests/test_gpu_direct_collectives_fuzz.py.
 """
 import numpy as np
 import pytest
