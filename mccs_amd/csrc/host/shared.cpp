@@ -62,8 +62,10 @@ extern "C" mccsResult_t mccsEventCreateShared(int device, void** event, void* ha
   hipEvent_t e = nullptr;
   MCCS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventInterprocess));
   hipIpcEventHandle_t h;
-  if (hipIpcGetEventHandle(&h, e) != hipSuccess) {
+  if (hipError_t err = hipIpcGetEventHandle(&h, e); err != hipSuccess) {
     (void)hipEventDestroy(e);
+    // recorded for the caller, and not left for a later launch to report
+    err_hip("hipIpcGetEventHandle(&h, e)", err, __FILE__, __LINE__);
     return mccsUnhandledCudaError;
   }
   std::memcpy(handle_out, &h, sizeof(h));

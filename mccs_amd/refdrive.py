@@ -16,14 +16,15 @@ gets can be timed and its results checked:
     "device" -- device memory of the owning GPU, shared with the peers over
       IPC: the xGMI connector that replaces the host-pinned SHM buffers
       (§8(f) 2);
-    "host"   -- the reference's own SHM memory: page-aligned host memory,
-      mlock'ed (transport/shm/buffer.rs:17-26) and registered mapped with
-      hipHostRegister + hipHostGetDevicePointer in every process that
-      touches it (cuda/alloc.rs:59-99, shm/transporter.rs:102-106).  The
+    "host"   -- the reference's own SHM memory: page-aligned pinned host
+      memory that the GPU maps (mlock'ed, transport/shm/buffer.rs:17-26, and
+      registered mapped there, cuda/alloc.rs:59-99, shm/transporter.rs:
+      102-106; allocated pinned and mapped here, hipHostMalloc, since not
+      every machine lets a GPU pin pages a process already has).  The
       reference service is one process, so a plain System.alloc suffices
-      there; the ranks here are processes, so each rank's segment is a POSIX
-      shared-memory object that its peers map too.  This is the deployment
-      an UNCHANGED Rust service runs;
+      there; the ranks here are processes, so each rank's segment is shared
+      with its peers over IPC.  This is the deployment an UNCHANGED Rust
+      service runs;
 * comm/device.rs:35-183 (CommDevResources::new, conn_info_to_dev):
   mccsDevCommAndChannels, per-channel peers arrays, userRanks,
   ring prev/next/index, abortFlag, workFifoDone (host-mapped,
@@ -69,6 +70,10 @@ ESIZE = {0: 1, 1: 1, 2: 4, 3: 4, 4: 8, 5: 8, 6: 2, 7: 4, 8: 8, 9: 2}
 _hip = None
 
 
+class _IpcMemHandle(ctypes.Structure):  # hipIpcMemHandle_t: hipIpcOpenMemHandle takes it by value
+    _fields_ = [("reserved", ctypes.c_ubyte * 64)]
+
+
 def hip() -> ctypes.CDLL:
     global _hip
     if _hip is None:
@@ -82,99 +87,62 @@ def hip() -> ctypes.CDLL:
         h.hipMalloc.argtypes = [ctypes.POINTER(vp), sz]
         h.hipFree.argtypes = [vp]
         h.hipSetDevice.argtypes = [ctypes.c_int]
-        h.hipHostRegister.argtypes = [vp, sz, ctypes.c_uint]
-        h.hipHostUnregister.argtypes = [vp]
+        h.hipIpcGetMemHandle.argtypes = [ctypes.POINTER(_IpcMemHandle), vp]
+        h.hipIpcOpenMemHandle.argtypes = [ctypes.POINTER(vp), _IpcMemHandle, ctypes.c_uint]
+        h.hipIpcCloseMemHandle.argtypes = [vp]
         _hip = h
     return _hip
 
 
-_libc = None
-
-
-def libc() -> ctypes.CDLL:
-    global _libc
-    if _libc is None:
-        c = ctypes.CDLL(None, use_errno=True)
-        vp, sz = ctypes.c_void_p, ctypes.c_size_t
-        c.shm_open.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_uint]
-        c.shm_unlink.argtypes = [ctypes.c_char_p]
-        c.ftruncate.argtypes = [ctypes.c_int, ctypes.c_long]
-        c.posix_fallocate.argtypes = [ctypes.c_int, ctypes.c_long, ctypes.c_long]
-        c.mmap.argtypes = [vp, sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long]
-        c.mmap.restype = vp
-        c.munmap.argtypes = [vp, sz]
-        c.mlock.argtypes = [vp, sz]
-        c.munlock.argtypes = [vp, sz]
-        c.close.argtypes = [ctypes.c_int]
-        _libc = c
-    return _libc
-
-
 PAGE = 4096
-hipHostRegisterMapped = 0x2
+hipHostMallocMapped = 0x2
+hipIpcMemLazyEnablePeerAccess = 0x1
 
 
 class HostSegment:
-    """One rank's SHM connector memory as the reference allocates it: page
-    aligned host memory, mlock'ed (buffer.rs:17-26: System.alloc + mlock),
-    registered mapped for the current device (DeviceHostMapped::register,
-    cuda/alloc.rs:59-99).  `create=True` makes the POSIX shm object (zeroed by
-    ftruncate); peers open it by name.  `dev` is the device address the
-    kernels use; `host` the CPU address."""
+    """One rank's SHM connector memory: page-aligned pinned host memory that
+    the GPU maps, zeroed, where the reference mlocks System.alloc pages and
+    registers them mapped (buffer.rs:17-26; DeviceHostMapped, cuda/alloc.rs:
+    59-99).  The memory is allocated pinned (hipHostMalloc mapped), not
+    registered after the fact: a virtual machine's GPU may refuse to pin
+    pages a process already has.  The owner (`handle=None`) allocates it and
+    exports `handle`, the 64 bytes of its hipIpcMemHandle_t; a peer opens that
+    handle.  `dev` is the device address the kernels use; `host` the CPU
+    address (the owner's only)."""
 
-    def __init__(self, name: str, nbytes: int, create: bool):
-        c = libc()
-        self.name, self.nbytes = name.encode(), (nbytes + PAGE - 1) // PAGE * PAGE
-        self.host = self.dev = None
-        self._fd, self._registered, self._locked, self._owner = -1, False, False, create
-        flags = (0o100 | 0o200 | 2) if create else 2  # O_CREAT|O_EXCL|O_RDWR / O_RDWR
-        self._fd = c.shm_open(self.name, flags, 0o600)
-        if self._fd < 0:
-            raise OSError(ctypes.get_errno(), f"shm_open({name})")
+    def __init__(self, nbytes: int, handle: bytes | None = None):
+        h = hip()
+        self.nbytes = (nbytes + PAGE - 1) // PAGE * PAGE
+        self.host = self.dev = self.handle = None
+        self._owner = handle is None
+        p = ctypes.c_void_p()
+        if not self._owner:
+            _ok(h.hipIpcOpenMemHandle(ctypes.byref(p), _IpcMemHandle.from_buffer_copy(handle),
+                                      hipIpcMemLazyEnablePeerAccess), "hipIpcOpenMemHandle(host segment)")
+            self.dev = p.value
+            return
+        _ok(h.hipHostMalloc(ctypes.byref(p), self.nbytes, hipHostMallocMapped), "hipHostMalloc(mapped)")
+        self.host = p.value
         try:
-            if create and c.ftruncate(self._fd, self.nbytes) != 0:
-                raise OSError(ctypes.get_errno(), "ftruncate")
-            # reserve the pages now: a full /dev/shm then fails here (ENOSPC)
-            # instead of a SIGBUS at the first touch of an unbacked page
-            if create:
-                rc = c.posix_fallocate(self._fd, 0, self.nbytes)
-                if rc != 0:
-                    raise OSError(rc, f"posix_fallocate({self.nbytes} bytes of /dev/shm)")
-            p = c.mmap(None, self.nbytes, 0x1 | 0x2, 0x01, self._fd, 0)  # PROT_READ|WRITE, MAP_SHARED
-            if p in (None, ctypes.c_void_p(-1).value):
-                raise OSError(ctypes.get_errno(), "mmap")
-            self.host = p
-            # mlock as the reference does; an ordinary user's RLIMIT_MEMLOCK
-            # may refuse it, and hipHostRegister pins the pages anyway
-            self._locked = c.mlock(p, self.nbytes) == 0
-            _ok(hip().hipHostRegister(p, self.nbytes, hipHostRegisterMapped), "hipHostRegister(mapped)")
-            self._registered = True
+            ctypes.memset(self.host, 0, self.nbytes)
             dp = ctypes.c_void_p()
-            _ok(hip().hipHostGetDevicePointer(ctypes.byref(dp), ctypes.c_void_p(p), 0), "hipHostGetDevicePointer")
-            self.dev = dp.value or p  # cuda/alloc.rs:80-82: fall back to the host address
+            _ok(h.hipHostGetDevicePointer(ctypes.byref(dp), p, 0), "hipHostGetDevicePointer")
+            self.dev = dp.value or self.host  # cuda/alloc.rs:80-82: fall back to the host address
+            out = _IpcMemHandle()
+            _ok(h.hipIpcGetMemHandle(ctypes.byref(out), p), "hipIpcGetMemHandle(host segment)")
+            self.handle = bytes(out.reserved)
         except Exception:
             self.close()
             raise
 
-    def unlink(self) -> None:
-        if self._owner:
-            libc().shm_unlink(self.name)
-            self._owner = False
-
     def close(self) -> None:
-        c = libc()
-        if self._registered:
-            hip().hipHostUnregister(ctypes.c_void_p(self.host))
-            self._registered = False
-        if self.host:
-            if self._locked:
-                c.munlock(ctypes.c_void_p(self.host), self.nbytes)
-            c.munmap(ctypes.c_void_p(self.host), self.nbytes)
-            self.host = None
-        if self._fd >= 0:
-            c.close(self._fd)
-            self._fd = -1
-        self.unlink()
+        """The owner frees the memory (after every peer closed its mapping);
+        a peer closes its mapping."""
+        if self._owner and self.host:
+            hip().hipHostFree(ctypes.c_void_p(self.host))
+        elif not self._owner and self.dev:
+            hip().hipIpcCloseMemHandle(ctypes.c_void_p(self.dev))
+        self.host = self.dev = None
 
 
 def _ok(rc: int, what: str) -> None:
@@ -492,20 +460,17 @@ class RefDrivenRank:
 
     def _init_host_connector(self, allgather) -> None:
         """Every rank's [SendBufMeta][RecvBufMeta][FIFO] x channels in host
-        memory (the reference SHM transport): this rank creates its segment,
-        then maps and registers every peer's.  Two exchanges, both joined by
-        every rank whatever fails locally: the names, then "all mapped" (after
-        which the names are unlinked; the mappings keep the memory)."""
-        import uuid
-
+        memory (the reference SHM transport): this rank allocates its segment,
+        then opens its ring neighbours'.  Two exchanges, both joined by every
+        rank whatever fails locally: the handles, then "all mapped"."""
         rank, n = self.rank, self.n
         nbytes = self.stride * self.nch
-        name, local_err = f"/mccs_refdrv_{uuid.uuid4().hex[:16]}_{rank}", None
+        local_err = None
         try:
-            self._segs.append(HostSegment(name, nbytes, create=True))
+            self._segs.append(HostSegment(nbytes))
         except Exception as e:  # noqa: BLE001
             local_err = e
-        names = allgather("" if local_err else name)
+        handles = allgather(b"" if local_err else self._segs[0].handle)
         self.base = [0] * n
         # only the ring neighbours' segments are touched (each channel's prev
         # and next): an 8-rank, 32-channel rank maps 2 of 7 peers' 128 MiB
@@ -513,7 +478,7 @@ class RefDrivenRank:
         for ring in self.rings:
             pos = ring.index(rank)
             neigh.update((ring[(pos + 1) % n], ring[(pos - 1) % n]))
-        if not local_err and all(names):
+        if not local_err and all(handles):
             try:
                 for r in range(n):
                     if r == rank:
@@ -521,14 +486,12 @@ class RefDrivenRank:
                         continue
                     if r not in neigh:
                         continue
-                    seg = HostSegment(names[r], nbytes, create=False)
+                    seg = HostSegment(nbytes, handles[r])
                     self._segs.append(seg)
                     self.base[r] = seg.dev
             except Exception as e:  # noqa: BLE001
                 local_err = e
-        oks = allgather(local_err is None and all(names))
-        for s in self._segs:
-            s.unlink()
+        oks = allgather(local_err is None and all(handles))
         if not all(oks):
             self.close()
             raise RuntimeError(f"reference-driven host connector setup failed ({local_err or 'on another rank'})")
@@ -747,13 +710,15 @@ class RefDrivenRank:
         for p in self._opened:
             self.lib.mccsMemCloseShared(self.device, ctypes.c_void_p(p))
         self._opened = []
-        # host connector: our mappings only (a peer's pages live on until its
-        # own close unmaps them; every name was unlinked after setup)
-        for s in self._segs:
+        # host connector: our mappings of the peers' segments; our own segment
+        # (the first) is freed after the barrier, like the device memory
+        for s in self._segs[1:]:
             s.close()
-        self._segs = []
         if barrier is not None:
             barrier()
+        for s in self._segs[:1]:
+            s.close()
+        self._segs = []
         if self._mine:
             self.lib.mccsMemFreeShared(self.device, ctypes.c_void_p(self._mine))
             self._mine = 0
@@ -790,7 +755,7 @@ def default_variants(world: int, default_rings, max_channels: int = 32) -> list[
     FIFO data at the sender (the reference SHM layout) or the receiver
     (`mccs.toml [shm] locality = receiver`, config only).  `fifo`: "device"
     (the xGMI connector: FIFOs in the owning GPU's HBM) or "host" (the
-    reference's own SHM memory, mlock'ed host pages registered mapped: what
+    reference's own SHM memory, pinned host pages mapped into the GPU: what
     an unchanged service allocates).  `max_channels` caps the budget where
     ranks share one GPU (a rehearsal: every rank's workgroups must be
     resident at once)."""

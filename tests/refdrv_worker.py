@@ -13,7 +13,7 @@ acks, get_task_schema and launch_plan: grid = #channels, 544-thread blocks).
 Each variant (reference ring with the FIFO at the sender, the reference
 default; a rotated ring override with the FIFO at the receiver; both again
 with every SendBufMeta / RecvBufMeta / FIFO in the reference's own SHM
-memory: mlock'ed host pages registered mapped, transport/shm/buffer.rs:17-26,
+memory: pinned host pages mapped into the GPU, transport/shm/buffer.rs:17-26,
 cuda/alloc.rs:59-99) runs four
 cases three times each on the same structures (conn->step persists across
 launches, prims_simple.h:318-319,461) and then 1100 back-to-back launches,

@@ -414,44 +414,66 @@ def test_reference_rings_are_the_engine_default():
 
 
 def test_host_segment_roundtrip_without_gpu(monkeypatch):
-    """The host connector's segment: shm_open + ftruncate (zeroed) + mmap +
-    mlock, registered through hipHostRegister (faked here: no GPU); a peer
-    opening the name sees the creator's bytes; the name is unlinked once
-    every rank mapped it."""
+    """The host connector's segment: whole pages allocated pinned and mapped
+    (hipHostMalloc, faked here: no GPU) and zeroed; a peer opening the
+    owner's IPC handle sees the owner's bytes; the peer closes its mapping,
+    the owner frees the memory, and a freed segment's handle opens no more."""
     import ctypes
-    import uuid
 
-    calls = []
+    calls, live = [], {}
 
     class FakeHip:
-        def hipHostRegister(self, p, n, flags):
-            calls.append(("reg", n, flags))
+        def hipHostMalloc(self, out, n, flags):
+            calls.append(("malloc", n, flags))
+            buf = (ctypes.c_char * n)()
+            ctypes.memset(buf, 0xEE, n)  # the segment's zeros are HostSegment's own
+            live[ctypes.addressof(buf)] = buf
+            out._obj.value = ctypes.addressof(buf)
             return 0
 
         def hipHostGetDevicePointer(self, out, p, flags):
             out._obj.value = p.value
             return 0
 
-        def hipHostUnregister(self, p):
-            calls.append(("unreg",))
+        def hipIpcGetMemHandle(self, out, p):
+            ctypes.memmove(ctypes.addressof(out._obj), b"FAKE" + p.value.to_bytes(8, "little") + bytes(52), 64)
+            return 0
+
+        def hipIpcOpenMemHandle(self, out, handle, flags):
+            raw = bytes(handle.reserved)
+            addr = int.from_bytes(raw[4:12], "little")
+            if raw[:4] != b"FAKE" or addr not in live or flags != refdrive.hipIpcMemLazyEnablePeerAccess:
+                return 1
+            calls.append(("open",))
+            out._obj.value = addr
+            return 0
+
+        def hipIpcCloseMemHandle(self, p):
+            calls.append(("close", p.value))
+            return 0
+
+        def hipHostFree(self, p):
+            calls.append(("free", p.value))
+            del live[p.value]
             return 0
 
     monkeypatch.setattr(refdrive, "hip", lambda: FakeHip())
-    name = f"/mccs_test_{uuid.uuid4().hex[:12]}"
-    a = refdrive.HostSegment(name, 3 * 4096 + 5, create=True)
+    a = refdrive.HostSegment(3 * 4096 + 5)
+    addr = a.host
     try:
-        assert a.nbytes == 4 * 4096 and a.dev == a.host
-        assert bytes((ctypes.c_char * 64).from_address(a.host)) == bytes(64)
+        assert a.nbytes == 4 * 4096 and a.dev == a.host and len(a.handle) == 64
+        assert bytes((ctypes.c_char * a.nbytes).from_address(a.host)) == bytes(a.nbytes)
         ctypes.memset(a.host + 4096, 0x5A, 16)
-        b = refdrive.HostSegment(name, 3 * 4096 + 5, create=False)
-        assert bytes((ctypes.c_char * 16).from_address(b.host + 4096)) == b"\x5a" * 16
-        a.unlink()
-        with pytest.raises(OSError):
-            refdrive.HostSegment(name, 4096, create=False)
+        b = refdrive.HostSegment(3 * 4096 + 5, a.handle)
+        assert b.host is None and b.handle is None
+        assert bytes((ctypes.c_char * 16).from_address(b.dev + 4096)) == b"\x5a" * 16
         b.close()
+        b.close()  # idempotent
     finally:
         a.close()
-    assert calls.count(("reg", 4 * 4096, refdrive.hipHostRegisterMapped)) == 2 and calls.count(("unreg",)) == 2
+    with pytest.raises(RuntimeError):
+        refdrive.HostSegment(4096, a.handle)
+    assert calls == [("malloc", 4 * 4096, refdrive.hipHostMallocMapped), ("open",), ("close", addr), ("free", addr)]
 
 
 # ---- redOpArg: PreMulSum's scalar / SumPostDiv's divisor, per work element ------------------
