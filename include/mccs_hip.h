@@ -536,6 +536,44 @@ mccsResult_t mccsCommReduceScatterDirectMax(mccsComm_t comm, size_t *cap, size_t
 mccsResult_t mccsCommSetRootedDirect(mccsComm_t comm, size_t bcast_bytes, size_t bcast_ll_bytes, size_t reduce_bytes,
                                      size_t reduce_ll_bytes);
 mccsResult_t mccsCommRootedDirectMax(mccsComm_t comm, size_t *cap, size_t *ll_cap);
+/* The wide-accumulate direct AllReduce, for mccsFloat16 and mccsBfloat16 with
+ * Sum or PreMulSum (mccsAvgOp of these dtypes maps to PreMulSum): every rank's
+ * input reaches every rank in one exchange of the direct region, is summed in
+ * binary32 in RANK order 0, 1, ..., n-1 and rounded to the dtype ONCE
+ * (DESIGN.md §3.4).  Per element: t_r = f32(x_r), or fl32(f32(x_r) * f32(s))
+ * for PreMulSum (two roundings, never a fused multiply-add); acc = t_0; acc =
+ * fl32(acc + t_r); out = T(acc), nearest even, denormals kept.  Every rank
+ * produces the same bits, whatever the rings, channels and kernel variant; THE
+ * BITS DIFFER FROM THE RING'S, which rounds to 16 bits after every addition,
+ * so a buffer's result changes at the opt-in limit: the stated price of opting
+ * in.  Opt-in per communicator; the three limits are bytes of
+ * the WHOLE BUFFER, all default to 0 = off, and with all three off every call
+ * plans exactly as without this entry point.  MCCS_AR_WIDE_LL_BYTES /
+ * MCCS_AR_WIDE_ONESHOT_BYTES / MCCS_AR_WIDE_BYTES in the environment set them
+ * when the communicator is created (clamped to the maxima below).
+ * mccsCommAllReduceWideMax: *ll_cap and *oneshot_cap, the direct
+ * ReduceScatter's two maxima over the whole buffer (ll_slot / 2; one one-shot
+ * slot); *twoshot_cap, one two-shot slot (direct_bytes rounded up to 64 KiB; 0
+ * without two-shot slots -- direct_bytes < 0, nranks outside 2..8 -- or
+ * without peer atomics).
+ * mccsCommSetAllReduceWide: a value above its maximum is refused with
+ * mccsInvalidArgument; a call while the communicator has a group open or a
+ * call pending, with mccsInvalidUsage.  EVERY RANK MUST SET THE SAME THREE
+ * VALUES: ranks that disagree pick different kernels for one call and stall
+ * until the watchdog; this is not detected.
+ * A qualifying mccsAllReduce / mccsAllReduceOpArg that is its communicator's
+ * only call of the launch takes the wide LL variant within ll_bytes
+ * (mccsCommLastAlgo reports MCCS_ALGO_WIDE_LL), else the wide one-shot within
+ * oneshot_bytes (MCCS_ALGO_WIDE_ONESHOT), else the wide two-shot within
+ * twoshot_bytes (MCCS_ALGO_WIDE_DIRECT); this is decided before the ring-order
+ * direct variants see the call.  A larger one, one sharing a group with a
+ * second call of the communicator (it goes to the ring, a PreMulSum with its
+ * scalar), every other dtype, Prod / Max / Min and SumPostDiv plan as before.
+ * In place is supported; ranks sharing a GPU are fused into one launch as
+ * always; the call may be captured into a HIP graph.  The node gate does not
+ * cover this path. */
+mccsResult_t mccsCommSetAllReduceWide(mccsComm_t comm, size_t ll_bytes, size_t oneshot_bytes, size_t twoshot_bytes);
+mccsResult_t mccsCommAllReduceWideMax(mccsComm_t comm, size_t *ll_cap, size_t *oneshot_cap, size_t *twoshot_cap);
 /* Send / Recv: grouped point-to-point (torch's batch_isend_irecv; the pieces of
  * a Gather or Scatter).  mccsSend moves count * elem_bytes(dtype) bytes from
  * sendbuff to rank `peer`, mccsRecv receives as many from rank `peer` into
@@ -665,11 +703,15 @@ mccsResult_t mccsCommInfo(mccsComm_t comm, int *info7);
 /* ring send order of channel ch (nranks ints). */
 mccsResult_t mccsCommRing(mccsComm_t comm, int ch, int *order);
 /* Algorithm of the comm's latest launch: MCCS_ALGO_RING, MCCS_ALGO_DIRECT
- * (two-shot), MCCS_ALGO_ONESHOT or MCCS_ALGO_LL (LL one-shot) (-1 before the first). */
+ * (two-shot), MCCS_ALGO_ONESHOT or MCCS_ALGO_LL (LL one-shot), or one of the
+ * wide-accumulate AllReduce variants (mccsCommSetAllReduceWide) (-1 before the first). */
 #define MCCS_ALGO_RING 0
 #define MCCS_ALGO_DIRECT 1
 #define MCCS_ALGO_ONESHOT 2
 #define MCCS_ALGO_LL 3
+#define MCCS_ALGO_WIDE_LL 4
+#define MCCS_ALGO_WIDE_ONESHOT 5
+#define MCCS_ALGO_WIDE_DIRECT 6
 int mccsCommLastAlgo(mccsComm_t comm);
 /* 1 when the comm may run the direct kernel: a direct region was configured
  * and every device of the communicator can perform atomics on every other's

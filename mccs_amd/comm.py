@@ -186,10 +186,12 @@ class Communicator:
         return out
 
     def last_algo(self) -> str | None:
-        """"ring", "direct" (two-shot) or "oneshot": the algorithm of the latest
-        launch (None before one)."""
+        """"ring", "direct" (two-shot), "oneshot" or "ll", or a wide-accumulate
+        variant ("wide-ll", "wide-oneshot", "wide-direct"): the algorithm of the
+        latest launch (None before one)."""
         a = _sig().mccsCommLastAlgo(self._h)
-        return {0: "ring", 1: "direct", 2: "oneshot", 3: "ll"}.get(a)
+        return {0: "ring", 1: "direct", 2: "oneshot", 3: "ll", 4: "wide-ll", 5: "wide-oneshot",
+                6: "wide-direct"}.get(a)
 
     def direct_enabled(self) -> bool:
         """Whether AllReduces may take the direct kernel (a direct region is
@@ -304,6 +306,28 @@ class Communicator:
                    "mccsCommRootedDirectMax")
         return int(cap.value), int(ll_cap.value)
 
+    def set_all_reduce_wide(self, ll_bytes: int = 0, oneshot_bytes: int = 0, twoshot_bytes: int = 0) -> None:
+        """mccsCommSetAllReduceWide: opts the communicator in to the
+        wide-accumulate direct AllReduce (0 = off, the default).  The three
+        limits are bytes of the whole buffer.  A Float16 / BFloat16 all_reduce
+        of Sum or PreMulSum (the average) that is the communicator's only call
+        of its launch is summed in binary32 in rank order and rounded once:
+        last_algo() == "wide-ll" within ll_bytes, else "wide-oneshot" within
+        oneshot_bytes, else "wide-direct" within twoshot_bytes.  The bits are
+        the same on every rank and differ from the ring's.  Every rank must set
+        the same three values, each at most its all_reduce_wide_max()."""
+        rc = _sig().mccsCommSetAllReduceWide(self._h, int(ll_bytes), int(oneshot_bytes), int(twoshot_bytes))
+        _lib.check(rc, "mccsCommSetAllReduceWide")
+
+    def all_reduce_wide_max(self) -> tuple[int, int, int]:
+        """mccsCommAllReduceWideMax: (ll_cap, oneshot_cap, twoshot_cap), the
+        largest buffer in bytes of each wide variant; 0 where one cannot be
+        used."""
+        ll_cap, cap, two_cap = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+        _lib.check(_sig().mccsCommAllReduceWideMax(self._h, ctypes.byref(ll_cap), ctypes.byref(cap),
+                                                   ctypes.byref(two_cap)), "mccsCommAllReduceWideMax")
+        return int(ll_cap.value), int(cap.value), int(two_cap.value)
+
     def all_to_all_route(self) -> dict:
         """The comm's AllToAll route (mccsCommAllToAllRoute): hops (1: every
         block goes straight to its ring successor; nranks - 1: relayed along the
@@ -401,8 +425,9 @@ def all_reduce(comm: Communicator, send_buf, recv_buf, size: int, data_type=AllR
     """libmccs::all_reduce (collectives.rs:75-138): stream-ordered, returns after launch.
     op_arg=None is mccsAllReduce (Sum / Prod / Max / Min); a value goes to
     mccsAllReduceOpArg, which also takes PreMulSum (op_arg: the scalar's bits,
-    red_op_arg()) and SumPostDiv (op_arg: the divisor) and always runs those
-    two on the ring."""
+    red_op_arg()) and SumPostDiv (op_arg: the divisor) and runs those two on
+    the ring, unless the communicator opted in with set_all_reduce_wide and
+    the call is a Float16 / BFloat16 PreMulSum within a wide limit."""
     if op_arg is None:
         rc = _sig().mccsAllReduce(_ptr(send_buf), _ptr(recv_buf), int(size), int(data_type), int(op_type),
                                   comm._h, _stream(stream))

@@ -17,7 +17,9 @@
 // Sum / Prod / Max / Min only: these kernels know neither PreMulSum's step on
 // the input nor SumPostDiv's on the finished value (dtypes.h pre_op / post_op),
 // so the planner sends those two ops to the ring at every size (plan.cpp
-// plan_enqueue); teaching the direct variants the two steps is left for later.
+// plan_enqueue).  The one exception is opt-in and not these kernels: the wide
+// AllReduce (direct_wide.h) carries PreMulSum for fp16 / bf16 in its binary32
+// accumulator, with bits of its own.
 //
 // One launch per device (blockIdx.y = rank slot when ranks share a GPU), G
 // workgroups per rank of MCCS_DIRECT_THREADS threads.  Each phase cuts the

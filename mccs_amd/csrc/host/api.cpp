@@ -960,6 +960,44 @@ extern "C" mccsResult_t mccsCommSetRootedDirect(mccsComm_t comm, size_t bcast_by
   return mccsSuccess;
 }
 
+extern "C" mccsResult_t mccsCommAllReduceWideMax(mccsComm_t comm, size_t* ll_cap, size_t* oneshot_cap,
+                                                 size_t* twoshot_cap) {
+  err_clear();
+  const Comm* c = (const Comm*)comm;
+  if (!c || !ll_cap || !oneshot_cap || !twoshot_cap)
+    MCCS_FAIL(mccsInvalidArgument, "mccsCommAllReduceWideMax: null communicator or output");
+  *ll_cap = c->connected ? rs_ll_cap(c) : 0;
+  *oneshot_cap = c->connected ? rs_direct_cap(c) : 0;
+  *twoshot_cap = c->connected ? ar_wide_cap(c) : 0;
+  return mccsSuccess;
+}
+
+extern "C" mccsResult_t mccsCommSetAllReduceWide(mccsComm_t comm, size_t ll_bytes, size_t oneshot_bytes,
+                                                 size_t twoshot_bytes) {
+  err_clear();
+  StepScope st("mccsCommSetAllReduceWide");
+  Comm* c = (Comm*)comm;
+  if (!c || !c->connected) MCCS_FAIL(mccsInvalidUsage, "the communicator is not connected");
+  if (g_group.depth > 0 || c->plan_pending)
+    MCCS_FAIL(mccsInvalidUsage, "the communicator has a group open or a call pending: set the limits between launches");
+  const size_t ll_cap = rs_ll_cap(c), cap = rs_direct_cap(c), two_cap = ar_wide_cap(c);
+  if (ll_bytes > ll_cap)
+    MCCS_FAIL(mccsInvalidArgument, "ll_bytes %zu is above the %zu bytes one buffer can move through an LL slot%s",
+              ll_bytes, ll_cap,
+              ll_cap ? "" : " (no LL slots, a cached arena or system-scope fences: the LL path is closed here)");
+  if (oneshot_bytes > cap)
+    MCCS_FAIL(mccsInvalidArgument, "oneshot_bytes %zu is above the %zu bytes of a one-shot slot%s", oneshot_bytes, cap,
+              cap ? "" : " (no one-shot slots or no peer atomics: the count-based path is closed here)");
+  if (twoshot_bytes > two_cap)
+    MCCS_FAIL(mccsInvalidArgument, "twoshot_bytes %zu is above the %zu bytes of a two-shot slot%s", twoshot_bytes,
+              two_cap, two_cap ? "" : " (no two-shot slots or no peer atomics: the two-shot path is closed here)");
+  c->ar_wide_ll_bytes = ll_bytes;
+  c->ar_wide_oneshot_bytes = oneshot_bytes;
+  c->ar_wide_bytes = twoshot_bytes;
+  ar_wide_prepare(c);
+  return mccsSuccess;
+}
+
 extern "C" mccsResult_t mccsCommAllToAllRoute(mccsComm_t comm, int* info2) {
   const Comm* c = (const Comm*)comm;
   if (!c || !info2) return mccsInvalidArgument;

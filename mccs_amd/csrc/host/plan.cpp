@@ -481,9 +481,11 @@ static mccsResult_t demote_direct(Comm* c) {
   if (!c->plan_direct) return mccsSuccess;
   c->plan_direct = false;
   c->plan_pending = false;
-  // (a held Broadcast / Reduce goes back with its root; every other held call has root 0, the default)
+  // (a held Broadcast / Reduce goes back with its root, a held wide PreMulSum with its scalar; every other
+  // held call has root 0 and op_arg 0, the defaults)
+  c->direct.wide = false;
   return ring_enqueue(c, c->plan_func, c->plan_dtype, c->plan_op, c->direct.send, c->direct.recv, c->direct.count,
-                      c->direct.root);
+                      c->direct.root, c->direct.op_arg);
 }
 
 // The LL one-shot needs an uncached arena: its lines are polled with
@@ -548,6 +550,34 @@ static bool rooted_takes_oneshot(const Comm* c, int func, size_t bytes) {
   return bytes <= (func == mccsFuncBoadcast ? c->bc_direct_bytes : c->rd_direct_bytes) && bytes <= rs_direct_cap(c);
 }
 
+// ---- wide direct AllReduce (direct_wide.h): the planner path ---------------------
+// LL and one-shot: the direct ReduceScatter's caps and conditions, with the
+// whole buffer where that has a block; two-shot: one two-shot slot holds the
+// buffer by element offset, and its counts are remote atomics.
+size_t ar_wide_cap(const Comm* c) { return c->direct_ok ? c->layout.direct_slot : 0; }
+
+void ar_wide_read_env(Comm* c) {
+  auto read = [&](const char* name, size_t cap) {
+    const char* v = std::getenv(name);
+    const long long x = v ? std::atoll(v) : 0;
+    return x > 0 ? std::min((size_t)x, cap) : (size_t)0;
+  };
+  c->ar_wide_ll_bytes = read("MCCS_AR_WIDE_LL_BYTES", rs_ll_cap(c));
+  c->ar_wide_oneshot_bytes = read("MCCS_AR_WIDE_ONESHOT_BYTES", rs_direct_cap(c));
+  c->ar_wide_bytes = read("MCCS_AR_WIDE_BYTES", ar_wide_cap(c));
+  ar_wide_prepare(c);
+}
+
+// The wide mode an fp16 / bf16 AllReduce of `bytes` takes on this comm (-1:
+// none): LL wins over one-shot, one-shot over two-shot.  Every rank sees the
+// same limits and the same call, so every rank decides alike.
+static int wide_mode(const Comm* c, size_t bytes) {
+  if (bytes <= c->ar_wide_ll_bytes && bytes <= rs_ll_cap(c)) return MCCS_DIRECT_WIDE_LL;
+  if (bytes <= c->ar_wide_oneshot_bytes && bytes <= rs_direct_cap(c)) return MCCS_DIRECT_WIDE_ONE_SHOT;
+  if (bytes <= c->ar_wide_bytes && bytes <= ar_wide_cap(c)) return MCCS_DIRECT_WIDE_TWO_SHOT;
+  return -1;
+}
+
 mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send, void* recv, size_t count,
                           int root, uint64_t op_arg) {
   if (c->plan_pending && (c->plan_func != func || c->plan_dtype != dtype || c->plan_op != op))
@@ -581,8 +611,30 @@ mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send
   // the count-based variants need them).  A Broadcast, Reduce or
   // ReduceScatter takes the ring unless its comm opted in (below):
   // the default direct variants are AllReduce / AllGather only.  So does a
-  // PreMulSum or SumPostDiv of any function and size: the direct kernels know
-  // neither the pre nor the post step.
+  // PreMulSum or SumPostDiv of any function and size: the ring-order direct
+  // kernels know neither the pre nor the post step.
+  // One fp16 / bf16 AllReduce of Sum or PreMulSum within an opt-in wide limit
+  // (all 0: never) is held for direct_wide_kernel with its scalar, before the
+  // ordinary direct hold below sees it; a second call demotes it to the ring
+  // (demote_direct above, which passes the scalar on).
+  c->direct.wide = false;
+  c->direct.op_arg = 0;
+  if (first && !c->plan_pending && func == mccsFuncAllReduce && (dtype == mccsFloat16 || dtype == mccsBfloat16) &&
+      (op == mccsDevSum || op == mccsDevPreMulSum) && c->nranks >= 2 && c->nranks <= MCCS_DIRECT_MAX_RANKS &&
+      count > 0 && wide_mode(c, bytes) >= 0) {
+    c->plan_direct = true;
+    c->direct.send = send;
+    c->direct.recv = recv;
+    c->direct.count = count;
+    c->direct.root = 0;
+    c->direct.wide = true;
+    c->direct.op_arg = op == mccsDevPreMulSum ? op_arg : 0;
+    c->plan_pending = true;
+    c->plan_func = func;
+    c->plan_dtype = dtype;
+    c->plan_op = op;
+    return mccsSuccess;
+  }
   // One ReduceScatter whose block is within an opt-in limit (both 0: never)
   // is held for direct_rs_kernel, as the comm's first and only call of the
   // launch; a second call demotes it (demote_direct above).
@@ -985,7 +1037,10 @@ static bool direct_group(std::vector<Comm*>& comms, const std::vector<int>& idx)
         ck->rs_direct_bytes != c0->rs_direct_bytes || ck->rs_ll_bytes != c0->rs_ll_bytes ||
         ck->bc_direct_bytes != c0->bc_direct_bytes || ck->bc_ll_bytes != c0->bc_ll_bytes ||
         ck->rd_direct_bytes != c0->rd_direct_bytes || ck->rd_ll_bytes != c0->rd_ll_bytes ||
-        ck->direct.root != c0->direct.root)  // one root for every rank slot (mccsDirectArgs.root)
+        ck->direct.root != c0->direct.root ||  // one root for every rank slot (mccsDirectArgs.root)
+        ck->ar_wide_ll_bytes != c0->ar_wide_ll_bytes || ck->ar_wide_oneshot_bytes != c0->ar_wide_oneshot_bytes ||
+        ck->ar_wide_bytes != c0->ar_wide_bytes || ck->direct.wide != c0->direct.wide ||
+        ck->direct.op_arg != c0->direct.op_arg)  // one scalar for every rank slot (mccsDirectArgs.op_arg)
       return false;
   }
   return idx.size() <= MCCS_MULTI_MAX_RANKS;
@@ -1354,6 +1409,129 @@ static mccsResult_t build_direct_rooted(std::vector<Comm*>& comms, const std::ve
   return mccsSuccess;
 }
 
+// Workgroups of the four wide AllReduce kernels the device holds at once (min
+// over them), as coresident_rs_blocks: probed when a comm opts in
+// (ar_wide_prepare), not at a launch a stream may be capturing.
+static int coresident_wide_blocks(int device, int* ncu_out) {
+  static std::mutex mu;
+  static std::map<std::pair<unsigned, int>, std::pair<int, int>> cache;  // (runtime, device) -> (blocks, CUs)
+  const auto key = std::make_pair(rt_generation(), device);
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = cache.find(key);
+    if (it != cache.end()) {
+      *ncu_out = it->second.second;
+      return it->second.first;
+    }
+  }
+  DeviceGuard g(device);
+  int ncu = 0;
+  if (rt().CuCount(&ncu, device) != hipSuccess) return 0;
+  int best = 1 << 30;
+  for (int dt : {(int)mccsFloat16, (int)mccsBfloat16})
+    for (int op : {(int)mccsDevSum, (int)mccsDevPreMulSum}) {
+      int per_cu = 0;
+      if (rt().BlocksPerCu(&per_cu, direct_wide_kernel_ptr(dt, op), MCCS_DIRECT_THREADS) != hipSuccess) return 0;  // not cached
+      best = std::min(best, per_cu);
+    }
+  std::lock_guard<std::mutex> lk(mu);
+  cache[key] = {best * ncu, ncu};
+  *ncu_out = ncu;
+  return best * ncu;
+}
+
+void ar_wide_prepare(const Comm* c) {
+  int ncu = 0;
+  if (c->ar_wide_ll_bytes > 0 || c->ar_wide_oneshot_bytes > 0 || c->ar_wide_bytes > 0)
+    (void)coresident_wide_blocks(c->device, &ncu);
+}
+
+// The wide AllReduce launch's arguments (direct_group checked the shape, the
+// scalar included).  No ring walk: nch / nthr_ref / idx2rank stay 0, the sum
+// runs in rank order.  owned[] is the two-shot's contiguous split
+// (MCCS_WIDE_SHARE); the one-shot and LL modes leave it 0.
+static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vector<int>& idx, mccsDirectArgs* da,
+                                      unsigned* grid_x) {
+  const Comm* c0 = comms[idx[0]];
+  const size_t esize = (size_t)elem_bytes(c0->plan_dtype);  // 2
+  const int n = c0->nranks;
+  const size_t nbytes = c0->direct.count * esize;
+  std::memset(da, 0, sizeof(*da));
+  da->count = c0->direct.count;
+  da->op_arg = c0->direct.op_arg;
+  da->slot_bytes = c0->layout.direct_slot;
+  da->oslot_bytes = c0->layout.oneshot_slot;
+  da->ll_slot_bytes = c0->layout.ll_slot;
+  const int mode = wide_mode(c0, nbytes);
+  for (size_t k = 0; k < idx.size(); ++k)  // every rank slot of the launch must take the same body
+    if (wide_mode(comms[idx[k]], nbytes) != mode) return mccsInternalError;
+  if (mode < 0) return mccsInternalError;  // plan_enqueue held it for one of them
+  da->mode = (uint32_t)mode;
+  const bool ll = mode == MCCS_DIRECT_WIDE_LL, oneshot = mode == MCCS_DIRECT_WIDE_ONE_SHOT;
+  da->nranks = (uint32_t)n;
+  da->buff_size = (uint32_t)c0->cfg.buffer_size;
+  da->fence_mode = c0->kcfg.fence_mode;
+  da->timeout_ticks = c0->kcfg.timeout_ticks;
+  if (mode == MCCS_DIRECT_WIDE_TWO_SHOT) {
+    const uint64_t q = MCCS_WIDE_SHARE((uint64_t)da->count, (uint64_t)n);
+    for (int t = 0; t < n; ++t) da->owned[t] = (uint64_t)t * q >= da->count ? 0 : std::min(q, da->count - (uint64_t)t * q);
+  }
+  for (size_t k = 0; k < idx.size(); ++k) {
+    const Comm* ck = comms[idx[k]];
+    mccsDirectRank& r = da->r[k];
+    r.send = ck->direct.send;
+    r.recv = ck->direct.recv;
+    for (int t = 0; t < n; ++t) {
+      if (!ck->peer_arena[t]) return mccsInternalError;
+      if (k == 0) da->region[t] = ck->peer_arena[t] + ck->layout.direct_off();
+      else if (da->region[t] != ck->peer_arena[t] + ck->layout.direct_off()) return mccsInternalError;  // direct_group
+    }
+    r.comm = (mccsDevComm*)ck->d_comm;
+    r.abort_flag = ck->d_abort;
+    r.rank = (uint32_t)ck->rank;
+    r.err_line = 1;
+    // safest hand-off of the group, as for the ring (SYSTEM > UNCACHED_RELEASE > UNCACHED)
+    if (ck->kcfg.fence_mode == MCCS_FENCE_SYSTEM) da->fence_mode = MCCS_FENCE_SYSTEM;
+    else if (ck->kcfg.fence_mode == MCCS_FENCE_UNCACHED_RELEASE && da->fence_mode == MCCS_FENCE_UNCACHED)
+      da->fence_mode = MCCS_FENCE_UNCACHED_RELEASE;
+    da->timeout_ticks = (da->timeout_ticks == 0 || ck->kcfg.timeout_ticks == 0)
+                            ? 0
+                            : std::max(da->timeout_ticks, ck->kcfg.timeout_ticks);
+  }
+  // Workgroups from phase 1 as build_direct sizes them: ~4 KiB each of the
+  // whole input (one-shot) or of the n-1 foreign shares (two-shot), or (LL)
+  // one 8-byte word per thread; capped by co-residency.
+  const size_t scatter = oneshot ? nbytes : nbytes - nbytes / (size_t)n;
+  int ncu = 0;
+  const int cap = coresident_wide_blocks(c0->device, &ncu);
+  if (ncu <= 0) ncu = cap;
+  long g = std::min<long>((long)((scatter + 4095) / 4096), c0->direct_blocks);
+  if (ll) g = std::min<long>((long)((nbytes + 8 * MCCS_DIRECT_THREADS - 1) / (8 * MCCS_DIRECT_THREADS)), c0->direct_blocks);
+  if (idx.size() > 1) g = std::min<long>(g, std::min(cap, ncu) / (long)idx.size());  // one fused launch
+  else if (c0->share > 1) g = std::min<long>(g, std::min(cap / 2, ncu) / c0->share);  // separate processes
+  g = std::max<long>(g, 1);
+  if (g * (long)idx.size() > cap)
+    MCCS_FAIL(mccsInvalidUsage, "wide AllReduce launch of %zu ranks x %ld workgroups exceeds the %d co-resident ones of "
+              "device %d", idx.size(), g, cap, c0->device);
+  *grid_x = (unsigned)g;
+  // pieces: each phase's bytes over the workgroups, in 4 KiB steps (pieces
+  // start on 16-byte packs), 4..64 KiB
+  auto piece = [&](size_t phase_bytes) {
+    size_t p = (phase_bytes + (size_t)g - 1) / (size_t)g;
+    p = std::min<size_t>(std::max<size_t>((p + 4095) & ~(size_t)4095, 4096), 65536);
+    return (uint32_t)(p / esize);
+  };
+  da->piece = piece(scatter);
+  da->piece2 = piece(oneshot ? nbytes : nbytes / (size_t)n + 1);
+  for (size_t k = 0; k < idx.size(); ++k) {
+    Comm* ck = comms[idx[k]];
+    ck->plan_direct = false;
+    ck->plan_pending = false;
+    ck->direct.wide = false;
+  }
+  return mccsSuccess;
+}
+
 // Workgroups of the LL all-to-all kernel the device holds at once: its launch
 // spins on peers' lines like a direct launch.  Probed only on this path.
 static int coresident_a2all_blocks(int device, int* ncu_out) {
@@ -1544,7 +1722,11 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
       for (int i : idx) la.no_guard |= comms[i]->kcfg.no_guard;
       args[0] = &la;
     } else if (direct) {
-      if (c0->plan_func == mccsFuncReduceScatter) {
+      if (c0->direct.wide) {
+        const int dt = c0->plan_dtype, op = c0->plan_op;  // before the build clears the plan
+        MCCS_CHECK(build_direct_wide(comms, idx, &da, &grid));
+        fn = direct_wide_kernel_ptr(dt, op);
+      } else if (c0->plan_func == mccsFuncReduceScatter) {
         MCCS_CHECK(build_direct_rs(comms, idx, &da, &grid));
         fn = direct_rs_kernel_ptr(c0->plan_dtype, c0->plan_op);
       } else if (c0->plan_func == mccsFuncBoadcast || c0->plan_func == mccsFuncReduce) {
@@ -1675,6 +1857,9 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
       }
       comms[idx[k]]->last_algo = a2all                              ? MCCS_ALGO_LL
                                  : !direct                          ? MCCS_ALGO_RING
+                                 : da.mode == MCCS_DIRECT_WIDE_LL       ? MCCS_ALGO_WIDE_LL
+                                 : da.mode == MCCS_DIRECT_WIDE_ONE_SHOT ? MCCS_ALGO_WIDE_ONESHOT
+                                 : da.mode == MCCS_DIRECT_WIDE_TWO_SHOT ? MCCS_ALGO_WIDE_DIRECT
                                  : da.mode == MCCS_DIRECT_TWO_SHOT ? MCCS_ALGO_DIRECT
                                  : da.mode == MCCS_DIRECT_LL_ONE_SHOT || da.mode == MCCS_DIRECT_LL_AG ||
                                            da.mode == MCCS_DIRECT_RS_LL || da.mode == MCCS_DIRECT_RD_LL ||

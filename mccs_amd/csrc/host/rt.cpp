@@ -403,6 +403,8 @@ class FakeRuntime final : public DeviceRuntime {
         direct = direct || fn == direct_kernel_ptr(dt, op) || fn == direct_rs_kernel_ptr(dt, op) ||
                  fn == direct_rd_kernel_ptr(dt, op);
     direct = direct || (fn && fn == direct_bc_kernel_ptr());
+    for (int dt : {(int)mccsFloat16, (int)mccsBfloat16})
+      for (int op : {(int)mccsDevSum, (int)mccsDevPreMulSum}) direct = direct || (fn && fn == direct_wide_kernel_ptr(dt, op));
     const bool a2all = fn && fn == a2a_ll_kernel_ptr();
     if (fn && args && grid.y >= 1 && grid.y <= MCCS_MULTI_MAX_RANKS) {
       if (a2all) {
@@ -446,6 +448,9 @@ class FakeRuntime final : public DeviceRuntime {
                             : da->mode == MCCS_DIRECT_RD_LL       ? "rd-ll"
                             : da->mode == MCCS_DIRECT_BC_ONE_SHOT ? "bc-oneshot"
                             : da->mode == MCCS_DIRECT_BC_LL       ? "bc-ll"
+                            : da->mode == MCCS_DIRECT_WIDE_LL       ? "wide-ll"
+                            : da->mode == MCCS_DIRECT_WIDE_ONE_SHOT ? "wide-oneshot"
+                            : da->mode == MCCS_DIRECT_WIDE_TWO_SHOT ? "wide-twoshot"
                                                                   : "twoshot") +
                 " gx=" + std::to_string(grid.x) + " llslot=" + std::to_string(da->ll_slot_bytes) +
                 " piece=" + std::to_string(da->piece) + " piece2=" + std::to_string(da->piece2) +
@@ -456,7 +461,14 @@ class FakeRuntime final : public DeviceRuntime {
         // a direct ReduceScatter also names its rank slots: rank:send:recv (hex), '/' between them
         const bool rooted_mode = da->mode >= MCCS_DIRECT_RD_ONE_SHOT && da->mode <= MCCS_DIRECT_BC_LL;
         if (rooted_mode) extra += " root=" + std::to_string(da->root);  // a direct Broadcast / Reduce names its root
-        if (da->mode == MCCS_DIRECT_RS_ONE_SHOT || da->mode == MCCS_DIRECT_RS_LL || rooted_mode) {
+        // a wide AllReduce names its scalar (hex); its share table is owned= above
+        const bool wide_mode = da->mode >= MCCS_DIRECT_WIDE_LL && da->mode <= MCCS_DIRECT_WIDE_TWO_SHOT;
+        if (wide_mode) {
+          char hex[32];
+          std::snprintf(hex, sizeof(hex), " op_arg=%llx", (unsigned long long)da->op_arg);
+          extra += hex;
+        }
+        if (da->mode == MCCS_DIRECT_RS_ONE_SHOT || da->mode == MCCS_DIRECT_RS_LL || rooted_mode || wide_mode) {
           extra += " slots=";
           for (unsigned k = 0; k < grid.y; ++k) {
             char hex[64];
@@ -573,6 +585,9 @@ class FakeRuntime final : public DeviceRuntime {
           return;
     if (fn == direct_bc_kernel_ptr()) return;
     if (fn == a2a_ll_kernel_ptr()) return;
+    for (int dt : {(int)mccsFloat16, (int)mccsBfloat16})
+      for (int op : {(int)mccsDevSum, (int)mccsDevPreMulSum})
+        if (fn == direct_wide_kernel_ptr(dt, op)) return;
     const mccsMultiLaunchArgs* ma = (const mccsMultiLaunchArgs*)args[0];
     if (ma->inline_works) return;
     const int nch = __builtin_popcountll(ma->channelMask);

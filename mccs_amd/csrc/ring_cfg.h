@@ -307,6 +307,27 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 // ReduceScatter, AllReduce, AllGather and all-to-all direct launches, and
 // under every change of root between launches: the rule does not mention the
 // root.
+//
+// Wide direct AllReduce (direct_wide.h, opt-in: mccsCommSetAllReduceWide; fp16
+// and bf16, Sum and PreMulSum) uses the same region and state and adds no
+// slot.  Only its arithmetic (binary32 accumulation in rank order, one
+// rounding) and its cut differ from the AllReduce variants above; every
+// hand-off is one of theirs with the same per-sender amounts:
+//   wide LL: the LL one-shot's lines word for word (every rank writes every
+//     word into every peer's LL slot [parity][sender]; LAUNCHES alone moves);
+//   wide one-shot: the one-shot's -- every sender adds the whole count to
+//     every peer's IN_CNT, E_IN += count, E_SELF += count in place;
+//   wide two-shot: the two-shot's with owned[t] = rank t's contiguous share
+//     (MCCS_WIDE_SHARE; 0 for trailing ranks of a small count) instead of the
+//     walk's chunks -- sender s adds owned[t] to t's IN_CNT(s), owner o adds
+//     owned[o] to every peer's OUT_CNT(o), E_IN += owned[self],
+//     E_OUT[t] += owned[t].
+// So the reuse paragraphs above hold word for word across any mix of wide and
+// other direct launches: nothing in them depends on how owned[] cuts the
+// buffer, only on "a peer cannot finish a launch without a hand-off this rank
+// makes in that same launch", which count >= 1 gives (rank 0 always owns
+// elements, and it waits, directly or through its broadcast, for every rank's
+// phase-1 count; a rank that owns nothing reads no in slot).
 #define MCCS_DIRECT_MAX_RANKS 8
 #define MCCS_DIRECT_CTRL_BYTES 65536
 // u64, added to by sender s; a rank's own line IN_CNT(rank) counts its own
@@ -338,6 +359,13 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 #define MCCS_DIRECT_RD_LL 8        // Reduce through the root's LL lines
 #define MCCS_DIRECT_BC_ONE_SHOT 9  // Broadcast through every peer's one-shot slot for the root
 #define MCCS_DIRECT_BC_LL 10       // Broadcast through every peer's LL lines for the root
+// wide-accumulate AllReduce (direct_wide.h; fp16 / bf16, op_arg = the PreMulSum scalar)
+#define MCCS_DIRECT_WIDE_LL 11        // through the LL lines
+#define MCCS_DIRECT_WIDE_ONE_SHOT 12  // through the one-shot slots, counted on IN_CNT
+#define MCCS_DIRECT_WIDE_TWO_SHOT 13  // through the two-shot slots, contiguous shares
+// elements of one rank's share of a wide two-shot: ceil(count / n) rounded up
+// to 8, so every share starts on a 16-byte pack of 2-byte elements
+#define MCCS_WIDE_SHARE(count, n) ((((count) + (n) - 1) / (n) + 7) & ~(uint64_t)7)
 
 struct mccsDirectRank {  // one rank slot of a direct launch (blockIdx.y)
   const void* send;
@@ -360,14 +388,15 @@ struct mccsDirectArgs {
   uint64_t timeout_ticks;  // s_memrealtime ticks; 0 = never
   uint32_t nranks, nch, nthr_ref, buff_size;  // the ring walk this launch reproduces
   uint32_t fence_mode;                        // MCCS_FENCE_*
-  uint32_t mode;                              // MCCS_DIRECT_* above (RS: direct_rs_kernel only; RD / BC: direct_rooted.h's kernels only)
+  uint32_t mode;                              // MCCS_DIRECT_* above (RS: direct_rs_kernel only; RD / BC: direct_rooted.h's kernels only; WIDE: direct_wide_kernel only)
   uint32_t piece;                             // elements per piece of the scatter / gather phases
   uint32_t piece2;                            // elements per piece of the reduction phase
   uint32_t no_guard;                          // 1: skip the launch guard (test hook only)
   uint32_t root;                              // the RD / BC modes: the root (one for all rank slots); else 0
   uint64_t guard_order;                       // rank slots by guard address, 4 bits each (launch_guard.h)
-  uint64_t owned[MCCS_DIRECT_MAX_RANKS];      // elements of the walk's chunks each rank owns
+  uint64_t owned[MCCS_DIRECT_MAX_RANKS];      // elements of the walk's chunks each rank owns (wide two-shot: of its share)
   uint8_t idx2rank[MCCS_MAX_NCHANNELS][MCCS_DIRECT_MAX_RANKS];  // rank at ring index k of channel bid
+  uint64_t op_arg;  // the wide modes: the PreMulSum scalar (T in the low bits); else 0 (last: the fields above keep their place)
 };
 #ifdef __cplusplus
 static_assert(sizeof(mccsDirectArgs) <= 4096, "direct launch arguments must stay within 4 KiB");

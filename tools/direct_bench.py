@@ -19,6 +19,10 @@ count-based and the LL variant (mccsCommSetRootedDirect at the caps), the root
 rotating on every call.  Every variant is warmed up, then timed in --regions
 regions of --calls calls each, the variants alternating region by region; a
 row holds the median and the min / max of the regions' us per call.
+  python tools/direct_bench.py --wide --dtype bfloat16 [--n 2 4 8] [--sizes-kib 8 32 ...] [--regions 5]
+The wide-accumulate AllReduce (mccsCommSetAllReduceWide) against the ring-order
+LL / one-shot / two-shot body the same size takes, timed like --rooted, plus
+us per call of a 20-call graph replay.
 """
 import argparse
 import json
@@ -172,6 +176,67 @@ def rooted_mode(args, torch, C, st, dt, code, es):
                       "regions": args.regions, "rows": rows}), flush=True)
 
 
+def wide_mode(args, torch, C, st, dt, code, es):
+    """--wide: the wide-accumulate AllReduce against the ring-order body that
+    the same size takes (LL to 64 KiB, one-shot to 1 MiB, two-shot to 8 MiB),
+    per call: eager regions that alternate between the two, and 20 calls per
+    graph replay."""
+    import statistics
+
+    assert es == 2, "--wide times float16 / bfloat16"
+    ll_top, one_top, two_top = 64 << 10, 1 << 20, 8 << 20
+    sizes = args.sizes_kib if args.sizes_kib != DEFAULT_SIZES_KIB else [8, 32, 128, 512, 2048, 8192]
+    rows = []
+    for n in args.n:
+        cfg = C.CommConfig(ll_bytes=ll_top, oneshot_bytes=one_top, direct_bytes=two_top)
+        sets = {"order": C.init_all([0] * n, cfg), "wide": C.init_all([0] * n, cfg)}
+        assert sets["wide"][0].all_reduce_wide_max() == (ll_top, one_top, two_top)
+        for c in sets["wide"]:
+            c.set_all_reduce_wide(ll_top, one_top, two_top)
+        for kib in sizes:
+            nbytes = kib << 10
+            cnt = nbytes // es
+            body = "ll" if nbytes <= ll_top else "oneshot" if nbytes <= one_top else "direct"
+            want = {"order": body, "wide": "wide-" + body}
+            xs = [torch.randn(cnt, device="cuda").to(dt) for _ in range(n)]
+            ys = [torch.empty(cnt, dtype=dt, device="cuda") for _ in xs]
+            row = {"n": n, "bytes": nbytes, "body": body}
+
+            def once(a):
+                with C.group():
+                    for r, c in enumerate(sets[a]):
+                        C.all_reduce(c, xs[r], ys[r], cnt, code, 0, stream=st)
+
+            for a in sets:  # warm-up: every kernel's code object
+                for _ in range(5):
+                    once(a)
+                st.synchronize()
+                assert sets[a][0].last_algo() == want[a], (a, sets[a][0].last_algo())
+            us = {a: [] for a in sets}
+            for _ in range(args.regions):
+                for a in sets:  # the variants alternate region by region
+                    t0 = time.perf_counter()
+                    for _ in range(args.calls):
+                        once(a)
+                    st.synchronize()
+                    us[a].append((time.perf_counter() - t0) / args.calls * 1e6)
+            for a in sets:
+                row[a + "_us"] = round(statistics.median(us[a]), 2)
+                row[a + "_min_us"], row[a + "_max_us"] = round(min(us[a]), 2), round(max(us[a]), 2)
+                row[a + "_graph_us"] = _time_call(torch, lambda: once(a), st, 5)[1]
+                for c in sets[a]:
+                    c.sync()
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            del xs, ys
+        torch.cuda.synchronize()
+        for comms in sets.values():
+            for c in comms:
+                c.destroy()
+    print(json.dumps({"tool": "direct_bench", "collective": "allreduce-wide", "dtype": args.dtype, "calls": args.calls,
+                      "regions": args.regions, "rows": rows}), flush=True)
+
+
 DEFAULT_SIZES_KIB = [32, 128, 512, 2048, 8192, 32768]
 
 
@@ -196,7 +261,10 @@ def main():
                          "the one-shot AllGather of the same bytes per rank")
     ap.add_argument("--rooted", action="store_true",
                     help="time Broadcast and Reduce (size = the buffer, 1 KiB to the caps): ring vs count-based vs LL")
-    ap.add_argument("--regions", type=int, default=5, help="--rooted: timed regions of --calls calls per variant")
+    ap.add_argument("--wide", action="store_true",
+                    help="time the wide-accumulate AllReduce (--dtype float16 / bfloat16; 8 KiB to 8 MiB) against the "
+                         "ring-order LL / one-shot / two-shot body of the same size")
+    ap.add_argument("--regions", type=int, default=5, help="--rooted, --wide: timed regions of --calls calls per variant")
     args = ap.parse_args()
     dt = getattr(torch, args.dtype)
     code = {torch.float16: 6, torch.float32: 7, torch.bfloat16: 9}[dt]
@@ -208,6 +276,9 @@ def main():
         return
     if args.rooted:
         rooted_mode(args, torch, C, st, dt, code, es)
+        return
+    if args.wide:
+        wide_mode(args, torch, C, st, dt, code, es)
         return
     for n in args.n:
         top = max(args.sizes_kib) << 10

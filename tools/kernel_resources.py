@@ -22,6 +22,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mccs_amd", "csrc")
+sys.path.insert(0, ROOT)
+from mccs_amd.build import EXTRA_CFLAGS  # noqa: E402  (a source's own flags, as the library build passes them)
 KEYS = (".vgpr_count", ".agpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size",
         ".vgpr_spill_count", ".sgpr_spill_count")
 
@@ -30,7 +32,7 @@ def compile_tu(src, extra, tmp):
     d = os.path.join(tmp, os.path.basename(src))
     os.makedirs(d, exist_ok=True)
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{ROOT}/include", f"-I{CSRC}",
-           "--save-temps", "-c", src, "-o", os.path.join(d, "x.o"), *extra]
+           *EXTRA_CFLAGS.get(os.path.basename(src), []), "--save-temps", "-c", src, "-o", os.path.join(d, "x.o"), *extra]
     subprocess.run(cmd, check=True, cwd=d, capture_output=True)
     out = {}
     for s in glob.glob(os.path.join(d, "*gfx950*.s")):
