@@ -574,6 +574,41 @@ mccsResult_t mccsCommRootedDirectMax(mccsComm_t comm, size_t *cap, size_t *ll_ca
  * cover this path. */
 mccsResult_t mccsCommSetAllReduceWide(mccsComm_t comm, size_t ll_bytes, size_t oneshot_bytes, size_t twoshot_bytes);
 mccsResult_t mccsCommAllReduceWideMax(mccsComm_t comm, size_t *ll_cap, size_t *oneshot_cap, size_t *twoshot_cap);
+/* The wide-accumulate direct ReduceScatter and Reduce: the wide AllReduce's
+ * contract (above) on their cut, for mccsFloat16 and mccsBfloat16 with Sum or
+ * PreMulSum (so mccsAvgOp).  Every rank writes each foreign block once into its
+ * owner's slot (ReduceScatter), or its buffer into the root's (Reduce); the
+ * owner sums in binary32 in RANK order 0 .. n-1 and rounds once.  Rank t gets
+ * the wide AllReduce's bits for elements [t * recvcount, (t+1) * recvcount);
+ * the root gets them for the whole buffer.  THE BITS DIFFER FROM THE RING'S
+ * (and from the ring-order direct variants'), the stated price of opting in
+ * (DESIGN.md §8).  A PreMulSum of these two functions has no other one-exchange
+ * path.  Opt-in per communicator, per function; limits are bytes PER BLOCK
+ * (ReduceScatter) or of the WHOLE BUFFER (Reduce), default to 0 = off, and with
+ * all four off every call plans exactly as without these entry points.
+ * MCCS_RS_WIDE_LL_BYTES / MCCS_RS_WIDE_BYTES / MCCS_RD_WIDE_LL_BYTES /
+ * MCCS_RD_WIDE_BYTES in the environment set them when the communicator is
+ * created (clamped to the maxima).
+ * mccsCommReduceScatterWideMax / mccsCommReduceWideMax: the direct
+ * ReduceScatter's two maxima (*ll_cap = ll_slot / 2, *cap = one one-shot slot).
+ * mccsCommSetReduceScatterWide / mccsCommSetReduceWide: a value above its
+ * maximum is refused with mccsInvalidArgument; a call while the communicator
+ * has a group open or a call pending, with mccsInvalidUsage.  EVERY RANK MUST
+ * SET THE SAME VALUES; this is not detected.
+ * A qualifying call (count > 0, 2 <= nranks <= 8) that is its communicator's
+ * only call of the launch takes the wide LL variant within the LL limit
+ * (mccsCommLastAlgo reports MCCS_ALGO_WIDE_LL), else the wide one-shot within
+ * the other (MCCS_ALGO_WIDE_ONESHOT); this is decided before the ring-order
+ * direct variants see the call.  A larger one, one sharing a group with a
+ * second call of the communicator (it goes to the ring with its scalar and
+ * root), every other dtype, Prod / Max / Min and SumPostDiv plan as before.  In
+ * place is supported; a Reduce non-root's recvbuff is never touched and may be
+ * NULL; ranks sharing a GPU are fused into one launch; the call may be captured
+ * into a HIP graph.  The node gate does not cover this path. */
+mccsResult_t mccsCommSetReduceScatterWide(mccsComm_t comm, size_t ll_block_bytes, size_t block_bytes);
+mccsResult_t mccsCommReduceScatterWideMax(mccsComm_t comm, size_t *ll_cap, size_t *cap);
+mccsResult_t mccsCommSetReduceWide(mccsComm_t comm, size_t ll_bytes, size_t bytes);
+mccsResult_t mccsCommReduceWideMax(mccsComm_t comm, size_t *ll_cap, size_t *cap);
 /* Send / Recv: grouped point-to-point (torch's batch_isend_irecv; the pieces of
  * a Gather or Scatter).  mccsSend moves count * elem_bytes(dtype) bytes from
  * sendbuff to rank `peer`, mccsRecv receives as many from rank `peer` into

@@ -115,6 +115,10 @@ SIGNATURES: dict[str, tuple] = {
     "mccsCommReduceScatterDirectMax": (_c_int, [_c_void_p, _P(_c_size_t), _P(_c_size_t)]),
     "mccsCommSetAllReduceWide": (_c_int, [_c_void_p, _c_size_t, _c_size_t, _c_size_t]),
     "mccsCommAllReduceWideMax": (_c_int, [_c_void_p, _P(_c_size_t), _P(_c_size_t), _P(_c_size_t)]),
+    "mccsCommSetReduceScatterWide": (_c_int, [_c_void_p, _c_size_t, _c_size_t]),
+    "mccsCommReduceScatterWideMax": (_c_int, [_c_void_p, _P(_c_size_t), _P(_c_size_t)]),
+    "mccsCommSetReduceWide": (_c_int, [_c_void_p, _c_size_t, _c_size_t]),
+    "mccsCommReduceWideMax": (_c_int, [_c_void_p, _P(_c_size_t), _P(_c_size_t)]),
     "mccsCommSetRootedDirect": (_c_int, [_c_void_p, _c_size_t, _c_size_t, _c_size_t, _c_size_t]),
     "mccsCommRootedDirectMax": (_c_int, [_c_void_p, _P(_c_size_t), _P(_c_size_t)]),
     "mccs_alltoall_route": (

@@ -35,12 +35,13 @@ CFLAGS = [
 ]
 
 
-# Extra flags of single sources.  direct_wide.hip: its binary32 accumulators
+# Extra flags of single sources.  direct_wide.hip, direct_wide_rs.hip: their binary32 accumulators
 # would otherwise be paired into packed fp32 instructions; the sum is defined
 # lane by lane (direct_wide.h), so the device code is compiled without them.
 EXTRA_CFLAGS = {
     # (the host pass does not know the feature and says so in a note; it is ignored there)
     "direct_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "direct_wide_rs.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

@@ -328,6 +328,41 @@ class Communicator:
                                                    ctypes.byref(two_cap)), "mccsCommAllReduceWideMax")
         return int(ll_cap.value), int(cap.value), int(two_cap.value)
 
+    def set_reduce_scatter_wide(self, ll_block_bytes: int = 0, block_bytes: int = 0) -> None:
+        """mccsCommSetReduceScatterWide: opts the communicator in to the
+        wide-accumulate direct ReduceScatter (0 = off, the default).  Both
+        limits are bytes per block.  A Float16 / BFloat16 reduce_scatter of Sum
+        or PreMulSum (the average) that is the communicator's only call of its
+        launch is summed in binary32 in rank order and rounded once:
+        last_algo() == "wide-ll" within ll_block_bytes, else "wide-oneshot"
+        within block_bytes.  The bits are the wide all_reduce's block and differ
+        from the ring's.  Every rank must set the same two values, each at most
+        its reduce_scatter_wide_max()."""
+        rc = _sig().mccsCommSetReduceScatterWide(self._h, int(ll_block_bytes), int(block_bytes))
+        _lib.check(rc, "mccsCommSetReduceScatterWide")
+
+    def reduce_scatter_wide_max(self) -> tuple[int, int]:
+        """mccsCommReduceScatterWideMax: (ll_cap, cap), the largest block in
+        bytes of the wide LL and one-shot variant; 0 where one cannot be used."""
+        ll_cap, cap = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        _lib.check(_sig().mccsCommReduceScatterWideMax(self._h, ctypes.byref(ll_cap), ctypes.byref(cap)),
+                   "mccsCommReduceScatterWideMax")
+        return int(ll_cap.value), int(cap.value)
+
+    def set_reduce_wide(self, ll_bytes: int = 0, nbytes: int = 0) -> None:
+        """mccsCommSetReduceWide: as set_reduce_scatter_wide for reduce, the
+        two limits in bytes of the whole buffer; the root receives the wide
+        all_reduce's bits, a non-root's recv buffer is not touched."""
+        _lib.check(_sig().mccsCommSetReduceWide(self._h, int(ll_bytes), int(nbytes)), "mccsCommSetReduceWide")
+
+    def reduce_wide_max(self) -> tuple[int, int]:
+        """mccsCommReduceWideMax: (ll_cap, cap), the largest buffer in bytes of
+        the wide LL and one-shot variant; 0 where one cannot be used."""
+        ll_cap, cap = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        _lib.check(_sig().mccsCommReduceWideMax(self._h, ctypes.byref(ll_cap), ctypes.byref(cap)),
+                   "mccsCommReduceWideMax")
+        return int(ll_cap.value), int(cap.value)
+
     def all_to_all_route(self) -> dict:
         """The comm's AllToAll route (mccsCommAllToAllRoute): hops (1: every
         block goes straight to its ring successor; nranks - 1: relayed along the
@@ -451,7 +486,8 @@ def reduce_scatter(comm: Communicator, send_buf, recv_buf, recv_count: int, data
     this rank's block over all ranks.  The ring, unless the communicator opted
     in with set_reduce_scatter_direct and the block is within a limit (then
     one direct exchange, same bits); stream-ordered.  op_arg as for all_reduce
-    (mccsReduceScatterOpArg; PreMulSum / SumPostDiv always take the ring)."""
+    (mccsReduceScatterOpArg; PreMulSum / SumPostDiv take the ring, but for a
+    Float16 / BFloat16 PreMulSum within a set_reduce_scatter_wide limit)."""
     if op_arg is None:
         rc = _sig().mccsReduceScatter(_ptr(send_buf), _ptr(recv_buf), int(recv_count), int(data_type),
                                       int(op_type), comm._h, _stream(stream))
@@ -479,7 +515,8 @@ def reduce(comm: Communicator, send_buf, recv_buf, count: int, data_type=AllRedu
     the root is recv == send.  The ring, unless the communicator opted in with
     set_rooted_direct and the buffer is within a limit (then one direct
     exchange, same bits); stream-ordered.  op_arg as for all_reduce
-    (mccsReduceOpArg; PreMulSum / SumPostDiv always take the ring)."""
+    (mccsReduceOpArg; PreMulSum / SumPostDiv take the ring, but for a Float16 /
+    BFloat16 PreMulSum within a set_reduce_wide limit)."""
     if op_arg is None:
         rc = _sig().mccsReduce(_ptr(send_buf), _ptr(recv_buf), int(count), int(data_type), int(op_type), int(root),
                                comm._h, _stream(stream))

@@ -998,6 +998,50 @@ extern "C" mccsResult_t mccsCommSetAllReduceWide(mccsComm_t comm, size_t ll_byte
   return mccsSuccess;
 }
 
+// The wide ReduceScatter's (rd = false) and Reduce's (rd = true) two limits.
+static mccsResult_t set_rs_wide(mccsComm_t comm, bool rd, size_t ll_bytes, size_t bytes) {
+  err_clear();
+  StepScope st(rd ? "mccsCommSetReduceWide" : "mccsCommSetReduceScatterWide");
+  Comm* c = (Comm*)comm;
+  if (!c || !c->connected) MCCS_FAIL(mccsInvalidUsage, "the communicator is not connected");
+  if (g_group.depth > 0 || c->plan_pending)
+    MCCS_FAIL(mccsInvalidUsage, "the communicator has a group open or a call pending: set the limits between launches");
+  const size_t ll_cap = rs_ll_cap(c), cap = rs_direct_cap(c);
+  if (ll_bytes > ll_cap)
+    MCCS_FAIL(mccsInvalidArgument, "%s %zu is above the %zu bytes one %s can move through an LL slot%s",
+              rd ? "ll_bytes" : "ll_block_bytes", ll_bytes, ll_cap, rd ? "buffer" : "block",
+              ll_cap ? "" : " (no LL slots, a cached arena or system-scope fences: the LL path is closed here)");
+  if (bytes > cap)
+    MCCS_FAIL(mccsInvalidArgument, "%s %zu is above the %zu bytes of a one-shot slot%s", rd ? "bytes" : "block_bytes",
+              bytes, cap, cap ? "" : " (no one-shot slots or no peer atomics: the count-based path is closed here)");
+  (rd ? c->rd_wide_ll_bytes : c->rs_wide_ll_bytes) = ll_bytes;
+  (rd ? c->rd_wide_bytes : c->rs_wide_bytes) = bytes;
+  rs_wide_prepare(c);
+  return mccsSuccess;
+}
+
+static mccsResult_t rs_wide_max(mccsComm_t comm, const char* who, size_t* ll_cap, size_t* cap) {
+  err_clear();
+  const Comm* c = (const Comm*)comm;
+  if (!c || !ll_cap || !cap) MCCS_FAIL(mccsInvalidArgument, "%s: null communicator or output", who);
+  *ll_cap = c->connected ? rs_ll_cap(c) : 0;
+  *cap = c->connected ? rs_direct_cap(c) : 0;
+  return mccsSuccess;
+}
+
+extern "C" mccsResult_t mccsCommSetReduceScatterWide(mccsComm_t comm, size_t ll_block_bytes, size_t block_bytes) {
+  return set_rs_wide(comm, false, ll_block_bytes, block_bytes);
+}
+extern "C" mccsResult_t mccsCommReduceScatterWideMax(mccsComm_t comm, size_t* ll_cap, size_t* cap) {
+  return rs_wide_max(comm, "mccsCommReduceScatterWideMax", ll_cap, cap);
+}
+extern "C" mccsResult_t mccsCommSetReduceWide(mccsComm_t comm, size_t ll_bytes, size_t bytes) {
+  return set_rs_wide(comm, true, ll_bytes, bytes);
+}
+extern "C" mccsResult_t mccsCommReduceWideMax(mccsComm_t comm, size_t* ll_cap, size_t* cap) {
+  return rs_wide_max(comm, "mccsCommReduceWideMax", ll_cap, cap);
+}
+
 extern "C" mccsResult_t mccsCommAllToAllRoute(mccsComm_t comm, int* info2) {
   const Comm* c = (const Comm*)comm;
   if (!c || !info2) return mccsInvalidArgument;

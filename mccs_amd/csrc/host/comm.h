@@ -316,7 +316,7 @@ struct Comm {
     void* recv;
     size_t count;
     int root;  // a held Broadcast / Reduce: its root (else 0)
-    bool wide;        // held for direct_wide_kernel (below)
+    bool wide;        // held for direct_wide_kernel, or direct_wide_rs.h's kernels (below)
     uint64_t op_arg;  // a held wide call's PreMulSum scalar (else 0); a demotion passes it on to the ring
   } direct{};
   // Wide-accumulate direct AllReduce (direct_wide.h).  The three opt-in limits
@@ -327,6 +327,16 @@ struct Comm {
   // with its op_arg) and runs direct_wide_kernel (LL, else one-shot, else
   // two-shot).  Every rank must set the same values.
   size_t ar_wide_ll_bytes = 0, ar_wide_oneshot_bytes = 0, ar_wide_bytes = 0;
+  // Wide-accumulate direct ReduceScatter and Reduce (direct_wide_rs.h).  Two
+  // opt-in limits per function, in bytes per block (mccsCommSetReduceScatterWide;
+  // MCCS_RS_WIDE_LL_BYTES / MCCS_RS_WIDE_BYTES) or of the whole buffer
+  // (mccsCommSetReduceWide; MCCS_RD_WIDE_LL_BYTES / MCCS_RD_WIDE_BYTES), all 0 =
+  // off: an fp16 / bf16 call of Sum or PreMulSum within one of its function's
+  // limits, and which is its comm's only call of the launch, is held in `direct`
+  // (wide = true, with its op_arg and root) before the ring-order direct holds
+  // see it and runs direct_wide_rs_kernel / direct_wide_rd_kernel (LL, else
+  // one-shot).  Every rank must set the same values.
+  size_t rs_wide_ll_bytes = 0, rs_wide_bytes = 0, rd_wide_ll_bytes = 0, rd_wide_bytes = 0;
   // Direct Broadcast and Reduce (direct_rooted.h).  The four opt-in limits in
   // bytes of the whole buffer (mccsCommSetRootedDirect; MCCS_BC_DIRECT_BYTES /
   // MCCS_BC_LL_BYTES / MCCS_RD_DIRECT_BYTES / MCCS_RD_LL_BYTES at creation),
@@ -476,6 +486,10 @@ size_t ar_wide_cap(const Comm* c);
 // reads MCCS_AR_WIDE_LL_BYTES / MCCS_AR_WIDE_ONESHOT_BYTES / MCCS_AR_WIDE_BYTES, clamped to the caps
 void ar_wide_read_env(Comm* c);
 void ar_wide_prepare(const Comm* c);  // after the limits changed: probes the wide kernels' co-residency once
+// Wide direct ReduceScatter / Reduce: the caps are the direct ReduceScatter's (per block / over the whole buffer)
+// reads MCCS_RS_WIDE_LL_BYTES / MCCS_RS_WIDE_BYTES / MCCS_RD_WIDE_LL_BYTES / MCCS_RD_WIDE_BYTES, clamped to the caps
+void rs_wide_read_env(Comm* c);
+void rs_wide_prepare(const Comm* c);  // after the limits changed: probes the eight kernels' co-residency once
 mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_t>& user_streams);
 // ring.hip
 const void* ring_kernel_ptr(int func, int dtype, int op);
@@ -492,6 +506,9 @@ const void* direct_rd_kernel_ptr(int dtype, int op);
 const void* direct_bc_kernel_ptr();
 // direct_wide.hip (fp16 / bf16 x Sum / PreMulSum; else null)
 const void* direct_wide_kernel_ptr(int dtype, int op);
+// direct_wide_rs.hip (likewise)
+const void* direct_wide_rs_kernel_ptr(int dtype, int op);
+const void* direct_wide_rd_kernel_ptr(int dtype, int op);
 hipError_t ring_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_flush_caches(hipStream_t st);
 

@@ -568,10 +568,35 @@ void ar_wide_read_env(Comm* c) {
   ar_wide_prepare(c);
 }
 
-// The wide mode an fp16 / bf16 AllReduce of `bytes` takes on this comm (-1:
-// none): LL wins over one-shot, one-shot over two-shot.  Every rank sees the
-// same limits and the same call, so every rank decides alike.
-static int wide_mode(const Comm* c, size_t bytes) {
+// The wide ReduceScatter's and Reduce's limits (direct_wide_rs.h): the direct
+// ReduceScatter's caps and conditions, per block / over the whole buffer.
+void rs_wide_read_env(Comm* c) {
+  auto read = [&](const char* name, size_t cap) {
+    const char* v = std::getenv(name);
+    const long long x = v ? std::atoll(v) : 0;
+    return x > 0 ? std::min((size_t)x, cap) : (size_t)0;
+  };
+  c->rs_wide_ll_bytes = read("MCCS_RS_WIDE_LL_BYTES", rs_ll_cap(c));
+  c->rs_wide_bytes = read("MCCS_RS_WIDE_BYTES", rs_direct_cap(c));
+  c->rd_wide_ll_bytes = read("MCCS_RD_WIDE_LL_BYTES", rs_ll_cap(c));
+  c->rd_wide_bytes = read("MCCS_RD_WIDE_BYTES", rs_direct_cap(c));
+  rs_wide_prepare(c);
+}
+
+// The wide mode an fp16 / bf16 call of `func` takes on this comm (-1: none),
+// `bytes` being the whole buffer (AllReduce, Reduce) or one block
+// (ReduceScatter): LL wins over one-shot, one-shot over two-shot.  Every rank
+// sees the same limits and the same call, so every rank decides alike.
+static int wide_mode(const Comm* c, int func, size_t bytes) {
+  if (func == mccsFuncReduceScatter || func == mccsFuncReduce) {
+    const bool rd = func == mccsFuncReduce;
+    if (bytes <= (rd ? c->rd_wide_ll_bytes : c->rs_wide_ll_bytes) && bytes <= rs_ll_cap(c))
+      return rd ? MCCS_DIRECT_WIDE_RD_LL : MCCS_DIRECT_WIDE_RS_LL;
+    if (bytes <= (rd ? c->rd_wide_bytes : c->rs_wide_bytes) && bytes <= rs_direct_cap(c))
+      return rd ? MCCS_DIRECT_WIDE_RD_ONE_SHOT : MCCS_DIRECT_WIDE_RS_ONE_SHOT;
+    return -1;
+  }
+  if (func != mccsFuncAllReduce) return -1;
   if (bytes <= c->ar_wide_ll_bytes && bytes <= rs_ll_cap(c)) return MCCS_DIRECT_WIDE_LL;
   if (bytes <= c->ar_wide_oneshot_bytes && bytes <= rs_direct_cap(c)) return MCCS_DIRECT_WIDE_ONE_SHOT;
   if (bytes <= c->ar_wide_bytes && bytes <= ar_wide_cap(c)) return MCCS_DIRECT_WIDE_TWO_SHOT;
@@ -613,20 +638,21 @@ mccsResult_t plan_enqueue(Comm* c, int func, int dtype, int op, const void* send
   // the default direct variants are AllReduce / AllGather only.  So does a
   // PreMulSum or SumPostDiv of any function and size: the ring-order direct
   // kernels know neither the pre nor the post step.
-  // One fp16 / bf16 AllReduce of Sum or PreMulSum within an opt-in wide limit
-  // (all 0: never) is held for direct_wide_kernel with its scalar, before the
-  // ordinary direct hold below sees it; a second call demotes it to the ring
-  // (demote_direct above, which passes the scalar on).
+  // One fp16 / bf16 AllReduce, ReduceScatter or Reduce of Sum or PreMulSum
+  // within an opt-in wide limit of its function (all 0: never) is held for
+  // direct_wide_kernel / direct_wide_rs.h's kernels with its scalar (a Reduce:
+  // and its root), before the ordinary direct holds below see it; a second call
+  // demotes it to the ring (demote_direct above, which passes both on).
   c->direct.wide = false;
   c->direct.op_arg = 0;
-  if (first && !c->plan_pending && func == mccsFuncAllReduce && (dtype == mccsFloat16 || dtype == mccsBfloat16) &&
+  if (first && !c->plan_pending && (dtype == mccsFloat16 || dtype == mccsBfloat16) &&
       (op == mccsDevSum || op == mccsDevPreMulSum) && c->nranks >= 2 && c->nranks <= MCCS_DIRECT_MAX_RANKS &&
-      count > 0 && wide_mode(c, bytes) >= 0) {
+      count > 0 && wide_mode(c, func, bytes) >= 0) {
     c->plan_direct = true;
     c->direct.send = send;
     c->direct.recv = recv;
     c->direct.count = count;
-    c->direct.root = 0;
+    c->direct.root = func == mccsFuncReduce ? root : 0;
     c->direct.wide = true;
     c->direct.op_arg = op == mccsDevPreMulSum ? op_arg : 0;
     c->plan_pending = true;
@@ -1040,6 +1066,8 @@ static bool direct_group(std::vector<Comm*>& comms, const std::vector<int>& idx)
         ck->direct.root != c0->direct.root ||  // one root for every rank slot (mccsDirectArgs.root)
         ck->ar_wide_ll_bytes != c0->ar_wide_ll_bytes || ck->ar_wide_oneshot_bytes != c0->ar_wide_oneshot_bytes ||
         ck->ar_wide_bytes != c0->ar_wide_bytes || ck->direct.wide != c0->direct.wide ||
+        ck->rs_wide_ll_bytes != c0->rs_wide_ll_bytes || ck->rs_wide_bytes != c0->rs_wide_bytes ||
+        ck->rd_wide_ll_bytes != c0->rd_wide_ll_bytes || ck->rd_wide_bytes != c0->rd_wide_bytes ||
         ck->direct.op_arg != c0->direct.op_arg)  // one scalar for every rank slot (mccsDirectArgs.op_arg)
       return false;
   }
@@ -1412,10 +1440,12 @@ static mccsResult_t build_direct_rooted(std::vector<Comm*>& comms, const std::ve
 // Workgroups of the four wide AllReduce kernels the device holds at once (min
 // over them), as coresident_rs_blocks: probed when a comm opts in
 // (ar_wide_prepare), not at a launch a stream may be capturing.
-static int coresident_wide_blocks(int device, int* ncu_out) {
+// `rs`: the eight wide ReduceScatter / Reduce kernels (direct_wide_rs.h)
+// instead, cached apart, so opting in to them changes no AllReduce launch.
+static int coresident_wide_blocks(int device, int* ncu_out, bool rs = false) {
   static std::mutex mu;
-  static std::map<std::pair<unsigned, int>, std::pair<int, int>> cache;  // (runtime, device) -> (blocks, CUs)
-  const auto key = std::make_pair(rt_generation(), device);
+  static std::map<std::tuple<unsigned, int, bool>, std::pair<int, int>> cache;  // (runtime, device, family) -> (blocks, CUs)
+  const auto key = std::make_tuple(rt_generation(), device, rs);
   {
     std::lock_guard<std::mutex> lk(mu);
     auto it = cache.find(key);
@@ -1430,9 +1460,13 @@ static int coresident_wide_blocks(int device, int* ncu_out) {
   int best = 1 << 30;
   for (int dt : {(int)mccsFloat16, (int)mccsBfloat16})
     for (int op : {(int)mccsDevSum, (int)mccsDevPreMulSum}) {
-      int per_cu = 0;
-      if (rt().BlocksPerCu(&per_cu, direct_wide_kernel_ptr(dt, op), MCCS_DIRECT_THREADS) != hipSuccess) return 0;  // not cached
-      best = std::min(best, per_cu);
+      for (const void* fn : {rs ? direct_wide_rs_kernel_ptr(dt, op) : direct_wide_kernel_ptr(dt, op),
+                             rs ? direct_wide_rd_kernel_ptr(dt, op) : nullptr}) {
+        int per_cu = 0;
+        if (!fn) continue;
+        if (rt().BlocksPerCu(&per_cu, fn, MCCS_DIRECT_THREADS) != hipSuccess) return 0;  // not cached
+        best = std::min(best, per_cu);
+      }
     }
   std::lock_guard<std::mutex> lk(mu);
   cache[key] = {best * ncu, ncu};
@@ -1446,10 +1480,17 @@ void ar_wide_prepare(const Comm* c) {
     (void)coresident_wide_blocks(c->device, &ncu);
 }
 
-// The wide AllReduce launch's arguments (direct_group checked the shape, the
-// scalar included).  No ring walk: nch / nthr_ref / idx2rank stay 0, the sum
-// runs in rank order.  owned[] is the two-shot's contiguous split
-// (MCCS_WIDE_SHARE); the one-shot and LL modes leave it 0.
+void rs_wide_prepare(const Comm* c) {
+  int ncu = 0;
+  if (c->rs_wide_ll_bytes > 0 || c->rs_wide_bytes > 0 || c->rd_wide_ll_bytes > 0 || c->rd_wide_bytes > 0)
+    (void)coresident_wide_blocks(c->device, &ncu, /*rs=*/true);
+}
+
+// The wide launch's arguments (direct_group checked the shape, the scalar and
+// the root included).  No ring walk: nch / nthr_ref / idx2rank stay 0, the sum
+// runs in rank order.  owned[] is the AllReduce two-shot's contiguous split
+// (MCCS_WIDE_SHARE); every other mode leaves it 0.  ReduceScatter: count is
+// one block; Reduce: the whole buffer, with the root.
 static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vector<int>& idx, mccsDirectArgs* da,
                                       unsigned* grid_x) {
   const Comm* c0 = comms[idx[0]];
@@ -1462,12 +1503,17 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
   da->slot_bytes = c0->layout.direct_slot;
   da->oslot_bytes = c0->layout.oneshot_slot;
   da->ll_slot_bytes = c0->layout.ll_slot;
-  const int mode = wide_mode(c0, nbytes);
+  const int func = c0->plan_func;
+  const bool rs = func == mccsFuncReduceScatter, rd = func == mccsFuncReduce;
+  const int mode = wide_mode(c0, func, nbytes);
   for (size_t k = 0; k < idx.size(); ++k)  // every rank slot of the launch must take the same body
-    if (wide_mode(comms[idx[k]], nbytes) != mode) return mccsInternalError;
+    if (wide_mode(comms[idx[k]], func, nbytes) != mode) return mccsInternalError;
   if (mode < 0) return mccsInternalError;  // plan_enqueue held it for one of them
+  if (rd && (c0->direct.root < 0 || c0->direct.root >= n)) return mccsInternalError;  // api.cpp checked the range
   da->mode = (uint32_t)mode;
-  const bool ll = mode == MCCS_DIRECT_WIDE_LL, oneshot = mode == MCCS_DIRECT_WIDE_ONE_SHOT;
+  da->root = rd ? (uint32_t)c0->direct.root : 0;
+  const bool ll = mode == MCCS_DIRECT_WIDE_LL || mode == MCCS_DIRECT_WIDE_RS_LL || mode == MCCS_DIRECT_WIDE_RD_LL;
+  const bool oneshot = mode == MCCS_DIRECT_WIDE_ONE_SHOT;
   da->nranks = (uint32_t)n;
   da->buff_size = (uint32_t)c0->cfg.buffer_size;
   da->fence_mode = c0->kcfg.fence_mode;
@@ -1499,20 +1545,22 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
                             : std::max(da->timeout_ticks, ck->kcfg.timeout_ticks);
   }
   // Workgroups from phase 1 as build_direct sizes them: ~4 KiB each of the
-  // whole input (one-shot) or of the n-1 foreign shares (two-shot), or (LL)
-  // one 8-byte word per thread; capped by co-residency.
-  const size_t scatter = oneshot ? nbytes : nbytes - nbytes / (size_t)n;
+  // whole input (one-shot; a Reduce sender), of the n-1 foreign shares
+  // (two-shot) or of the n-1 foreign blocks (ReduceScatter), or (LL) one 8-byte
+  // word of phase 1 per thread; capped by co-residency.
+  const size_t scatter = rs ? nbytes * (size_t)(n - 1) : (oneshot || rd) ? nbytes : nbytes - nbytes / (size_t)n;
   int ncu = 0;
-  const int cap = coresident_wide_blocks(c0->device, &ncu);
+  const int cap = coresident_wide_blocks(c0->device, &ncu, rs || rd);
   if (ncu <= 0) ncu = cap;
   long g = std::min<long>((long)((scatter + 4095) / 4096), c0->direct_blocks);
-  if (ll) g = std::min<long>((long)((nbytes + 8 * MCCS_DIRECT_THREADS - 1) / (8 * MCCS_DIRECT_THREADS)), c0->direct_blocks);
+  const size_t ll_words = (rs ? (size_t)(n - 1) : 1) * ((nbytes + 7) / 8);
+  if (ll) g = std::min<long>((long)((ll_words + MCCS_DIRECT_THREADS - 1) / MCCS_DIRECT_THREADS), c0->direct_blocks);
   if (idx.size() > 1) g = std::min<long>(g, std::min(cap, ncu) / (long)idx.size());  // one fused launch
   else if (c0->share > 1) g = std::min<long>(g, std::min(cap / 2, ncu) / c0->share);  // separate processes
   g = std::max<long>(g, 1);
   if (g * (long)idx.size() > cap)
-    MCCS_FAIL(mccsInvalidUsage, "wide AllReduce launch of %zu ranks x %ld workgroups exceeds the %d co-resident ones of "
-              "device %d", idx.size(), g, cap, c0->device);
+    MCCS_FAIL(mccsInvalidUsage, "wide %s launch of %zu ranks x %ld workgroups exceeds the %d co-resident ones of "
+              "device %d", rs ? "ReduceScatter" : rd ? "Reduce" : "AllReduce", idx.size(), g, cap, c0->device);
   *grid_x = (unsigned)g;
   // pieces: each phase's bytes over the workgroups, in 4 KiB steps (pieces
   // start on 16-byte packs), 4..64 KiB
@@ -1522,7 +1570,7 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
     return (uint32_t)(p / esize);
   };
   da->piece = piece(scatter);
-  da->piece2 = piece(oneshot ? nbytes : nbytes / (size_t)n + 1);
+  da->piece2 = piece(oneshot || rs || rd ? nbytes : nbytes / (size_t)n + 1);
   for (size_t k = 0; k < idx.size(); ++k) {
     Comm* ck = comms[idx[k]];
     ck->plan_direct = false;
@@ -1723,9 +1771,11 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
       args[0] = &la;
     } else if (direct) {
       if (c0->direct.wide) {
-        const int dt = c0->plan_dtype, op = c0->plan_op;  // before the build clears the plan
+        const int func = c0->plan_func, dt = c0->plan_dtype, op = c0->plan_op;  // before the build clears the plan
         MCCS_CHECK(build_direct_wide(comms, idx, &da, &grid));
-        fn = direct_wide_kernel_ptr(dt, op);
+        fn = func == mccsFuncReduceScatter ? direct_wide_rs_kernel_ptr(dt, op)
+             : func == mccsFuncReduce      ? direct_wide_rd_kernel_ptr(dt, op)
+                                           : direct_wide_kernel_ptr(dt, op);
       } else if (c0->plan_func == mccsFuncReduceScatter) {
         MCCS_CHECK(build_direct_rs(comms, idx, &da, &grid));
         fn = direct_rs_kernel_ptr(c0->plan_dtype, c0->plan_op);
@@ -1857,8 +1907,12 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
       }
       comms[idx[k]]->last_algo = a2all                              ? MCCS_ALGO_LL
                                  : !direct                          ? MCCS_ALGO_RING
-                                 : da.mode == MCCS_DIRECT_WIDE_LL       ? MCCS_ALGO_WIDE_LL
-                                 : da.mode == MCCS_DIRECT_WIDE_ONE_SHOT ? MCCS_ALGO_WIDE_ONESHOT
+                                 : da.mode == MCCS_DIRECT_WIDE_LL || da.mode == MCCS_DIRECT_WIDE_RS_LL ||
+                                           da.mode == MCCS_DIRECT_WIDE_RD_LL
+                                     ? MCCS_ALGO_WIDE_LL
+                                 : da.mode == MCCS_DIRECT_WIDE_ONE_SHOT || da.mode == MCCS_DIRECT_WIDE_RS_ONE_SHOT ||
+                                           da.mode == MCCS_DIRECT_WIDE_RD_ONE_SHOT
+                                     ? MCCS_ALGO_WIDE_ONESHOT
                                  : da.mode == MCCS_DIRECT_WIDE_TWO_SHOT ? MCCS_ALGO_WIDE_DIRECT
                                  : da.mode == MCCS_DIRECT_TWO_SHOT ? MCCS_ALGO_DIRECT
                                  : da.mode == MCCS_DIRECT_LL_ONE_SHOT || da.mode == MCCS_DIRECT_LL_AG ||

@@ -404,7 +404,9 @@ class FakeRuntime final : public DeviceRuntime {
                  fn == direct_rd_kernel_ptr(dt, op);
     direct = direct || (fn && fn == direct_bc_kernel_ptr());
     for (int dt : {(int)mccsFloat16, (int)mccsBfloat16})
-      for (int op : {(int)mccsDevSum, (int)mccsDevPreMulSum}) direct = direct || (fn && fn == direct_wide_kernel_ptr(dt, op));
+      for (int op : {(int)mccsDevSum, (int)mccsDevPreMulSum})
+        direct = direct || (fn && (fn == direct_wide_kernel_ptr(dt, op) || fn == direct_wide_rs_kernel_ptr(dt, op) ||
+                                   fn == direct_wide_rd_kernel_ptr(dt, op)));
     const bool a2all = fn && fn == a2a_ll_kernel_ptr();
     if (fn && args && grid.y >= 1 && grid.y <= MCCS_MULTI_MAX_RANKS) {
       if (a2all) {
@@ -451,6 +453,10 @@ class FakeRuntime final : public DeviceRuntime {
                             : da->mode == MCCS_DIRECT_WIDE_LL       ? "wide-ll"
                             : da->mode == MCCS_DIRECT_WIDE_ONE_SHOT ? "wide-oneshot"
                             : da->mode == MCCS_DIRECT_WIDE_TWO_SHOT ? "wide-twoshot"
+                            : da->mode == MCCS_DIRECT_WIDE_RS_LL       ? "wide-rs-ll"
+                            : da->mode == MCCS_DIRECT_WIDE_RS_ONE_SHOT ? "wide-rs-oneshot"
+                            : da->mode == MCCS_DIRECT_WIDE_RD_LL       ? "wide-rd-ll"
+                            : da->mode == MCCS_DIRECT_WIDE_RD_ONE_SHOT ? "wide-rd-oneshot"
                                                                   : "twoshot") +
                 " gx=" + std::to_string(grid.x) + " llslot=" + std::to_string(da->ll_slot_bytes) +
                 " piece=" + std::to_string(da->piece) + " piece2=" + std::to_string(da->piece2) +
@@ -459,10 +465,11 @@ class FakeRuntime final : public DeviceRuntime {
         for (unsigned t = 0; t < da->nranks && t < MCCS_DIRECT_MAX_RANKS; ++t)
           extra += (t ? "," : "") + std::to_string(da->owned[t]);
         // a direct ReduceScatter also names its rank slots: rank:send:recv (hex), '/' between them
-        const bool rooted_mode = da->mode >= MCCS_DIRECT_RD_ONE_SHOT && da->mode <= MCCS_DIRECT_BC_LL;
+        const bool rooted_mode = (da->mode >= MCCS_DIRECT_RD_ONE_SHOT && da->mode <= MCCS_DIRECT_BC_LL) ||
+                                 da->mode == MCCS_DIRECT_WIDE_RD_LL || da->mode == MCCS_DIRECT_WIDE_RD_ONE_SHOT;
         if (rooted_mode) extra += " root=" + std::to_string(da->root);  // a direct Broadcast / Reduce names its root
-        // a wide AllReduce names its scalar (hex); its share table is owned= above
-        const bool wide_mode = da->mode >= MCCS_DIRECT_WIDE_LL && da->mode <= MCCS_DIRECT_WIDE_TWO_SHOT;
+        // a wide launch names its scalar (hex); a wide AllReduce's share table is owned= above
+        const bool wide_mode = da->mode >= MCCS_DIRECT_WIDE_LL && da->mode <= MCCS_DIRECT_WIDE_RD_ONE_SHOT;
         if (wide_mode) {
           char hex[32];
           std::snprintf(hex, sizeof(hex), " op_arg=%llx", (unsigned long long)da->op_arg);
@@ -587,7 +594,9 @@ class FakeRuntime final : public DeviceRuntime {
     if (fn == a2a_ll_kernel_ptr()) return;
     for (int dt : {(int)mccsFloat16, (int)mccsBfloat16})
       for (int op : {(int)mccsDevSum, (int)mccsDevPreMulSum})
-        if (fn == direct_wide_kernel_ptr(dt, op)) return;
+        if (fn == direct_wide_kernel_ptr(dt, op) || fn == direct_wide_rs_kernel_ptr(dt, op) ||
+            fn == direct_wide_rd_kernel_ptr(dt, op))
+          return;
     const mccsMultiLaunchArgs* ma = (const mccsMultiLaunchArgs*)args[0];
     if (ma->inline_works) return;
     const int nch = __builtin_popcountll(ma->channelMask);

@@ -328,6 +328,31 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 // makes in that same launch", which count >= 1 gives (rank 0 always owns
 // elements, and it waits, directly or through its broadcast, for every rank's
 // phase-1 count; a rank that owns nothing reads no in slot).
+//
+// Wide direct ReduceScatter and Reduce (direct_wide_rs.h, opt-in:
+// mccsCommSetReduceScatterWide / mccsCommSetReduceWide; fp16 and bf16, Sum and
+// PreMulSum) use the same region and state and add no slot.  Only the
+// arithmetic (binary32 in rank order, one rounding) and the absence of a walk
+// differ from the ring-order kernels; every hand-off is one of theirs with the
+// same per-sender amounts:
+//   wide RS one-shot: the direct ReduceScatter's count-based hand-off --
+//     sender s writes block t into t's one-shot slot [parity][s] and adds
+//     recvcount to t's IN_CNT(s); E_IN += recvcount on every rank;
+//   wide RS LL: the direct ReduceScatter's lines -- word w of block t into
+//     line w of t's LL slot [parity][s]; LAUNCHES alone moves;
+//   wide RD one-shot: the direct Reduce's under THE RULE above, word for word
+//     -- every rank adds count to IN_CNT(self) of every peer (over its pieces
+//     towards the root, by one add of workgroup 0 elsewhere), E_IN += count on
+//     every rank, and workgroup 0 of every rank waits for every peer's line;
+//   wide RD LL: the direct Reduce's lines under the rule -- every rank writes a
+//     flagged line 0 into every peer's slot (a dummy word where the pair
+//     carries no data) and global thread 0 of every rank polls line 0 of every
+//     peer's slot.
+// So with count >= 1 every ordered pair hands off in every such launch with
+// one common amount per sender, which is all the ReduceScatter and rooted
+// paragraphs above rest on: parity reuse and the single E_IN word hold across
+// any mix of these with every other direct launch and under every change of
+// root.
 #define MCCS_DIRECT_MAX_RANKS 8
 #define MCCS_DIRECT_CTRL_BYTES 65536
 // u64, added to by sender s; a rank's own line IN_CNT(rank) counts its own
@@ -366,6 +391,11 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 // elements of one rank's share of a wide two-shot: ceil(count / n) rounded up
 // to 8, so every share starts on a 16-byte pack of 2-byte elements
 #define MCCS_WIDE_SHARE(count, n) ((((count) + (n) - 1) / (n) + 7) & ~(uint64_t)7)
+// wide-accumulate ReduceScatter and Reduce (direct_wide_rs.h; count / root as RS / RD above, op_arg as WIDE)
+#define MCCS_DIRECT_WIDE_RS_LL 14        // ReduceScatter through the LL lines
+#define MCCS_DIRECT_WIDE_RS_ONE_SHOT 15  // ReduceScatter through the one-shot slots, counted on IN_CNT
+#define MCCS_DIRECT_WIDE_RD_LL 16        // Reduce through the root's LL lines
+#define MCCS_DIRECT_WIDE_RD_ONE_SHOT 17  // Reduce through the root's one-shot slots, counted on IN_CNT
 
 struct mccsDirectRank {  // one rank slot of a direct launch (blockIdx.y)
   const void* send;
@@ -388,11 +418,11 @@ struct mccsDirectArgs {
   uint64_t timeout_ticks;  // s_memrealtime ticks; 0 = never
   uint32_t nranks, nch, nthr_ref, buff_size;  // the ring walk this launch reproduces
   uint32_t fence_mode;                        // MCCS_FENCE_*
-  uint32_t mode;                              // MCCS_DIRECT_* above (RS: direct_rs_kernel only; RD / BC: direct_rooted.h's kernels only; WIDE: direct_wide_kernel only)
+  uint32_t mode;                              // MCCS_DIRECT_* above (RS: direct_rs_kernel only; RD / BC: direct_rooted.h's kernels only; WIDE: direct_wide_kernel only; WIDE_RS / WIDE_RD: direct_wide_rs.h's kernels only)
   uint32_t piece;                             // elements per piece of the scatter / gather phases
   uint32_t piece2;                            // elements per piece of the reduction phase
   uint32_t no_guard;                          // 1: skip the launch guard (test hook only)
-  uint32_t root;                              // the RD / BC modes: the root (one for all rank slots); else 0
+  uint32_t root;                              // the RD / BC / WIDE_RD modes: the root (one for all rank slots); else 0
   uint64_t guard_order;                       // rank slots by guard address, 4 bits each (launch_guard.h)
   uint64_t owned[MCCS_DIRECT_MAX_RANKS];      // elements of the walk's chunks each rank owns (wide two-shot: of its share)
   uint8_t idx2rank[MCCS_MAX_NCHANNELS][MCCS_DIRECT_MAX_RANKS];  // rank at ring index k of channel bid

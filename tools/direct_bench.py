@@ -23,6 +23,11 @@ row holds the median and the min / max of the regions' us per call.
 The wide-accumulate AllReduce (mccsCommSetAllReduceWide) against the ring-order
 LL / one-shot / two-shot body the same size takes, timed like --rooted, plus
 us per call of a 20-call graph replay.
+  python tools/direct_bench.py --wide --reduce-scatter | --wide --rooted --dtype bfloat16 [--n 2 4 8] [--sizes-kib ...]
+The wide-accumulate ReduceScatter (size = bytes per block) or Reduce (the
+buffer, the root rotating; mccsCommSetReduceScatterWide / mccsCommSetReduceWide)
+timed the same way: Sum beside the ring-order direct body of the same size,
+the average (PreMulSum) beside the ring, its only other path.
 """
 import argparse
 import json
@@ -237,6 +242,84 @@ def wide_mode(args, torch, C, st, dt, code, es):
                       "regions": args.regions, "rows": rows}), flush=True)
 
 
+def wide_rs_mode(args, torch, C, st, dt, code, es, rooted):
+    """--wide --reduce-scatter / --wide --rooted: the wide ReduceScatter (per
+    block) or Reduce (per buffer, the root rotating on every call), LL to
+    64 KiB and one-shot to 1 MiB.  Sum: beside the ring-order direct body of
+    the same size ("order"); the average: beside the ring ("ring").  Eager
+    regions alternate between the two; 20 calls per graph replay."""
+    import statistics
+
+    assert es == 2, "--wide times float16 / bfloat16"
+    ll_top, one_top = 64 << 10, 1 << 20
+    sizes = args.sizes_kib if args.sizes_kib != DEFAULT_SIZES_KIB else [1, 8, 64, 256, 1024]
+    rows = []
+    for n in args.n:
+        cfg = C.CommConfig(ll_bytes=ll_top, oneshot_bytes=one_top, direct_bytes=-1)
+        sets = {a: C.init_all([0] * n, cfg) for a in ("ring", "order", "wide")}
+        for c in sets["order"]:
+            if rooted:
+                c.set_rooted_direct(reduce_bytes=one_top, reduce_ll_bytes=ll_top)
+            else:
+                c.set_reduce_scatter_direct(one_top, ll_top)
+        for c in sets["wide"]:
+            assert (c.reduce_wide_max() if rooted else c.reduce_scatter_wide_max()) == (ll_top, one_top)
+            (c.set_reduce_wide if rooted else c.set_reduce_scatter_wide)(ll_top, one_top)
+        turn = [0]
+        for kib in sizes:
+            nbytes = kib << 10
+            cnt = nbytes // es
+            body = "ll" if nbytes <= ll_top else "oneshot"
+            xs = [torch.randn(cnt * (1 if rooted else n), device="cuda").to(dt) for _ in range(n)]
+            ys = [torch.empty(cnt, dtype=dt, device="cuda") for _ in xs]
+            for op, base in (("sum", "order"), ("avg", "ring")):
+                want = {base: body if base == "order" else "ring", "wide": "wide-" + body}
+                row = {"n": n, "func": "reduce" if rooted else "reducescatter", "bytes": nbytes, "body": body, "op": op}
+
+                def once(a):
+                    turn[0] += 1
+                    root = turn[0] % n
+                    with C.group():
+                        for r, c in enumerate(sets[a]):
+                            if rooted and op == "avg":
+                                C.reduce_avg(c, xs[r], ys[r] if r == root else None, cnt, code, root, stream=st)
+                            elif rooted:
+                                C.reduce(c, xs[r], ys[r] if r == root else None, cnt, code, 0, root, stream=st)
+                            elif op == "avg":
+                                C.reduce_scatter_avg(c, xs[r], ys[r], cnt, code, stream=st)
+                            else:
+                                C.reduce_scatter(c, xs[r], ys[r], cnt, code, 0, stream=st)
+
+                for a in want:  # warm-up: every kernel's code object, every root
+                    for _ in range(max(5, n)):
+                        once(a)
+                    st.synchronize()
+                    assert sets[a][0].last_algo() == want[a], (a, sets[a][0].last_algo())
+                us = {a: [] for a in want}
+                for _ in range(args.regions):
+                    for a in want:  # the variants alternate region by region
+                        t0 = time.perf_counter()
+                        for _ in range(args.calls):
+                            once(a)
+                        st.synchronize()
+                        us[a].append((time.perf_counter() - t0) / args.calls * 1e6)
+                for a in want:
+                    row[a + "_us"] = round(statistics.median(us[a]), 2)
+                    row[a + "_min_us"], row[a + "_max_us"] = round(min(us[a]), 2), round(max(us[a]), 2)
+                    row[a + "_graph_us"] = _time_call(torch, lambda: once(a), st, 5)[1]
+                    for c in sets[a]:
+                        c.sync()
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+            del xs, ys
+        torch.cuda.synchronize()
+        for comms in sets.values():
+            for c in comms:
+                c.destroy()
+    print(json.dumps({"tool": "direct_bench", "collective": "reduce-wide" if rooted else "reducescatter-wide",
+                      "dtype": args.dtype, "calls": args.calls, "regions": args.regions, "rows": rows}), flush=True)
+
+
 DEFAULT_SIZES_KIB = [32, 128, 512, 2048, 8192, 32768]
 
 
@@ -263,7 +346,9 @@ def main():
                     help="time Broadcast and Reduce (size = the buffer, 1 KiB to the caps): ring vs count-based vs LL")
     ap.add_argument("--wide", action="store_true",
                     help="time the wide-accumulate AllReduce (--dtype float16 / bfloat16; 8 KiB to 8 MiB) against the "
-                         "ring-order LL / one-shot / two-shot body of the same size")
+                         "ring-order LL / one-shot / two-shot body of the same size; with --reduce-scatter or --rooted: "
+                         "the wide ReduceScatter / Reduce (1 KiB to 1 MiB) against the ring-order direct body, and its "
+                         "average against the ring")
     ap.add_argument("--regions", type=int, default=5, help="--rooted, --wide: timed regions of --calls calls per variant")
     args = ap.parse_args()
     dt = getattr(torch, args.dtype)
@@ -271,6 +356,9 @@ def main():
     es = torch.empty(0, dtype=dt).element_size()
     rows = []
     st = side_stream(torch, 0, slot=1)
+    if args.wide and (args.reduce_scatter or args.rooted):
+        wide_rs_mode(args, torch, C, st, dt, code, es, args.rooted)
+        return
     if args.reduce_scatter:
         reduce_scatter_mode(args, torch, C, st, dt, code, es)
         return

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Register, scratch and LDS use of the shipped ring and direct kernels (gfx950).
 
-Compiles the ring translation units (ring.hip, ring_ar_*.hip) with
+Compiles the ring and direct translation units (ring*.hip, direct*.hip,
+direct_wide_rs.hip among them, each with its own build flags) with
 --save-temps into a scratch directory and reads each kernel's AMDGPU
 metadata from the generated assembly: .vgpr_count, .agpr_count,
 .sgpr_count, .private_segment_fixed_size (scratch bytes per lane) and
