@@ -609,6 +609,40 @@ mccsResult_t mccsCommSetReduceScatterWide(mccsComm_t comm, size_t ll_block_bytes
 mccsResult_t mccsCommReduceScatterWideMax(mccsComm_t comm, size_t *ll_cap, size_t *cap);
 mccsResult_t mccsCommSetReduceWide(mccsComm_t comm, size_t ll_bytes, size_t bytes);
 mccsResult_t mccsCommReduceWideMax(mccsComm_t comm, size_t *ll_cap, size_t *cap);
+/* The wide streamed ReduceScatter: the wide ReduceScatter's contract (above)
+ * for a block of ANY size, for mccsFloat16 and mccsBfloat16 with Sum or
+ * PreMulSum (so mccsAvgOp).  One kernel moves every foreign block to its owner
+ * through the one-shot slot in rounds of round_bytes, round k on the links
+ * while the owner folds round k-1; the owner sums in binary32 in RANK order
+ * 0 .. n-1 and rounds once.  Rank t gets the wide AllReduce's bits for elements
+ * [t * recvcount, (t+1) * recvcount) -- what mccsCommSetReduceScatterWide's
+ * one-shot gives for a block that fits both -- whatever the rings, the round
+ * size and the number of rounds.  THE BITS DIFFER FROM THE RING'S, the stated
+ * price of opting in.
+ * max_block_bytes: bytes PER BLOCK, 0 = off (the default; then every call
+ * plans exactly as without this entry point); there is no maximum.
+ * round_bytes: the pipeline granularity, 0 = one whole one-shot slot, else a
+ * multiple of 16 of at most *round_cap (mccsCommReduceScatterWideStreamMax:
+ * one one-shot slot, oneshot_bytes rounded up to 64 KiB; 0 without one-shot
+ * slots, outside 2..8 ranks or without peer atomics).  Anything else is refused
+ * with mccsInvalidArgument, as is a max_block_bytes > 0 where *round_cap is 0;
+ * a call while the communicator has a group open or a call pending, with
+ * mccsInvalidUsage.  MCCS_RS_WIDE_STREAM_BYTES / MCCS_RS_WIDE_STREAM_ROUND_BYTES
+ * in the environment set the two when the communicator is created (the round
+ * clamped to the maximum and cut to a multiple of 16, at least 16).  EVERY RANK MUST SET THE
+ * SAME TWO VALUES: ranks that disagree run different rounds of one call and
+ * stall until the watchdog; this is not detected.
+ * A qualifying mccsReduceScatter (count > 0, 2 <= nranks <= 8) that is its
+ * communicator's only call of the launch and that the wide LL and one-shot
+ * limits of mccsCommSetReduceScatterWide leave takes this path within
+ * max_block_bytes (mccsCommLastAlgo reports MCCS_ALGO_WIDE_STREAM).  A larger
+ * one, one sharing a group with a second call of the communicator (it goes to
+ * the ring with its scalar), every other dtype, Prod / Max / Min and SumPostDiv
+ * plan as before.  In place is supported; ranks sharing a GPU are fused into
+ * one launch; the call may be captured into a HIP graph.  The node gate does
+ * not cover this path. */
+mccsResult_t mccsCommSetReduceScatterWideStream(mccsComm_t comm, size_t max_block_bytes, size_t round_bytes);
+mccsResult_t mccsCommReduceScatterWideStreamMax(mccsComm_t comm, size_t *round_cap);
 /* Send / Recv: grouped point-to-point (torch's batch_isend_irecv; the pieces of
  * a Gather or Scatter).  mccsSend moves count * elem_bytes(dtype) bytes from
  * sendbuff to rank `peer`, mccsRecv receives as many from rank `peer` into
@@ -739,7 +773,8 @@ mccsResult_t mccsCommInfo(mccsComm_t comm, int *info7);
 mccsResult_t mccsCommRing(mccsComm_t comm, int ch, int *order);
 /* Algorithm of the comm's latest launch: MCCS_ALGO_RING, MCCS_ALGO_DIRECT
  * (two-shot), MCCS_ALGO_ONESHOT or MCCS_ALGO_LL (LL one-shot), or one of the
- * wide-accumulate AllReduce variants (mccsCommSetAllReduceWide) (-1 before the first). */
+ * wide-accumulate variants (mccsCommSetAllReduceWide and its siblings;
+ * MCCS_ALGO_WIDE_STREAM: mccsCommSetReduceScatterWideStream) (-1 before the first). */
 #define MCCS_ALGO_RING 0
 #define MCCS_ALGO_DIRECT 1
 #define MCCS_ALGO_ONESHOT 2
@@ -747,6 +782,7 @@ mccsResult_t mccsCommRing(mccsComm_t comm, int ch, int *order);
 #define MCCS_ALGO_WIDE_LL 4
 #define MCCS_ALGO_WIDE_ONESHOT 5
 #define MCCS_ALGO_WIDE_DIRECT 6
+#define MCCS_ALGO_WIDE_STREAM 7
 int mccsCommLastAlgo(mccsComm_t comm);
 /* 1 when the comm may run the direct kernel: a direct region was configured
  * and every device of the communicator can perform atomics on every other's

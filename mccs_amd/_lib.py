@@ -117,6 +117,8 @@ SIGNATURES: dict[str, tuple] = {
     "mccsCommAllReduceWideMax": (_c_int, [_c_void_p, _P(_c_size_t), _P(_c_size_t), _P(_c_size_t)]),
     "mccsCommSetReduceScatterWide": (_c_int, [_c_void_p, _c_size_t, _c_size_t]),
     "mccsCommReduceScatterWideMax": (_c_int, [_c_void_p, _P(_c_size_t), _P(_c_size_t)]),
+    "mccsCommSetReduceScatterWideStream": (_c_int, [_c_void_p, _c_size_t, _c_size_t]),
+    "mccsCommReduceScatterWideStreamMax": (_c_int, [_c_void_p, _P(_c_size_t)]),
     "mccsCommSetReduceWide": (_c_int, [_c_void_p, _c_size_t, _c_size_t]),
     "mccsCommReduceWideMax": (_c_int, [_c_void_p, _P(_c_size_t), _P(_c_size_t)]),
     "mccsCommSetRootedDirect": (_c_int, [_c_void_p, _c_size_t, _c_size_t, _c_size_t, _c_size_t]),

@@ -42,6 +42,7 @@ EXTRA_CFLAGS = {
     # (the host pass does not know the feature and says so in a note; it is ignored there)
     "direct_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "direct_wide_rs.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "direct_wide_stream.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

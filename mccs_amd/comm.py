@@ -187,11 +187,11 @@ class Communicator:
 
     def last_algo(self) -> str | None:
         """"ring", "direct" (two-shot), "oneshot" or "ll", or a wide-accumulate
-        variant ("wide-ll", "wide-oneshot", "wide-direct"): the algorithm of the
-        latest launch (None before one)."""
+        variant ("wide-ll", "wide-oneshot", "wide-direct", "wide-stream"): the
+        algorithm of the latest launch (None before one)."""
         a = _sig().mccsCommLastAlgo(self._h)
         return {0: "ring", 1: "direct", 2: "oneshot", 3: "ll", 4: "wide-ll", 5: "wide-oneshot",
-                6: "wide-direct"}.get(a)
+                6: "wide-direct", 7: "wide-stream"}.get(a)
 
     def direct_enabled(self) -> bool:
         """Whether AllReduces may take the direct kernel (a direct region is
@@ -348,6 +348,28 @@ class Communicator:
         _lib.check(_sig().mccsCommReduceScatterWideMax(self._h, ctypes.byref(ll_cap), ctypes.byref(cap)),
                    "mccsCommReduceScatterWideMax")
         return int(ll_cap.value), int(cap.value)
+
+    def set_reduce_scatter_wide_stream(self, max_block_bytes: int, round_bytes: int = 0) -> None:
+        """mccsCommSetReduceScatterWideStream: opts the communicator in to the
+        wide streamed ReduceScatter (max_block_bytes = 0: off, the default).  A
+        Float16 / BFloat16 reduce_scatter / reduce_scatter_avg of Sum or
+        PreMulSum that is the communicator's only call of its launch, that
+        set_reduce_scatter_wide's limits leave and whose block is within
+        max_block_bytes (any size) moves through the one-shot slot in rounds
+        of round_bytes (0: the whole slot; else a multiple of 16 of at most
+        reduce_scatter_wide_stream_max()), summed in binary32 in rank order and
+        rounded once: last_algo() == "wide-stream", the wide all_reduce's
+        block whatever the rounds.  Every rank must set the same two values."""
+        rc = _sig().mccsCommSetReduceScatterWideStream(self._h, int(max_block_bytes), int(round_bytes))
+        _lib.check(rc, "mccsCommSetReduceScatterWideStream")
+
+    def reduce_scatter_wide_stream_max(self) -> int:
+        """mccsCommReduceScatterWideStreamMax: the largest round in bytes (one
+        one-shot slot); 0 where the streamed path cannot be used."""
+        cap = ctypes.c_size_t(0)
+        _lib.check(_sig().mccsCommReduceScatterWideStreamMax(self._h, ctypes.byref(cap)),
+                   "mccsCommReduceScatterWideStreamMax")
+        return int(cap.value)
 
     def set_reduce_wide(self, ll_bytes: int = 0, nbytes: int = 0) -> None:
         """mccsCommSetReduceWide: as set_reduce_scatter_wide for reduce, the

@@ -1042,6 +1042,37 @@ extern "C" mccsResult_t mccsCommReduceWideMax(mccsComm_t comm, size_t* ll_cap, s
   return rs_wide_max(comm, "mccsCommReduceWideMax", ll_cap, cap);
 }
 
+extern "C" mccsResult_t mccsCommReduceScatterWideStreamMax(mccsComm_t comm, size_t* round_cap) {
+  err_clear();
+  const Comm* c = (const Comm*)comm;
+  if (!c || !round_cap) MCCS_FAIL(mccsInvalidArgument, "mccsCommReduceScatterWideStreamMax: null communicator or output");
+  *round_cap = c->connected ? rs_direct_cap(c) : 0;
+  return mccsSuccess;
+}
+
+extern "C" mccsResult_t mccsCommSetReduceScatterWideStream(mccsComm_t comm, size_t max_block_bytes, size_t round_bytes) {
+  err_clear();
+  StepScope st("mccsCommSetReduceScatterWideStream");
+  Comm* c = (Comm*)comm;
+  if (!c || !c->connected) MCCS_FAIL(mccsInvalidUsage, "the communicator is not connected");
+  if (g_group.depth > 0 || c->plan_pending)
+    MCCS_FAIL(mccsInvalidUsage, "the communicator has a group open or a call pending: set the limits between launches");
+  const size_t cap = rs_direct_cap(c);
+  if (max_block_bytes > 0 && cap == 0)
+    MCCS_FAIL(mccsInvalidArgument, "max_block_bytes %zu: there is no one-shot slot to stream a block through (no "
+              "one-shot slots or no peer atomics: the count-based path is closed here)", max_block_bytes);
+  if (round_bytes > cap)
+    MCCS_FAIL(mccsInvalidArgument, "round_bytes %zu is above the %zu bytes of a one-shot slot%s", round_bytes, cap,
+              cap ? "" : " (no one-shot slots or no peer atomics: the count-based path is closed here)");
+  if (round_bytes % 16)
+    MCCS_FAIL(mccsInvalidArgument, "round_bytes %zu is not a multiple of 16 (a round starts on a 16-byte pack; 0 = the "
+              "whole slot of %zu bytes)", round_bytes, cap);
+  c->rs_wide_stream_bytes = max_block_bytes;
+  c->rs_wide_stream_round = round_bytes;
+  rs_wide_stream_prepare(c);
+  return mccsSuccess;
+}
+
 extern "C" mccsResult_t mccsCommAllToAllRoute(mccsComm_t comm, int* info2) {
   const Comm* c = (const Comm*)comm;
   if (!c || !info2) return mccsInvalidArgument;

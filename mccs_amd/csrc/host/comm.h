@@ -337,6 +337,14 @@ struct Comm {
   // see it and runs direct_wide_rs_kernel / direct_wide_rd_kernel (LL, else
   // one-shot).  Every rank must set the same values.
   size_t rs_wide_ll_bytes = 0, rs_wide_bytes = 0, rd_wide_ll_bytes = 0, rd_wide_bytes = 0;
+  // Wide streamed ReduceScatter (direct_wide_stream.h).  The opt-in limit in
+  // bytes per block, without a cap (mccsCommSetReduceScatterWideStream;
+  // MCCS_RS_WIDE_STREAM_BYTES), 0 = off, and the bytes of one round (0 = one
+  // one-shot slot, else a multiple of 16 within it; MCCS_RS_WIDE_STREAM_ROUND_BYTES):
+  // a qualifying ReduceScatter the two limits above leave, and which is its
+  // comm's only call of the launch, is held likewise and runs
+  // direct_wide_stream_kernel.  Every rank must set the same values.
+  size_t rs_wide_stream_bytes = 0, rs_wide_stream_round = 0;
   // Direct Broadcast and Reduce (direct_rooted.h).  The four opt-in limits in
   // bytes of the whole buffer (mccsCommSetRootedDirect; MCCS_BC_DIRECT_BYTES /
   // MCCS_BC_LL_BYTES / MCCS_RD_DIRECT_BYTES / MCCS_RD_LL_BYTES at creation),
@@ -490,6 +498,9 @@ void ar_wide_prepare(const Comm* c);  // after the limits changed: probes the wi
 // reads MCCS_RS_WIDE_LL_BYTES / MCCS_RS_WIDE_BYTES / MCCS_RD_WIDE_LL_BYTES / MCCS_RD_WIDE_BYTES, clamped to the caps
 void rs_wide_read_env(Comm* c);
 void rs_wide_prepare(const Comm* c);  // after the limits changed: probes the eight kernels' co-residency once
+// Wide streamed ReduceScatter: reads MCCS_RS_WIDE_STREAM_BYTES (kept only where rs_direct_cap > 0) and
+// MCCS_RS_WIDE_STREAM_ROUND_BYTES (clamped to the cap, cut to a multiple of 16); called by rs_wide_read_env
+void rs_wide_stream_prepare(const Comm* c);  // probes the four streamed kernels' co-residency once
 mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_t>& user_streams);
 // ring.hip
 const void* ring_kernel_ptr(int func, int dtype, int op);
@@ -509,6 +520,8 @@ const void* direct_wide_kernel_ptr(int dtype, int op);
 // direct_wide_rs.hip (likewise)
 const void* direct_wide_rs_kernel_ptr(int dtype, int op);
 const void* direct_wide_rd_kernel_ptr(int dtype, int op);
+// direct_wide_stream.hip (likewise)
+const void* direct_wide_stream_kernel_ptr(int dtype, int op);
 hipError_t ring_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_flush_caches(hipStream_t st);
 

@@ -581,6 +581,14 @@ void rs_wide_read_env(Comm* c) {
   c->rd_wide_ll_bytes = read("MCCS_RD_WIDE_LL_BYTES", rs_ll_cap(c));
   c->rd_wide_bytes = read("MCCS_RD_WIDE_BYTES", rs_direct_cap(c));
   rs_wide_prepare(c);
+  // the streamed ReduceScatter's: a block limit without a cap (kept where the
+  // count-based path is open), a round within one one-shot slot, in 16-byte steps
+  c->rs_wide_stream_bytes = rs_direct_cap(c) > 0 ? read("MCCS_RS_WIDE_STREAM_BYTES", SIZE_MAX) : 0;
+  c->rs_wide_stream_round = read("MCCS_RS_WIDE_STREAM_ROUND_BYTES", rs_direct_cap(c)) & ~(size_t)15;
+  // (1 .. 15 is the smallest round, not 0 = the whole slot)
+  if (c->rs_wide_stream_round == 0 && read("MCCS_RS_WIDE_STREAM_ROUND_BYTES", rs_direct_cap(c)) > 0)
+    c->rs_wide_stream_round = 16;
+  rs_wide_stream_prepare(c);
 }
 
 // The wide mode an fp16 / bf16 call of `func` takes on this comm (-1: none),
@@ -594,6 +602,8 @@ static int wide_mode(const Comm* c, int func, size_t bytes) {
       return rd ? MCCS_DIRECT_WIDE_RD_LL : MCCS_DIRECT_WIDE_RS_LL;
     if (bytes <= (rd ? c->rd_wide_bytes : c->rs_wide_bytes) && bytes <= rs_direct_cap(c))
       return rd ? MCCS_DIRECT_WIDE_RD_ONE_SHOT : MCCS_DIRECT_WIDE_RS_ONE_SHOT;
+    // the streamed ReduceScatter takes what those two leave, at any size within its own limit
+    if (!rd && bytes <= c->rs_wide_stream_bytes && rs_direct_cap(c) > 0) return MCCS_DIRECT_WIDE_RS_STREAM;
     return -1;
   }
   if (func != mccsFuncAllReduce) return -1;
@@ -1068,6 +1078,7 @@ static bool direct_group(std::vector<Comm*>& comms, const std::vector<int>& idx)
         ck->ar_wide_bytes != c0->ar_wide_bytes || ck->direct.wide != c0->direct.wide ||
         ck->rs_wide_ll_bytes != c0->rs_wide_ll_bytes || ck->rs_wide_bytes != c0->rs_wide_bytes ||
         ck->rd_wide_ll_bytes != c0->rd_wide_ll_bytes || ck->rd_wide_bytes != c0->rd_wide_bytes ||
+        ck->rs_wide_stream_bytes != c0->rs_wide_stream_bytes || ck->rs_wide_stream_round != c0->rs_wide_stream_round ||
         ck->direct.op_arg != c0->direct.op_arg)  // one scalar for every rank slot (mccsDirectArgs.op_arg)
       return false;
   }
@@ -1441,11 +1452,13 @@ static mccsResult_t build_direct_rooted(std::vector<Comm*>& comms, const std::ve
 // over them), as coresident_rs_blocks: probed when a comm opts in
 // (ar_wide_prepare), not at a launch a stream may be capturing.
 // `rs`: the eight wide ReduceScatter / Reduce kernels (direct_wide_rs.h)
-// instead, cached apart, so opting in to them changes no AllReduce launch.
-static int coresident_wide_blocks(int device, int* ncu_out, bool rs = false) {
+// instead, cached apart, so opting in to them changes no AllReduce launch;
+// `stream`: the four streamed ReduceScatter kernels (direct_wide_stream.h),
+// cached apart again.
+static int coresident_wide_blocks(int device, int* ncu_out, bool rs = false, bool stream = false) {
   static std::mutex mu;
-  static std::map<std::tuple<unsigned, int, bool>, std::pair<int, int>> cache;  // (runtime, device, family) -> (blocks, CUs)
-  const auto key = std::make_tuple(rt_generation(), device, rs);
+  static std::map<std::tuple<unsigned, int, int>, std::pair<int, int>> cache;  // (runtime, device, family) -> (blocks, CUs)
+  const auto key = std::make_tuple(rt_generation(), device, stream ? 2 : rs ? 1 : 0);
   {
     std::lock_guard<std::mutex> lk(mu);
     auto it = cache.find(key);
@@ -1460,8 +1473,10 @@ static int coresident_wide_blocks(int device, int* ncu_out, bool rs = false) {
   int best = 1 << 30;
   for (int dt : {(int)mccsFloat16, (int)mccsBfloat16})
     for (int op : {(int)mccsDevSum, (int)mccsDevPreMulSum}) {
-      for (const void* fn : {rs ? direct_wide_rs_kernel_ptr(dt, op) : direct_wide_kernel_ptr(dt, op),
-                             rs ? direct_wide_rd_kernel_ptr(dt, op) : nullptr}) {
+      for (const void* fn : {stream ? direct_wide_stream_kernel_ptr(dt, op)
+                             : rs   ? direct_wide_rs_kernel_ptr(dt, op)
+                                    : direct_wide_kernel_ptr(dt, op),
+                             rs && !stream ? direct_wide_rd_kernel_ptr(dt, op) : nullptr}) {
         int per_cu = 0;
         if (!fn) continue;
         if (rt().BlocksPerCu(&per_cu, fn, MCCS_DIRECT_THREADS) != hipSuccess) return 0;  // not cached
@@ -1486,11 +1501,19 @@ void rs_wide_prepare(const Comm* c) {
     (void)coresident_wide_blocks(c->device, &ncu, /*rs=*/true);
 }
 
+void rs_wide_stream_prepare(const Comm* c) {
+  int ncu = 0;
+  if (c->rs_wide_stream_bytes > 0) (void)coresident_wide_blocks(c->device, &ncu, /*rs=*/true, /*stream=*/true);
+}
+
 // The wide launch's arguments (direct_group checked the shape, the scalar and
 // the root included).  No ring walk: nch / nthr_ref / idx2rank stay 0, the sum
 // runs in rank order.  owned[] is the AllReduce two-shot's contiguous split
 // (MCCS_WIDE_SHARE); every other mode leaves it 0.  ReduceScatter: count is
-// one block; Reduce: the whole buffer, with the root.
+// one block; Reduce: the whole buffer, with the root.  The streamed
+// ReduceScatter adds the round: round_elems from the comm's round bytes (0: the
+// whole slot) and rounds = ceil(count / round_elems); its workgroups and pieces
+// are sized from ONE round.
 static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vector<int>& idx, mccsDirectArgs* da,
                                       unsigned* grid_x) {
   const Comm* c0 = comms[idx[0]];
@@ -1514,6 +1537,15 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
   da->root = rd ? (uint32_t)c0->direct.root : 0;
   const bool ll = mode == MCCS_DIRECT_WIDE_LL || mode == MCCS_DIRECT_WIDE_RS_LL || mode == MCCS_DIRECT_WIDE_RD_LL;
   const bool oneshot = mode == MCCS_DIRECT_WIDE_ONE_SHOT;
+  const bool stream = mode == MCCS_DIRECT_WIDE_RS_STREAM;
+  size_t rbytes = nbytes;  // the bytes of one block a data phase moves: the streamed mode's, of one round
+  if (stream) {
+    const size_t round = c0->rs_wide_stream_round ? c0->rs_wide_stream_round : c0->layout.oneshot_slot;
+    if (round < 16 || round % 16 || round > c0->layout.oneshot_slot) return mccsInternalError;  // api.cpp checked it
+    da->round_elems = (uint32_t)(round / esize);
+    da->rounds = (da->count + da->round_elems - 1) / da->round_elems;
+    rbytes = std::min(nbytes, round);
+  }
   da->nranks = (uint32_t)n;
   da->buff_size = (uint32_t)c0->cfg.buffer_size;
   da->fence_mode = c0->kcfg.fence_mode;
@@ -1548,9 +1580,9 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
   // whole input (one-shot; a Reduce sender), of the n-1 foreign shares
   // (two-shot) or of the n-1 foreign blocks (ReduceScatter), or (LL) one 8-byte
   // word of phase 1 per thread; capped by co-residency.
-  const size_t scatter = rs ? nbytes * (size_t)(n - 1) : (oneshot || rd) ? nbytes : nbytes - nbytes / (size_t)n;
+  const size_t scatter = rs ? rbytes * (size_t)(n - 1) : (oneshot || rd) ? nbytes : nbytes - nbytes / (size_t)n;
   int ncu = 0;
-  const int cap = coresident_wide_blocks(c0->device, &ncu, rs || rd);
+  const int cap = coresident_wide_blocks(c0->device, &ncu, rs || rd, stream);
   if (ncu <= 0) ncu = cap;
   long g = std::min<long>((long)((scatter + 4095) / 4096), c0->direct_blocks);
   const size_t ll_words = (rs ? (size_t)(n - 1) : 1) * ((nbytes + 7) / 8);
@@ -1570,7 +1602,7 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
     return (uint32_t)(p / esize);
   };
   da->piece = piece(scatter);
-  da->piece2 = piece(oneshot || rs || rd ? nbytes : nbytes / (size_t)n + 1);
+  da->piece2 = piece(rs ? rbytes : oneshot || rd ? nbytes : nbytes / (size_t)n + 1);
   for (size_t k = 0; k < idx.size(); ++k) {
     Comm* ck = comms[idx[k]];
     ck->plan_direct = false;
@@ -1773,7 +1805,8 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
       if (c0->direct.wide) {
         const int func = c0->plan_func, dt = c0->plan_dtype, op = c0->plan_op;  // before the build clears the plan
         MCCS_CHECK(build_direct_wide(comms, idx, &da, &grid));
-        fn = func == mccsFuncReduceScatter ? direct_wide_rs_kernel_ptr(dt, op)
+        fn = da.mode == MCCS_DIRECT_WIDE_RS_STREAM ? direct_wide_stream_kernel_ptr(dt, op)
+             : func == mccsFuncReduceScatter     ? direct_wide_rs_kernel_ptr(dt, op)
              : func == mccsFuncReduce      ? direct_wide_rd_kernel_ptr(dt, op)
                                            : direct_wide_kernel_ptr(dt, op);
       } else if (c0->plan_func == mccsFuncReduceScatter) {
@@ -1914,6 +1947,7 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
                                            da.mode == MCCS_DIRECT_WIDE_RD_ONE_SHOT
                                      ? MCCS_ALGO_WIDE_ONESHOT
                                  : da.mode == MCCS_DIRECT_WIDE_TWO_SHOT ? MCCS_ALGO_WIDE_DIRECT
+                                 : da.mode == MCCS_DIRECT_WIDE_RS_STREAM ? MCCS_ALGO_WIDE_STREAM
                                  : da.mode == MCCS_DIRECT_TWO_SHOT ? MCCS_ALGO_DIRECT
                                  : da.mode == MCCS_DIRECT_LL_ONE_SHOT || da.mode == MCCS_DIRECT_LL_AG ||
                                            da.mode == MCCS_DIRECT_RS_LL || da.mode == MCCS_DIRECT_RD_LL ||

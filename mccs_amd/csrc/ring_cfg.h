@@ -353,6 +353,84 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 // paragraphs above rest on: parity reuse and the single E_IN word hold across
 // any mix of these with every other direct launch and under every change of
 // root.
+//
+// Wide streamed ReduceScatter (direct_wide_stream.h, opt-in:
+// mccsCommSetReduceScatterWideStream; fp16 and bf16, Sum and PreMulSum) moves a
+// block of ANY size through the same one-shot slots and adds none.  A launch
+// runs K = ceil(recvcount / B) rounds, B = round_elems (a multiple of 8 that
+// fits one slot).  Round k has the sequence number seq0 + k (seq0 = LAUNCHES +
+// 1) and is, on the wire, one wide one-shot ReduceScatter of the elements
+// [k B, min((k+1) B, recvcount)) of every block: sender s writes them into t's
+// slot [parity (seq0 + k) & 1][s] at the offset within the round, and t's
+// IN_CNT(s) grows by the round's count.  The launch ends with LAUNCHES += K and E_IN
+// += recvcount (every sender added every round's count on every owner, so the
+// single word stays every line's running total); E_OUT and E_SELF stay.  With
+// K = 1 that is the wide RS one-shot's state word for word.  A workgroup runs
+// send(0); for k = 1 .. K: { send(k) if k < K; fold(k-1) }, so round k's bytes
+// are in flight while round k-1 is folded -- and a launch now crosses its own
+// parities, which the launch-boundary argument above does not cover.  Three new
+// kinds of line in the control block (zero at init with it) close the gap:
+//   SEND_DONE(q), q = round seq & 3: u32, this rank's workgroups that finished
+//     sending that round.  IN_CNT is one running total per sender, and the
+//     workgroups of one rank may be a round apart; if each added its own pieces
+//     (as direct_count_out does in the one-launch kernels, whose count is one
+//     total per launch), elements one workgroup counted for round k would stand
+//     in for elements a slower one has not yet written for round k-1.  So a
+//     round's count is INDIVISIBLE: EVERY workgroup, with or without pieces in
+//     the round, drains its stores (cached arenas: and writes them back, as
+//     direct_count_out) and arrives; the last to arrive puts the word back to
+//     0, adds the round's WHOLE length to IN_CNT(s) of every owner, and drains.
+//     Its add follows every workgroup's drained stores of round k, and the
+//     same holds for the adds of rounds < k, each made before some workgroup
+//     could arrive at round k.  Hence IN_CNT(s) >= E_IN + k B + len_k at t
+//     means ALL of rounds 0 .. k from s are in t's slots.
+//   ROUND_DONE(q), q = round seq & 3: u32, this rank's workgroups that finished
+//     folding that round.  EVERY workgroup, with or without pieces in the
+//     round, waits for the round's in-count, folds its pieces, drains its loads
+//     and arrives; the last to arrive puts the word back to 0 and
+//   ACK(t): u64 in every peer's block, written only by rank t -- stores the
+//     round's seq there and drains.  Rounds 0 .. K-2 are acknowledged; nobody
+//     waits for an ack of round K-1.  The value only grows (LAUNCHES only
+//     grows; the last arriver of round k+1 arrives after the last arriver of
+//     round k drained its stores), so a value left by an earlier streamed
+//     launch never satisfies a later wait.
+// The three hazards:
+//   1. within a launch: s writes round k+2 into the parity of round k only
+//      after it polled ACK(t) >= seq0 + k on its own block for every peer t,
+//      i.e. after EVERY workgroup of t finished reading round k.  (t's
+//      in-count of round k+1 would not show that: workgroups send ahead of
+//      folding.)  Every workgroup polls before every round k >= 2, whether or
+//      not it holds a piece of it.
+//   2. against the previous launch L-1 of any kind, which used round 1's
+//      parity: before round 1 every workgroup of s waits for the in-count of
+//      round 0 from every peer t, which t adds only inside its launch L, i.e.
+//      after its launch L-1 ended.  Round 0's parity is launch L-2's and the
+//      one-shot argument covers it (s finished L-1, which needed t's hand-off
+//      of L-1, made after t finished L-2).
+//   3. against the next launch of any kind, whose first write goes to the
+//      parity of round K-2: with K >= 2 every workgroup polls ACK(t) >= seq0 +
+//      K-2 for every peer before the kernel ends, so every peer finished
+//      reading that parity.  The parity of round K-1 is written next in the
+//      launch after, and the one-shot argument holds for it: every ordered pair
+//      hands off in the next launch, which t enters only after this one ended.
+// Four ROUND_DONE words suffice: a workgroup arrives at round k only after the
+// in-count of round k, which the peers add only after this rank's ack of round
+// k-2, i.e. after every workgroup of this rank arrived at round k-2; so at most
+// rounds k-1, k, k+1 are counted at once, and round k+4 finds the word its
+// last arriver of round k put back to 0 and drained.  Four SEND_DONE words
+// suffice likewise: a workgroup sends round k >= 2 only after every peer's ack
+// of round k-2, which a peer gives after folding it, i.e. after this rank's
+// count of round k-2, i.e. after every workgroup of this rank arrived there.
+// No workgroup waits for a workgroup of its own rank (arriving on SEND_DONE or
+// ROUND_DONE is an add, not a wait), and the waits form no cycle: round j
+// completes (every workgroup of every rank folded it and arrived) given the
+// counts of round j, i.e. every workgroup of every rank reaching the end of
+// send(j), which needs its fold of round j-2 and the acks of round j-2 (and,
+// j = 1, the in-counts of round 0), and given that every workgroup passed
+// send(j+1), which needs the acks of round j-1; both are completions of earlier
+// rounds, so induction on j from rounds 0 and 1 (which wait for no ack) ends.
+// Every wait is direct_wait: it polls the abort flag and the watchdog and
+// returns on either.
 #define MCCS_DIRECT_MAX_RANKS 8
 #define MCCS_DIRECT_CTRL_BYTES 65536
 // u64, added to by sender s; a rank's own line IN_CNT(rank) counts its own
@@ -369,6 +447,12 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 #define MCCS_DIRECT_ST_E_SELF (2 + MCCS_DIRECT_MAX_RANKS)  // elements this rank counted to itself (in-place one-shot)
 #define MCCS_DIRECT_ST_WORDS (3 + MCCS_DIRECT_MAX_RANKS)
 #define MCCS_DIRECT_DONE 4096                                          // u32: workgroups arrived in the launch
+// wide streamed ReduceScatter (above): u64, the latest round seq rank t acknowledged to this rank; u32, this
+// rank's workgroups that finished folding the round of seq & 3
+#define MCCS_DIRECT_ACK(t) (8192 + (t) * MCCS_FLAG_LINE_BYTES)
+#define MCCS_DIRECT_ROUND_DONE(q) (12288 + (q) * MCCS_FLAG_LINE_BYTES)
+// u32, this rank's workgroups that finished sending the round of seq & 3 (the last one adds the round's count)
+#define MCCS_DIRECT_SEND_DONE(q) (16384 + (q) * MCCS_FLAG_LINE_BYTES)
 #define MCCS_DIRECT_SLOTS (MCCS_DIRECT_MAX_RANKS + 1)                  // two-shot slots
 #define MCCS_DIRECT_THREADS 512
 #define MCCS_DIRECT_TWO_SHOT 0
@@ -396,6 +480,8 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 #define MCCS_DIRECT_WIDE_RS_ONE_SHOT 15  // ReduceScatter through the one-shot slots, counted on IN_CNT
 #define MCCS_DIRECT_WIDE_RD_LL 16        // Reduce through the root's LL lines
 #define MCCS_DIRECT_WIDE_RD_ONE_SHOT 17  // Reduce through the root's one-shot slots, counted on IN_CNT
+// wide streamed ReduceScatter (direct_wide_stream.h; count = recvcount of any size, rounds x round_elems)
+#define MCCS_DIRECT_WIDE_RS_STREAM 18    // rounds through the one-shot slots, counted on IN_CNT, acknowledged on ACK
 
 struct mccsDirectRank {  // one rank slot of a direct launch (blockIdx.y)
   const void* send;
@@ -418,7 +504,7 @@ struct mccsDirectArgs {
   uint64_t timeout_ticks;  // s_memrealtime ticks; 0 = never
   uint32_t nranks, nch, nthr_ref, buff_size;  // the ring walk this launch reproduces
   uint32_t fence_mode;                        // MCCS_FENCE_*
-  uint32_t mode;                              // MCCS_DIRECT_* above (RS: direct_rs_kernel only; RD / BC: direct_rooted.h's kernels only; WIDE: direct_wide_kernel only; WIDE_RS / WIDE_RD: direct_wide_rs.h's kernels only)
+  uint32_t mode;                              // MCCS_DIRECT_* above (RS: direct_rs_kernel only; RD / BC: direct_rooted.h's kernels only; WIDE: direct_wide_kernel only; WIDE_RS / WIDE_RD: direct_wide_rs.h's kernels only; WIDE_RS_STREAM: direct_wide_stream_kernel only)
   uint32_t piece;                             // elements per piece of the scatter / gather phases
   uint32_t piece2;                            // elements per piece of the reduction phase
   uint32_t no_guard;                          // 1: skip the launch guard (test hook only)
@@ -426,7 +512,10 @@ struct mccsDirectArgs {
   uint64_t guard_order;                       // rank slots by guard address, 4 bits each (launch_guard.h)
   uint64_t owned[MCCS_DIRECT_MAX_RANKS];      // elements of the walk's chunks each rank owns (wide two-shot: of its share)
   uint8_t idx2rank[MCCS_MAX_NCHANNELS][MCCS_DIRECT_MAX_RANKS];  // rank at ring index k of channel bid
-  uint64_t op_arg;  // the wide modes: the PreMulSum scalar (T in the low bits); else 0 (last: the fields above keep their place)
+  uint64_t op_arg;  // the wide modes: the PreMulSum scalar (T in the low bits); else 0 (the fields above keep their place)
+  uint64_t rounds;       // WIDE_RS_STREAM: K = ceil(count / round_elems) >= 1; else 0
+  uint32_t round_elems;  // WIDE_RS_STREAM: elements of one round (a multiple of 8, at most one one-shot slot); else 0
+  uint32_t pad4;
 };
 #ifdef __cplusplus
 static_assert(sizeof(mccsDirectArgs) <= 4096, "direct launch arguments must stay within 4 KiB");

@@ -28,6 +28,11 @@ The wide-accumulate ReduceScatter (size = bytes per block) or Reduce (the
 buffer, the root rotating; mccsCommSetReduceScatterWide / mccsCommSetReduceWide)
 timed the same way: Sum beside the ring-order direct body of the same size,
 the average (PreMulSum) beside the ring, its only other path.
+  python tools/direct_bench.py --wide --reduce-scatter --stream --dtype bfloat16 [--n 2 4 8] [--sizes-kib 1024 4096 16384]
+The wide streamed ReduceScatter (mccsCommSetReduceScatterWideStream, whole-slot
+rounds of 1 MiB) at blocks of 1x, 4x and 16x the slot, timed the same way
+beside the ring of the same size and the same bytes as a host-issued sequence
+of slot-sized wide one-shot launches.
 """
 import argparse
 import json
@@ -320,6 +325,75 @@ def wide_rs_mode(args, torch, C, st, dt, code, es, rooted):
                       "dtype": args.dtype, "calls": args.calls, "regions": args.regions, "rows": rows}), flush=True)
 
 
+def wide_stream_mode(args, torch, C, st, dt, code, es):
+    """--wide --reduce-scatter --stream: per block size (1x, 4x, 16x the 1 MiB
+    one-shot slot) the ring ReduceScatter ("ring": where such a block goes
+    without the opt-in), the streamed kernel ("stream", rounds of one slot) and
+    the same bytes as K host-issued wide one-shot launches of one slot each
+    ("split": launch j reduces n blocks of one slot lying one after another, so
+    the layout differs and the bytes do not).  Eager regions alternate between
+    the three."""
+    import statistics
+
+    assert es == 2, "--wide times float16 / bfloat16"
+    slot = 1 << 20
+    sizes = args.sizes_kib if args.sizes_kib != DEFAULT_SIZES_KIB else [1024, 4096, 16384]
+    rows = []
+    for n in args.n:
+        cfg = C.CommConfig(ll_bytes=-1, oneshot_bytes=slot, direct_bytes=-1)
+        sets = {a: C.init_all([0] * n, cfg) for a in ("ring", "stream", "split")}
+        for c in sets["stream"]:
+            assert c.reduce_scatter_wide_stream_max() == slot
+            c.set_reduce_scatter_wide_stream(max(sizes) << 10, 0)
+        for c in sets["split"]:
+            c.set_reduce_scatter_wide(0, slot)
+        want = {"ring": "ring", "stream": "wide-stream", "split": "wide-oneshot"}
+        for kib in sizes:
+            nbytes = kib << 10
+            cnt, part, k = nbytes // es, slot // es, nbytes // slot
+            assert k * slot == nbytes, "--stream block sizes are multiples of the 1 MiB slot"
+            xs = [torch.randn(cnt * n, device="cuda").to(dt) for _ in range(n)]
+            ys = [torch.empty(cnt, dtype=dt, device="cuda") for _ in xs]
+            row = {"n": n, "func": "reducescatter", "block_bytes": nbytes, "slot_bytes": slot, "rounds": k}
+
+            def once(a):
+                for j in range(k if a == "split" else 1):
+                    with C.group():
+                        for r, c in enumerate(sets[a]):
+                            if a == "split":
+                                C.reduce_scatter(c, xs[r][j * n * part:], ys[r][j * part:], part, code, 0, stream=st)
+                            else:
+                                C.reduce_scatter(c, xs[r], ys[r], cnt, code, 0, stream=st)
+
+            for a in sets:  # warm-up: every kernel's code object
+                for _ in range(5):
+                    once(a)
+                st.synchronize()
+                assert sets[a][0].last_algo() == want[a], (a, sets[a][0].last_algo())
+            us = {a: [] for a in sets}
+            for _ in range(args.regions):
+                for a in sets:  # the variants alternate region by region
+                    t0 = time.perf_counter()
+                    for _ in range(args.calls):
+                        once(a)
+                    st.synchronize()
+                    us[a].append((time.perf_counter() - t0) / args.calls * 1e6)
+            for a in sets:
+                row[a + "_us"] = round(statistics.median(us[a]), 2)
+                row[a + "_min_us"], row[a + "_max_us"] = round(min(us[a]), 2), round(max(us[a]), 2)
+                for c in sets[a]:
+                    c.sync()
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            del xs, ys
+        torch.cuda.synchronize()
+        for comms in sets.values():
+            for c in comms:
+                c.destroy()
+    print(json.dumps({"tool": "direct_bench", "collective": "reducescatter-wide-stream", "dtype": args.dtype,
+                      "calls": args.calls, "regions": args.regions, "rows": rows}), flush=True)
+
+
 DEFAULT_SIZES_KIB = [32, 128, 512, 2048, 8192, 32768]
 
 
@@ -349,6 +423,9 @@ def main():
                          "ring-order LL / one-shot / two-shot body of the same size; with --reduce-scatter or --rooted: "
                          "the wide ReduceScatter / Reduce (1 KiB to 1 MiB) against the ring-order direct body, and its "
                          "average against the ring")
+    ap.add_argument("--stream", action="store_true",
+                    help="with --wide --reduce-scatter: the wide streamed ReduceScatter at 1x, 4x and 16x the one-shot "
+                         "slot against the ring and a host-issued sequence of slot-sized wide one-shot launches")
     ap.add_argument("--regions", type=int, default=5, help="--rooted, --wide: timed regions of --calls calls per variant")
     args = ap.parse_args()
     dt = getattr(torch, args.dtype)
@@ -356,6 +433,9 @@ def main():
     es = torch.empty(0, dtype=dt).element_size()
     rows = []
     st = side_stream(torch, 0, slot=1)
+    if args.wide and args.reduce_scatter and args.stream:
+        wide_stream_mode(args, torch, C, st, dt, code, es)
+        return
     if args.wide and (args.reduce_scatter or args.rooted):
         wide_rs_mode(args, torch, C, st, dt, code, es, args.rooted)
         return
