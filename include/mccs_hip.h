@@ -643,6 +643,41 @@ mccsResult_t mccsCommReduceWideMax(mccsComm_t comm, size_t *ll_cap, size_t *cap)
  * not cover this path. */
 mccsResult_t mccsCommSetReduceScatterWideStream(mccsComm_t comm, size_t max_block_bytes, size_t round_bytes);
 mccsResult_t mccsCommReduceScatterWideStreamMax(mccsComm_t comm, size_t *round_cap);
+/* The wide streamed AllReduce: the wide AllReduce's contract
+ * (mccsCommSetAllReduceWide) for a buffer of ANY size, for mccsFloat16 and
+ * mccsBfloat16 with Sum or PreMulSum (so mccsAvgOp).  One kernel runs scatter,
+ * fold and gather in rounds: rank t owns a contiguous share; round i of every
+ * foreign share goes to its owner's one-shot slot while the owner sums round
+ * i-1 in binary32 in RANK order 0 .. n-1, rounds once and writes the result to
+ * its output and to a half of every peer's two-shot in slot, from where round
+ * i-2 is copied out.  Every rank gets the same bits -- what the wide LL,
+ * one-shot and two-shot bodies give for a size that fits both -- whatever the
+ * rings, the round size and the number of rounds.  THE BITS DIFFER FROM THE
+ * RING'S, the stated price of opting in.
+ * max_bytes: bytes of the whole buffer, 0 = off (the default; then every call
+ * plans exactly as without this entry point); there is no maximum.
+ * round_bytes: bytes of one round of one share, 0 = *round_cap, else a
+ * multiple of 16 of at most *round_cap (mccsCommAllReduceWideStreamMax: the
+ * smaller of one one-shot slot and half a two-shot slot cut to 16 bytes; 0
+ * without either kind of slot, outside 2..8 ranks, without peer atomics or on
+ * an unconnected communicator).  Anything else is refused with
+ * mccsInvalidArgument, as is a max_bytes > 0 where *round_cap is 0; a call
+ * while the communicator has a group open or a call pending, with
+ * mccsInvalidUsage.  MCCS_AR_WIDE_STREAM_BYTES / MCCS_AR_WIDE_STREAM_ROUND_BYTES
+ * in the environment set the two when the communicator is created (the round
+ * clamped to the maximum and cut to a multiple of 16, at least 16).  EVERY RANK
+ * MUST SET THE SAME TWO VALUES; this is not detected.
+ * A qualifying mccsAllReduce of more than 8 * nranks * (nranks - 1) elements
+ * (every rank then owns one) that is its communicator's only call of the
+ * launch and that the three limits of mccsCommSetAllReduceWide leave takes
+ * this path within max_bytes (mccsCommLastAlgo reports MCCS_ALGO_WIDE_STREAM).
+ * A larger or smaller one, one sharing a group with a second call of the
+ * communicator (it goes to the ring with its scalar), every other dtype, Prod /
+ * Max / Min and SumPostDiv plan as before.  In place is supported; ranks
+ * sharing a GPU are fused into one launch; the call may be captured into a HIP
+ * graph.  The node gate does not cover this path. */
+mccsResult_t mccsCommSetAllReduceWideStream(mccsComm_t comm, size_t max_bytes, size_t round_bytes);
+mccsResult_t mccsCommAllReduceWideStreamMax(mccsComm_t comm, size_t *round_cap);
 /* Send / Recv: grouped point-to-point (torch's batch_isend_irecv; the pieces of
  * a Gather or Scatter).  mccsSend moves count * elem_bytes(dtype) bytes from
  * sendbuff to rank `peer`, mccsRecv receives as many from rank `peer` into
@@ -774,7 +809,8 @@ mccsResult_t mccsCommRing(mccsComm_t comm, int ch, int *order);
 /* Algorithm of the comm's latest launch: MCCS_ALGO_RING, MCCS_ALGO_DIRECT
  * (two-shot), MCCS_ALGO_ONESHOT or MCCS_ALGO_LL (LL one-shot), or one of the
  * wide-accumulate variants (mccsCommSetAllReduceWide and its siblings;
- * MCCS_ALGO_WIDE_STREAM: mccsCommSetReduceScatterWideStream) (-1 before the first). */
+ * MCCS_ALGO_WIDE_STREAM: mccsCommSetReduceScatterWideStream,
+ * mccsCommSetAllReduceWideStream) (-1 before the first). */
 #define MCCS_ALGO_RING 0
 #define MCCS_ALGO_DIRECT 1
 #define MCCS_ALGO_ONESHOT 2

@@ -115,6 +115,8 @@ SIGNATURES: dict[str, tuple] = {
     "mccsCommReduceScatterDirectMax": (_c_int, [_c_void_p, _P(_c_size_t), _P(_c_size_t)]),
     "mccsCommSetAllReduceWide": (_c_int, [_c_void_p, _c_size_t, _c_size_t, _c_size_t]),
     "mccsCommAllReduceWideMax": (_c_int, [_c_void_p, _P(_c_size_t), _P(_c_size_t), _P(_c_size_t)]),
+    "mccsCommSetAllReduceWideStream": (_c_int, [_c_void_p, _c_size_t, _c_size_t]),
+    "mccsCommAllReduceWideStreamMax": (_c_int, [_c_void_p, _P(_c_size_t)]),
     "mccsCommSetReduceScatterWide": (_c_int, [_c_void_p, _c_size_t, _c_size_t]),
     "mccsCommReduceScatterWideMax": (_c_int, [_c_void_p, _P(_c_size_t), _P(_c_size_t)]),
     "mccsCommSetReduceScatterWideStream": (_c_int, [_c_void_p, _c_size_t, _c_size_t]),

@@ -371,6 +371,28 @@ class Communicator:
                    "mccsCommReduceScatterWideStreamMax")
         return int(cap.value)
 
+    def set_all_reduce_wide_stream(self, max_bytes: int, round_bytes: int = 0) -> None:
+        """mccsCommSetAllReduceWideStream: opts the communicator in to the wide
+        streamed AllReduce (max_bytes = 0: off, the default).  A Float16 /
+        BFloat16 all_reduce / all_reduce_avg of Sum or PreMulSum that is the
+        communicator's only call of its launch, that set_all_reduce_wide's
+        limits leave, of more than 8 n (n-1) elements and within max_bytes
+        (any size) runs scatter, binary32 fold in rank order and gather in
+        rounds of round_bytes per share inside one launch (0: the largest
+        round; else a multiple of 16 of at most all_reduce_wide_stream_max()):
+        last_algo() == "wide-stream", the wide all_reduce's bits whatever the
+        rounds.  Every rank must set the same two values."""
+        rc = _sig().mccsCommSetAllReduceWideStream(self._h, int(max_bytes), int(round_bytes))
+        _lib.check(rc, "mccsCommSetAllReduceWideStream")
+
+    def all_reduce_wide_stream_max(self) -> int:
+        """mccsCommAllReduceWideStreamMax: the largest round in bytes (one
+        one-shot slot and half a two-shot slot hold it); 0 where the streamed
+        path cannot be used."""
+        cap = ctypes.c_size_t(0)
+        _lib.check(_sig().mccsCommAllReduceWideStreamMax(self._h, ctypes.byref(cap)), "mccsCommAllReduceWideStreamMax")
+        return int(cap.value)
+
     def set_reduce_wide(self, ll_bytes: int = 0, nbytes: int = 0) -> None:
         """mccsCommSetReduceWide: as set_reduce_scatter_wide for reduce, the
         two limits in bytes of the whole buffer; the root receives the wide

@@ -998,6 +998,37 @@ extern "C" mccsResult_t mccsCommSetAllReduceWide(mccsComm_t comm, size_t ll_byte
   return mccsSuccess;
 }
 
+extern "C" mccsResult_t mccsCommAllReduceWideStreamMax(mccsComm_t comm, size_t* round_cap) {
+  err_clear();
+  const Comm* c = (const Comm*)comm;
+  if (!c || !round_cap) MCCS_FAIL(mccsInvalidArgument, "mccsCommAllReduceWideStreamMax: null communicator or output");
+  *round_cap = c->connected ? ar_wide_stream_cap(c) : 0;
+  return mccsSuccess;
+}
+
+extern "C" mccsResult_t mccsCommSetAllReduceWideStream(mccsComm_t comm, size_t max_bytes, size_t round_bytes) {
+  err_clear();
+  StepScope st("mccsCommSetAllReduceWideStream");
+  Comm* c = (Comm*)comm;
+  if (!c || !c->connected) MCCS_FAIL(mccsInvalidUsage, "the communicator is not connected");
+  if (g_group.depth > 0 || c->plan_pending)
+    MCCS_FAIL(mccsInvalidUsage, "the communicator has a group open or a call pending: set the limits between launches");
+  const size_t cap = ar_wide_stream_cap(c);
+  const char* closed = cap ? "" : " (no one-shot or two-shot slots, or no peer atomics: the count-based path is closed here)";
+  if (max_bytes > 0 && cap == 0)
+    MCCS_FAIL(mccsInvalidArgument, "max_bytes %zu: there are no slots to stream a buffer through%s", max_bytes, closed);
+  if (round_bytes > cap)
+    MCCS_FAIL(mccsInvalidArgument, "round_bytes %zu is above the %zu bytes of a one-shot slot and of half a two-shot "
+              "slot%s", round_bytes, cap, closed);
+  if (round_bytes % 16)
+    MCCS_FAIL(mccsInvalidArgument, "round_bytes %zu is not a multiple of 16 (a round starts on a 16-byte pack; 0 = the "
+              "largest round, %zu bytes)", round_bytes, cap);
+  c->ar_wide_stream_bytes = max_bytes;
+  c->ar_wide_stream_round = round_bytes;
+  ar_wide_stream_prepare(c);
+  return mccsSuccess;
+}
+
 // The wide ReduceScatter's (rd = false) and Reduce's (rd = true) two limits.
 static mccsResult_t set_rs_wide(mccsComm_t comm, bool rd, size_t ll_bytes, size_t bytes) {
   err_clear();

@@ -345,6 +345,15 @@ struct Comm {
   // comm's only call of the launch, is held likewise and runs
   // direct_wide_stream_kernel.  Every rank must set the same values.
   size_t rs_wide_stream_bytes = 0, rs_wide_stream_round = 0;
+  // Wide streamed AllReduce (direct_wide_stream_ar.h).  The opt-in limit in
+  // bytes of the whole buffer, without a cap (mccsCommSetAllReduceWideStream;
+  // MCCS_AR_WIDE_STREAM_BYTES), 0 = off, and the bytes of one round (0 =
+  // ar_wide_stream_cap, else a multiple of 16 within it;
+  // MCCS_AR_WIDE_STREAM_ROUND_BYTES): a qualifying AllReduce the three limits of
+  // ar_wide_* leave, of more than 8 n (n-1) elements (every rank then owns one)
+  // and its comm's only call of the launch, is held likewise and runs
+  // direct_wide_stream_ar_kernel.  Every rank must set the same values.
+  size_t ar_wide_stream_bytes = 0, ar_wide_stream_round = 0;
   // Direct Broadcast and Reduce (direct_rooted.h).  The four opt-in limits in
   // bytes of the whole buffer (mccsCommSetRootedDirect; MCCS_BC_DIRECT_BYTES /
   // MCCS_BC_LL_BYTES / MCCS_RD_DIRECT_BYTES / MCCS_RD_LL_BYTES at creation),
@@ -501,6 +510,11 @@ void rs_wide_prepare(const Comm* c);  // after the limits changed: probes the ei
 // Wide streamed ReduceScatter: reads MCCS_RS_WIDE_STREAM_BYTES (kept only where rs_direct_cap > 0) and
 // MCCS_RS_WIDE_STREAM_ROUND_BYTES (clamped to the cap, cut to a multiple of 16); called by rs_wide_read_env
 void rs_wide_stream_prepare(const Comm* c);  // probes the four streamed kernels' co-residency once
+// Wide streamed AllReduce: the largest round in bytes, min(one one-shot slot, half a two-shot slot cut to 16); 0
+// unless direct_ok and both kinds of slot exist.  ar_wide_read_env reads MCCS_AR_WIDE_STREAM_BYTES (kept only where
+// the cap > 0) and MCCS_AR_WIDE_STREAM_ROUND_BYTES (clamped to the cap, cut to a multiple of 16).
+size_t ar_wide_stream_cap(const Comm* c);
+void ar_wide_stream_prepare(const Comm* c);  // probes the four streamed AllReduce kernels' co-residency once
 mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_t>& user_streams);
 // ring.hip
 const void* ring_kernel_ptr(int func, int dtype, int op);
@@ -522,6 +536,8 @@ const void* direct_wide_rs_kernel_ptr(int dtype, int op);
 const void* direct_wide_rd_kernel_ptr(int dtype, int op);
 // direct_wide_stream.hip (likewise)
 const void* direct_wide_stream_kernel_ptr(int dtype, int op);
+// direct_wide_stream_ar.hip (likewise)
+const void* direct_wide_stream_ar_kernel_ptr(int dtype, int op);
 hipError_t ring_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_flush_caches(hipStream_t st);
 

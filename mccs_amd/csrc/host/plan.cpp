@@ -555,6 +555,11 @@ static bool rooted_takes_oneshot(const Comm* c, int func, size_t bytes) {
 // whole buffer where that has a block; two-shot: one two-shot slot holds the
 // buffer by element offset, and its counts are remote atomics.
 size_t ar_wide_cap(const Comm* c) { return c->direct_ok ? c->layout.direct_slot : 0; }
+// The streamed AllReduce's largest round: it scatters through one one-shot
+// slot and gathers through one half of a two-shot in slot, so it needs both.
+size_t ar_wide_stream_cap(const Comm* c) {
+  return std::min(rs_direct_cap(c), (ar_wide_cap(c) / 2) & ~(size_t)15);
+}
 
 void ar_wide_read_env(Comm* c) {
   auto read = [&](const char* name, size_t cap) {
@@ -566,6 +571,14 @@ void ar_wide_read_env(Comm* c) {
   c->ar_wide_oneshot_bytes = read("MCCS_AR_WIDE_ONESHOT_BYTES", rs_direct_cap(c));
   c->ar_wide_bytes = read("MCCS_AR_WIDE_BYTES", ar_wide_cap(c));
   ar_wide_prepare(c);
+  // the streamed AllReduce's, as the streamed ReduceScatter's below: a limit
+  // without a cap (kept where a round can exist), a round within the cap, in
+  // 16-byte steps (1 .. 15 is the smallest round, not 0 = the cap)
+  const size_t rcap = ar_wide_stream_cap(c);
+  c->ar_wide_stream_bytes = rcap > 0 ? read("MCCS_AR_WIDE_STREAM_BYTES", SIZE_MAX) : 0;
+  c->ar_wide_stream_round = read("MCCS_AR_WIDE_STREAM_ROUND_BYTES", rcap) & ~(size_t)15;
+  if (c->ar_wide_stream_round == 0 && read("MCCS_AR_WIDE_STREAM_ROUND_BYTES", rcap) > 0) c->ar_wide_stream_round = 16;
+  ar_wide_stream_prepare(c);
 }
 
 // The wide ReduceScatter's and Reduce's limits (direct_wide_rs.h): the direct
@@ -593,8 +606,11 @@ void rs_wide_read_env(Comm* c) {
 
 // The wide mode an fp16 / bf16 call of `func` takes on this comm (-1: none),
 // `bytes` being the whole buffer (AllReduce, Reduce) or one block
-// (ReduceScatter): LL wins over one-shot, one-shot over two-shot.  Every rank
-// sees the same limits and the same call, so every rank decides alike.
+// (ReduceScatter): LL wins over one-shot, one-shot over two-shot, two-shot over
+// the streamed AllReduce, which takes only a count > 8 n (n-1): then (n-1) q <
+// count for q = MCCS_WIDE_SHARE < count / n + 8, so every rank owns an element
+// (ring_cfg.h: the round-0 hand-off).  Every rank sees the same limits and the
+// same call, so every rank decides alike.
 static int wide_mode(const Comm* c, int func, size_t bytes) {
   if (func == mccsFuncReduceScatter || func == mccsFuncReduce) {
     const bool rd = func == mccsFuncReduce;
@@ -610,6 +626,9 @@ static int wide_mode(const Comm* c, int func, size_t bytes) {
   if (bytes <= c->ar_wide_ll_bytes && bytes <= rs_ll_cap(c)) return MCCS_DIRECT_WIDE_LL;
   if (bytes <= c->ar_wide_oneshot_bytes && bytes <= rs_direct_cap(c)) return MCCS_DIRECT_WIDE_ONE_SHOT;
   if (bytes <= c->ar_wide_bytes && bytes <= ar_wide_cap(c)) return MCCS_DIRECT_WIDE_TWO_SHOT;
+  if (bytes <= c->ar_wide_stream_bytes && ar_wide_stream_cap(c) > 0 &&
+      bytes / 2 > (size_t)(8 * c->nranks * (c->nranks - 1)))  // (2-byte elements)
+    return MCCS_DIRECT_WIDE_AR_STREAM;
   return -1;
 }
 
@@ -1079,6 +1098,7 @@ static bool direct_group(std::vector<Comm*>& comms, const std::vector<int>& idx)
         ck->rs_wide_ll_bytes != c0->rs_wide_ll_bytes || ck->rs_wide_bytes != c0->rs_wide_bytes ||
         ck->rd_wide_ll_bytes != c0->rd_wide_ll_bytes || ck->rd_wide_bytes != c0->rd_wide_bytes ||
         ck->rs_wide_stream_bytes != c0->rs_wide_stream_bytes || ck->rs_wide_stream_round != c0->rs_wide_stream_round ||
+        ck->ar_wide_stream_bytes != c0->ar_wide_stream_bytes || ck->ar_wide_stream_round != c0->ar_wide_stream_round ||
         ck->direct.op_arg != c0->direct.op_arg)  // one scalar for every rank slot (mccsDirectArgs.op_arg)
       return false;
   }
@@ -1453,12 +1473,13 @@ static mccsResult_t build_direct_rooted(std::vector<Comm*>& comms, const std::ve
 // (ar_wide_prepare), not at a launch a stream may be capturing.
 // `rs`: the eight wide ReduceScatter / Reduce kernels (direct_wide_rs.h)
 // instead, cached apart, so opting in to them changes no AllReduce launch;
-// `stream`: the four streamed ReduceScatter kernels (direct_wide_stream.h),
-// cached apart again.
+// `stream`: the four streamed ReduceScatter kernels (direct_wide_stream.h), or
+// with rs = false the four streamed AllReduce kernels
+// (direct_wide_stream_ar.h), each cached apart again.
 static int coresident_wide_blocks(int device, int* ncu_out, bool rs = false, bool stream = false) {
   static std::mutex mu;
   static std::map<std::tuple<unsigned, int, int>, std::pair<int, int>> cache;  // (runtime, device, family) -> (blocks, CUs)
-  const auto key = std::make_tuple(rt_generation(), device, stream ? 2 : rs ? 1 : 0);
+  const auto key = std::make_tuple(rt_generation(), device, stream ? (rs ? 2 : 3) : rs ? 1 : 0);
   {
     std::lock_guard<std::mutex> lk(mu);
     auto it = cache.find(key);
@@ -1473,7 +1494,7 @@ static int coresident_wide_blocks(int device, int* ncu_out, bool rs = false, boo
   int best = 1 << 30;
   for (int dt : {(int)mccsFloat16, (int)mccsBfloat16})
     for (int op : {(int)mccsDevSum, (int)mccsDevPreMulSum}) {
-      for (const void* fn : {stream ? direct_wide_stream_kernel_ptr(dt, op)
+      for (const void* fn : {stream ? (rs ? direct_wide_stream_kernel_ptr(dt, op) : direct_wide_stream_ar_kernel_ptr(dt, op))
                              : rs   ? direct_wide_rs_kernel_ptr(dt, op)
                                     : direct_wide_kernel_ptr(dt, op),
                              rs && !stream ? direct_wide_rd_kernel_ptr(dt, op) : nullptr}) {
@@ -1506,6 +1527,11 @@ void rs_wide_stream_prepare(const Comm* c) {
   if (c->rs_wide_stream_bytes > 0) (void)coresident_wide_blocks(c->device, &ncu, /*rs=*/true, /*stream=*/true);
 }
 
+void ar_wide_stream_prepare(const Comm* c) {
+  int ncu = 0;
+  if (c->ar_wide_stream_bytes > 0) (void)coresident_wide_blocks(c->device, &ncu, /*rs=*/false, /*stream=*/true);
+}
+
 // The wide launch's arguments (direct_group checked the shape, the scalar and
 // the root included).  No ring walk: nch / nthr_ref / idx2rank stay 0, the sum
 // runs in rank order.  owned[] is the AllReduce two-shot's contiguous split
@@ -1513,7 +1539,9 @@ void rs_wide_stream_prepare(const Comm* c) {
 // one block; Reduce: the whole buffer, with the root.  The streamed
 // ReduceScatter adds the round: round_elems from the comm's round bytes (0: the
 // whole slot) and rounds = ceil(count / round_elems); its workgroups and pieces
-// are sized from ONE round.
+// are sized from ONE round.  The streamed AllReduce has both: the two-shot's
+// owned[], and rounds = ceil(largest share / round_elems) with round_elems from
+// the comm's round bytes (0: ar_wide_stream_cap); sized from one round too.
 static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vector<int>& idx, mccsDirectArgs* da,
                                       unsigned* grid_x) {
   const Comm* c0 = comms[idx[0]];
@@ -1537,9 +1565,19 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
   da->root = rd ? (uint32_t)c0->direct.root : 0;
   const bool ll = mode == MCCS_DIRECT_WIDE_LL || mode == MCCS_DIRECT_WIDE_RS_LL || mode == MCCS_DIRECT_WIDE_RD_LL;
   const bool oneshot = mode == MCCS_DIRECT_WIDE_ONE_SHOT;
-  const bool stream = mode == MCCS_DIRECT_WIDE_RS_STREAM;
-  size_t rbytes = nbytes;  // the bytes of one block a data phase moves: the streamed mode's, of one round
-  if (stream) {
+  const bool ar_stream = mode == MCCS_DIRECT_WIDE_AR_STREAM;
+  const bool stream = mode == MCCS_DIRECT_WIDE_RS_STREAM || ar_stream;
+  size_t rbytes = nbytes;  // the bytes of one block a data phase moves: the streamed modes', of one round
+  if (ar_stream) {
+    const size_t cap = ar_wide_stream_cap(c0);
+    const size_t round = c0->ar_wide_stream_round ? c0->ar_wide_stream_round : cap;
+    if (round < 16 || round % 16 || round > cap) return mccsInternalError;  // api.cpp checked it
+    const uint64_t q = MCCS_WIDE_SHARE((uint64_t)da->count, (uint64_t)n);
+    if ((uint64_t)(n - 1) * q >= da->count) return mccsInternalError;  // wide_mode: every rank owns an element
+    da->round_elems = (uint32_t)(round / esize);
+    da->rounds = (q + da->round_elems - 1) / da->round_elems;
+    rbytes = std::min((size_t)q * esize, round);
+  } else if (stream) {
     const size_t round = c0->rs_wide_stream_round ? c0->rs_wide_stream_round : c0->layout.oneshot_slot;
     if (round < 16 || round % 16 || round > c0->layout.oneshot_slot) return mccsInternalError;  // api.cpp checked it
     da->round_elems = (uint32_t)(round / esize);
@@ -1550,7 +1588,7 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
   da->buff_size = (uint32_t)c0->cfg.buffer_size;
   da->fence_mode = c0->kcfg.fence_mode;
   da->timeout_ticks = c0->kcfg.timeout_ticks;
-  if (mode == MCCS_DIRECT_WIDE_TWO_SHOT) {
+  if (mode == MCCS_DIRECT_WIDE_TWO_SHOT || ar_stream) {
     const uint64_t q = MCCS_WIDE_SHARE((uint64_t)da->count, (uint64_t)n);
     for (int t = 0; t < n; ++t) da->owned[t] = (uint64_t)t * q >= da->count ? 0 : std::min(q, da->count - (uint64_t)t * q);
   }
@@ -1580,7 +1618,9 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
   // whole input (one-shot; a Reduce sender), of the n-1 foreign shares
   // (two-shot) or of the n-1 foreign blocks (ReduceScatter), or (LL) one 8-byte
   // word of phase 1 per thread; capped by co-residency.
-  const size_t scatter = rs ? rbytes * (size_t)(n - 1) : (oneshot || rd) ? nbytes : nbytes - nbytes / (size_t)n;
+  const size_t scatter = rs || ar_stream ? rbytes * (size_t)(n - 1)
+                         : (oneshot || rd) ? nbytes
+                                           : nbytes - nbytes / (size_t)n;
   int ncu = 0;
   const int cap = coresident_wide_blocks(c0->device, &ncu, rs || rd, stream);
   if (ncu <= 0) ncu = cap;
@@ -1602,7 +1642,7 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
     return (uint32_t)(p / esize);
   };
   da->piece = piece(scatter);
-  da->piece2 = piece(rs ? rbytes : oneshot || rd ? nbytes : nbytes / (size_t)n + 1);
+  da->piece2 = piece(rs || ar_stream ? rbytes : oneshot || rd ? nbytes : nbytes / (size_t)n + 1);
   for (size_t k = 0; k < idx.size(); ++k) {
     Comm* ck = comms[idx[k]];
     ck->plan_direct = false;
@@ -1805,7 +1845,8 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
       if (c0->direct.wide) {
         const int func = c0->plan_func, dt = c0->plan_dtype, op = c0->plan_op;  // before the build clears the plan
         MCCS_CHECK(build_direct_wide(comms, idx, &da, &grid));
-        fn = da.mode == MCCS_DIRECT_WIDE_RS_STREAM ? direct_wide_stream_kernel_ptr(dt, op)
+        fn = da.mode == MCCS_DIRECT_WIDE_AR_STREAM   ? direct_wide_stream_ar_kernel_ptr(dt, op)
+             : da.mode == MCCS_DIRECT_WIDE_RS_STREAM ? direct_wide_stream_kernel_ptr(dt, op)
              : func == mccsFuncReduceScatter     ? direct_wide_rs_kernel_ptr(dt, op)
              : func == mccsFuncReduce      ? direct_wide_rd_kernel_ptr(dt, op)
                                            : direct_wide_kernel_ptr(dt, op);
@@ -1947,7 +1988,8 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
                                            da.mode == MCCS_DIRECT_WIDE_RD_ONE_SHOT
                                      ? MCCS_ALGO_WIDE_ONESHOT
                                  : da.mode == MCCS_DIRECT_WIDE_TWO_SHOT ? MCCS_ALGO_WIDE_DIRECT
-                                 : da.mode == MCCS_DIRECT_WIDE_RS_STREAM ? MCCS_ALGO_WIDE_STREAM
+                                 : da.mode == MCCS_DIRECT_WIDE_RS_STREAM || da.mode == MCCS_DIRECT_WIDE_AR_STREAM
+                                     ? MCCS_ALGO_WIDE_STREAM
                                  : da.mode == MCCS_DIRECT_TWO_SHOT ? MCCS_ALGO_DIRECT
                                  : da.mode == MCCS_DIRECT_LL_ONE_SHOT || da.mode == MCCS_DIRECT_LL_AG ||
                                            da.mode == MCCS_DIRECT_RS_LL || da.mode == MCCS_DIRECT_RD_LL ||

@@ -431,6 +431,96 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 // rounds, so induction on j from rounds 0 and 1 (which wait for no ack) ends.
 // Every wait is direct_wait: it polls the abort flag and the watchdog and
 // returns on either.
+//
+// Wide streamed AllReduce (direct_wide_stream_ar.h, opt-in:
+// mccsCommSetAllReduceWideStream; fp16 and bf16, Sum and PreMulSum) runs
+// scatter -> wide fold -> gather in rounds inside one launch, for a buffer of
+// ANY size, and adds no slot.  The split is the wide two-shot's (rank t owns
+// owned[t] elements from t q, q = MCCS_WIDE_SHARE), the planner streams only a
+// count > 8 n (n-1), which gives every rank an element, and a launch runs K =
+// ceil(q / B) rounds, B = round_elems; round k has the sequence number seq0 + k
+// (seq0 = LAUNCHES + 1), parity (seq0 + k) & 1, and covers len_k(t) = min(B,
+// owned[t] - k B) elements of share t, 0 once the short last share is exhausted.
+// Two kinds of buffer, each with two parities:
+//   scatter slots: the one-shot in slots, as the streamed ReduceScatter uses
+//     them -- sender s writes round k of share t into t's slot [parity][s];
+//   gather buffers: the two halves (floor16(slot_bytes / 2) each) of the
+//     two-shot IN slots, which a streamed launch otherwise leaves idle -- owner
+//     o writes round k's results into t's in slot [o], half [parity].
+// A workgroup runs, for step i = 0 .. K+1: send(i) if i < K; fold(i-1) if 1 <=
+// i <= K; copy(i-2) if i >= 2.  Counts and acknowledgements:
+//   IN_CNT / SEND_DONE(q): as in the streamed ReduceScatter, a round's count is
+//     indivisible; the last workgroup to arrive after send(k) adds len_k(t) to
+//     IN_CNT(s) of every owner t.  Owner t starts fold(k) at E_IN + min(owned[t],
+//     (k+1) B) on every peer's line.  Over the launch every sender adds owned[t]
+//     on t: the wide two-shot's amount, E_IN += owned[self].
+//   OUT_CNT / FOLD_DONE(q), q = round seq & 3: the same for the gather leg, the
+//     new word: EVERY workgroup drains its stores of fold(k) (cached arenas: and
+//     writes them back) and arrives, with or without pieces; the last puts the
+//     word back to 0 and adds len_k(o) to OUT_CNT(o) of every peer.  copy(k)
+//     starts at E_OUT[o] + min(owned[o], (k+1) B) on every owner o's line, which
+//     therefore proves ALL of rounds 0 .. k from o.  E_OUT[t] += owned[t].
+//   ACK / ROUND_DONE(q): ONE acknowledgement per step.  At the end of step i >=
+//     1 every workgroup drains its loads and arrives on ROUND_DONE((seq0 + i-1)
+//     & 3); the last stores seq0 + i-1 into ACK(me) of every peer and drains.
+//     The value says: every workgroup of this rank finished step i, i.e.
+//     finished reading the scatter slots of round i-1 (fold) AND the gather
+//     buffers of round i-2 (copy).  Every workgroup polls every peer's ACK >=
+//     seq0 + i-2 at the top of step 2 <= i <= K, and ACK >= seq0 + K before the
+//     kernel ends.  The launch leaves LAUNCHES += K + 1: the drain step K+1 has
+//     a number of its own, so every ACK value of a launch is below every value
+//     the next streamed launch of either kind waits for.
+// Hazards within a launch.  send(i) rewrites the scatter parity of round i-2;
+// fold(i-1) rewrites the gather parity of round i-3.  Both run in step i after
+// the wait for ACK >= seq0 + i-2 from every peer t, i.e. after every workgroup
+// of t finished step i-1: fold(i-2) and copy(i-3).  The one wait covers both
+// rewrites, and it stands before fold(K-1) in step K too, which has no send.
+// Steps 0 and 1 rewrite nothing of this launch.
+// Against the previous launch L-1 of any kind.  send(0) writes the scatter
+// parity launch L-1 did NOT use (that of seq0 - 2): the one-shot argument above
+// covers it (s finished L-1, which needed t's hand-off of L-1, made after t
+// finished reading in L-2; where seq0 - 2 was a round of a streamed launch,
+// that launch's closing ACK wait covers it).  send(1) writes the parity of seq0
+// - 1, which a peer may still be reading in L-1, and fold(0) writes gather
+// buffers, i.e. two-shot in slots a peer may still be folding from in a
+// two-shot L-1: both come after the wait for round 0's in-count from EVERY peer
+// t (taken once, at the top of step 1), which t adds only inside its launch L,
+// after its L-1 ended.  That is a hand-off only if t adds something: len_0(me)
+// >= 1 on every rank, which is the planner's owned[n-1] >= 1.
+// Against the next launch of any kind.  The kernel ends on s only after ACK >=
+// seq0 + K from every peer t: every workgroup of t finished step K+1, so t has
+// read every scatter slot and every gather buffer of the launch.  The next
+// launch may refill one-shot slots of either parity and two-shot in slots (which
+// have no parity of their own in the two-shot kernels) at once; the two-shot out
+// slot is not touched here.  Conversely t's counts of the next launch cannot
+// reach s early: t is in the next launch only after s's last workgroup finished
+// step K+1.
+// Four words per arrival kind suffice.  Passing the top of step j (3 <= j <= K)
+// needs every peer's ACK of step j-1, hence a peer's copy(j-3), hence this
+// rank's out-count of round j-3, hence EVERY workgroup of this rank past
+// fold(j-3), which lies in step j-2: all of them finished step j-3, and the
+// last arriver there put its word back and drained before it went on.  A
+// workgroup that arrives for step i+4 (ROUND_DONE), round k+4 (SEND_DONE, in
+// step k+4; FOLD_DONE, in step k+5) has passed the top of step min(i+4, K) >=
+// i+3, resp. k+4, resp. k+5 <= K, so every workgroup finished step i, resp.
+// k+1, resp. k+2: the earlier use of the word is over and the word is 0.
+// No workgroup waits on its own rank (arrivals are adds, never waits), and the
+// waits form no cycle: every wait of step i is for something the peers do in a
+// step below i -- ACK >= seq0 + i-2 is their step i-1; round 0's and round
+// i-1's in-counts are their send in steps 0 and i-1; round i-2's out-count is
+// their fold in step i-1 -- so by induction on i every workgroup of every rank
+// finishes every step, and the closing wait needs only step K+1.  A rank whose
+// share is exhausted (len_k = 0) still waits, arrives and acknowledges.
+// In place (recv == send).  fold(k) loads and stores each element of the own
+// share through one thread, and no send reads the own share.  copy(k) stores
+// into foreign shares' round k, which only send(k) reads: send and copy deal
+// their pieces through ONE function with equal counters (numbered through all
+// rounds, piece p to workgroup p % G), so the workgroup that stores a range in
+// copy(k), step k+2, is the one that read it in send(k), step k, and has long
+// drained those loads (its arrival on SEND_DONE).  A slower workgroup of the
+// same rank sends other ranges.
+// Every wait is direct_wait: it polls the abort flag and the watchdog and
+// returns on either.
 #define MCCS_DIRECT_MAX_RANKS 8
 #define MCCS_DIRECT_CTRL_BYTES 65536
 // u64, added to by sender s; a rank's own line IN_CNT(rank) counts its own
@@ -453,6 +543,9 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 #define MCCS_DIRECT_ROUND_DONE(q) (12288 + (q) * MCCS_FLAG_LINE_BYTES)
 // u32, this rank's workgroups that finished sending the round of seq & 3 (the last one adds the round's count)
 #define MCCS_DIRECT_SEND_DONE(q) (16384 + (q) * MCCS_FLAG_LINE_BYTES)
+// wide streamed AllReduce (above): u32, this rank's workgroups that finished folding the round of seq & 3 (the last
+// one adds the round's count to OUT_CNT); its ACK / ROUND_DONE / SEND_DONE are the lines above, one step per value
+#define MCCS_DIRECT_FOLD_DONE(q) (20480 + (q) * MCCS_FLAG_LINE_BYTES)
 #define MCCS_DIRECT_SLOTS (MCCS_DIRECT_MAX_RANKS + 1)                  // two-shot slots
 #define MCCS_DIRECT_THREADS 512
 #define MCCS_DIRECT_TWO_SHOT 0
@@ -482,6 +575,8 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 #define MCCS_DIRECT_WIDE_RD_ONE_SHOT 17  // Reduce through the root's one-shot slots, counted on IN_CNT
 // wide streamed ReduceScatter (direct_wide_stream.h; count = recvcount of any size, rounds x round_elems)
 #define MCCS_DIRECT_WIDE_RS_STREAM 18    // rounds through the one-shot slots, counted on IN_CNT, acknowledged on ACK
+// wide streamed AllReduce (direct_wide_stream_ar.h; count of any size, owned[] the two-shot's split, rounds x round_elems)
+#define MCCS_DIRECT_WIDE_AR_STREAM 19    // scatter through the one-shot slots, gather through the halves of the two-shot in slots
 
 struct mccsDirectRank {  // one rank slot of a direct launch (blockIdx.y)
   const void* send;
@@ -504,17 +599,17 @@ struct mccsDirectArgs {
   uint64_t timeout_ticks;  // s_memrealtime ticks; 0 = never
   uint32_t nranks, nch, nthr_ref, buff_size;  // the ring walk this launch reproduces
   uint32_t fence_mode;                        // MCCS_FENCE_*
-  uint32_t mode;                              // MCCS_DIRECT_* above (RS: direct_rs_kernel only; RD / BC: direct_rooted.h's kernels only; WIDE: direct_wide_kernel only; WIDE_RS / WIDE_RD: direct_wide_rs.h's kernels only; WIDE_RS_STREAM: direct_wide_stream_kernel only)
+  uint32_t mode;                              // MCCS_DIRECT_* above (RS: direct_rs_kernel only; RD / BC: direct_rooted.h's kernels only; WIDE: direct_wide_kernel only; WIDE_RS / WIDE_RD: direct_wide_rs.h's kernels only; WIDE_RS_STREAM: direct_wide_stream_kernel only; WIDE_AR_STREAM: direct_wide_stream_ar_kernel only)
   uint32_t piece;                             // elements per piece of the scatter / gather phases
   uint32_t piece2;                            // elements per piece of the reduction phase
   uint32_t no_guard;                          // 1: skip the launch guard (test hook only)
   uint32_t root;                              // the RD / BC / WIDE_RD modes: the root (one for all rank slots); else 0
   uint64_t guard_order;                       // rank slots by guard address, 4 bits each (launch_guard.h)
-  uint64_t owned[MCCS_DIRECT_MAX_RANKS];      // elements of the walk's chunks each rank owns (wide two-shot: of its share)
+  uint64_t owned[MCCS_DIRECT_MAX_RANKS];      // elements of the walk's chunks each rank owns (wide two-shot and WIDE_AR_STREAM: of its share)
   uint8_t idx2rank[MCCS_MAX_NCHANNELS][MCCS_DIRECT_MAX_RANKS];  // rank at ring index k of channel bid
   uint64_t op_arg;  // the wide modes: the PreMulSum scalar (T in the low bits); else 0 (the fields above keep their place)
-  uint64_t rounds;       // WIDE_RS_STREAM: K = ceil(count / round_elems) >= 1; else 0
-  uint32_t round_elems;  // WIDE_RS_STREAM: elements of one round (a multiple of 8, at most one one-shot slot); else 0
+  uint64_t rounds;       // WIDE_RS_STREAM: K = ceil(count / round_elems) >= 1; WIDE_AR_STREAM: ceil(share / round_elems); else 0
+  uint32_t round_elems;  // the STREAM modes: elements of one round (a multiple of 8, at most one one-shot slot; AR: and half a two-shot slot); else 0
   uint32_t pad4;
 };
 #ifdef __cplusplus

@@ -33,6 +33,11 @@ The wide streamed ReduceScatter (mccsCommSetReduceScatterWideStream, whole-slot
 rounds of 1 MiB) at blocks of 1x, 4x and 16x the slot, timed the same way
 beside the ring of the same size and the same bytes as a host-issued sequence
 of slot-sized wide one-shot launches.
+  python tools/direct_bench.py --wide --stream --dtype bfloat16 [--n 2 4 8] [--sizes-kib 4096 16384 65536]
+The wide streamed AllReduce (mccsCommSetAllReduceWideStream, largest rounds) at
+buffers of 2x, 8x and 32x the 2 MiB two-shot slot, per graph-replayed call,
+beside the ring of the same size and the same bytes as a host-issued sequence
+of slot-sized wide two-shot launches; the three alternate region by region.
 """
 import argparse
 import json
@@ -394,6 +399,83 @@ def wide_stream_mode(args, torch, C, st, dt, code, es):
                       "calls": args.calls, "regions": args.regions, "rows": rows}), flush=True)
 
 
+def wide_ar_stream_mode(args, torch, C, st, dt, code, es):
+    """--wide --stream: per buffer size (2x, 8x, 32x the 2 MiB two-shot slot)
+    the ring AllReduce ("ring": where such a buffer goes without the opt-in),
+    the streamed kernel ("stream", rounds of 1 MiB per share) and the same
+    bytes as K host-issued wide two-shot launches of one slot each ("split":
+    what keeps the bits today).  Each variant is captured as a graph of
+    --graph-calls calls after an eager warm-up; a region replays it until
+    --calls calls ran, and the regions alternate between the three."""
+    import statistics
+
+    assert es == 2, "--wide times float16 / bfloat16"
+    slot = 2 << 20
+    sizes = args.sizes_kib if args.sizes_kib != DEFAULT_SIZES_KIB else [4096, 16384, 65536]
+    per, rows = args.graph_calls, []
+    for n in args.n:
+        cfg = C.CommConfig(ll_bytes=-1, oneshot_bytes=slot // 2, direct_bytes=slot)
+        sets = {a: C.init_all([0] * n, cfg) for a in ("ring", "stream", "split")}
+        for c in sets["stream"]:
+            assert c.all_reduce_wide_stream_max() == slot // 2
+            c.set_all_reduce_wide_stream(max(sizes) << 10, 0)
+        for c in sets["split"]:
+            c.set_all_reduce_wide(0, 0, slot)
+        want = {"ring": "ring", "stream": "wide-stream", "split": "wide-direct"}
+        for kib in sizes:
+            nbytes = kib << 10
+            cnt, part, k = nbytes // es, slot // es, nbytes // slot
+            assert k * slot == nbytes, "--stream buffer sizes are multiples of the 2 MiB slot"
+            xs = [torch.randn(cnt, device="cuda").to(dt) for _ in range(n)]
+            ys = [torch.empty(cnt, dtype=dt, device="cuda") for _ in xs]
+            rounds = -(-((-(-cnt // n) + 7) // 8 * 8) // (slot // 2 // es))
+            row = {"n": n, "func": "allreduce", "bytes": nbytes, "slot_bytes": slot, "launches_split": k, "rounds": rounds}
+
+            def once(a):
+                for j in range(k if a == "split" else 1):
+                    with C.group():
+                        for r, c in enumerate(sets[a]):
+                            if a == "split":
+                                C.all_reduce(c, xs[r][j * part:], ys[r][j * part:], part, code, 0, stream=st)
+                            else:
+                                C.all_reduce(c, xs[r], ys[r], cnt, code, 0, stream=st)
+
+            graphs = {}
+            for a in sets:  # warm-up (every kernel's code object), then one graph of `per` calls per variant
+                for _ in range(3):
+                    once(a)
+                st.synchronize()
+                assert sets[a][0].last_algo() == want[a], (a, sets[a][0].last_algo())
+                graphs[a] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[a], stream=st):
+                    for _ in range(per):
+                        once(a)
+                graphs[a].replay()
+                torch.cuda.synchronize()
+            us = {a: [] for a in sets}
+            for _ in range(args.regions):
+                for a in sets:  # the variants alternate region by region
+                    t0 = time.perf_counter()
+                    for _ in range(max(1, args.calls // per)):
+                        graphs[a].replay()
+                    torch.cuda.synchronize()
+                    us[a].append((time.perf_counter() - t0) / (max(1, args.calls // per) * per) * 1e6)
+            for a in sets:
+                row[a + "_us"] = round(statistics.median(us[a]), 2)
+                row[a + "_min_us"], row[a + "_max_us"] = round(min(us[a]), 2), round(max(us[a]), 2)
+                for c in sets[a]:
+                    c.sync()
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            del graphs, xs, ys
+        torch.cuda.synchronize()
+        for comms in sets.values():
+            for c in comms:
+                c.destroy()
+    print(json.dumps({"tool": "direct_bench", "collective": "allreduce-wide-stream", "dtype": args.dtype, "timed": "graph",
+                      "calls": args.calls, "graph_calls": per, "regions": args.regions, "rows": rows}), flush=True)
+
+
 DEFAULT_SIZES_KIB = [32, 128, 512, 2048, 8192, 32768]
 
 
@@ -425,7 +507,10 @@ def main():
                          "average against the ring")
     ap.add_argument("--stream", action="store_true",
                     help="with --wide --reduce-scatter: the wide streamed ReduceScatter at 1x, 4x and 16x the one-shot "
-                         "slot against the ring and a host-issued sequence of slot-sized wide one-shot launches")
+                         "slot against the ring and a host-issued sequence of slot-sized wide one-shot launches; with "
+                         "--wide alone: the wide streamed AllReduce at 2x, 8x and 32x the two-shot slot, graph-replayed, "
+                         "against the ring and a host-issued sequence of slot-sized wide two-shot launches")
+    ap.add_argument("--graph-calls", type=int, default=4, help="--wide --stream: calls captured into each replayed graph")
     ap.add_argument("--regions", type=int, default=5, help="--rooted, --wide: timed regions of --calls calls per variant")
     args = ap.parse_args()
     dt = getattr(torch, args.dtype)
@@ -435,6 +520,9 @@ def main():
     st = side_stream(torch, 0, slot=1)
     if args.wide and args.reduce_scatter and args.stream:
         wide_stream_mode(args, torch, C, st, dt, code, es)
+        return
+    if args.wide and args.stream and not args.rooted:
+        wide_ar_stream_mode(args, torch, C, st, dt, code, es)
         return
     if args.wide and (args.reduce_scatter or args.rooted):
         wide_rs_mode(args, torch, C, st, dt, code, es, args.rooted)

@@ -2,7 +2,8 @@
 """Register, scratch and LDS use of the shipped ring and direct kernels (gfx950).
 
 Compiles the ring and direct translation units (ring*.hip, direct*.hip,
-direct_wide_rs.hip and direct_wide_stream.hip among them, each with its own
+direct_wide_rs.hip, direct_wide_stream.hip and direct_wide_stream_ar.hip among
+them, each with its own
 build flags) with
 --save-temps into a scratch directory and reads each kernel's AMDGPU
 metadata from the generated assembly: .vgpr_count, .agpr_count,
