@@ -678,6 +678,46 @@ mccsResult_t mccsCommReduceScatterWideStreamMax(mccsComm_t comm, size_t *round_c
  * graph.  The node gate does not cover this path. */
 mccsResult_t mccsCommSetAllReduceWideStream(mccsComm_t comm, size_t max_bytes, size_t round_bytes);
 mccsResult_t mccsCommAllReduceWideStreamMax(mccsComm_t comm, size_t *round_cap);
+/* The block-scaled FP8 AllReduce, for mccsFloat16 and mccsBfloat16 with Sum or
+ * PreMulSum (so mccsAvgOp): a two-shot through the direct region that carries
+ * every element as an OCP E4M3FN code plus one E8M0 scale byte per block of 32
+ * elements (the MX layout), about 8.25 bits per element on the wire instead of
+ * 16.  IT IS LOSSY ON PURPOSE: on N(0,1) bf16 inputs the relative L2 error
+ * against the exact sum is 3.7e-2 to 3.9e-2 at 2, 4 and 8 ranks, where the
+ * ring's is 1.8e-3 to 3.7e-3 (computed on the CPU from the definition; DESIGN.md
+ * section 8).  Off by default.
+ * Definition.  A block is the 32 elements at indices [32k, 32k + 32) of the
+ * buffer, elements past count counting as +0.  QDQ(y) of one block in binary32:
+ * amax = max |y_i| with biased exponent field f; an Inf or NaN in the block
+ * gives scale byte 255 and 32 NaN; else b = max(f - 7, 1), v_i = y_i *
+ * 2^(127 - b) (exact, |v_i| < 256), c_i = v_i rounded to nearest even onto
+ * E4M3FN (subnormals and signs kept), d_i = e4m3(c_i) * 2^(b - 127).  Per
+ * block, in RANK order: y_r = QDQ(f32(x_r)) for every rank, the owner's own
+ * input included; t_r = y_r, or fl32(y_r * f32(s)) for PreMulSum (never a fused
+ * multiply-add); acc = t_0; acc = fl32(acc + t_r); out = T(QDQ(acc)), one
+ * rounding to nearest even.  The result is a function of the inputs and nranks
+ * alone, the same on every rank, in place or not.  ONE Inf OR NaN, OR A SUM
+ * THAT LEAVES BINARY32, MAKES ITS BLOCK OF 32 NaN ON EVERY RANK.
+ * mccsCommAllReduceQuantMax: *cap, the largest buffer in bytes: twice the
+ * payload bytes of a two-shot slot (slot * 32 / 33 cut to a multiple of 512),
+ * about 1.94 times the two-shot's own cap on the same arena; 0 without
+ * two-shot slots, outside 2..8 ranks, without peer atomics or unconnected.
+ * mccsCommSetAllReduceQuant: a qualifying mccsAllReduce / mccsAllReduceOpArg of
+ * min_bytes <= bytes <= max_bytes that is its communicator's only call of the
+ * launch takes this path (mccsCommLastAlgo reports MCCS_ALGO_QUANT), decided
+ * BEFORE the wide limits and the ring-order direct variants see the call;
+ * max_bytes 0 = off, and then every call plans exactly as without this entry
+ * point.  max_bytes above *cap and min_bytes > max_bytes are refused with
+ * mccsInvalidArgument; a call while the communicator has a group open or a
+ * call pending, with mccsInvalidUsage.  MCCS_AR_QUANT_MIN_BYTES /
+ * MCCS_AR_QUANT_BYTES in the environment set the two at creation (clamped to
+ * *cap).  EVERY RANK MUST SET THE SAME TWO VALUES; this is not detected.  One
+ * sharing a group with a second call of the communicator goes to the ring with
+ * its scalar; every other dtype and op plans as before.  Ranks sharing a GPU
+ * are fused into one launch; the call may be captured into a HIP graph.  The
+ * node gate does not cover this path. */
+mccsResult_t mccsCommSetAllReduceQuant(mccsComm_t comm, size_t min_bytes, size_t max_bytes);
+mccsResult_t mccsCommAllReduceQuantMax(mccsComm_t comm, size_t *cap);
 /* Send / Recv: grouped point-to-point (torch's batch_isend_irecv; the pieces of
  * a Gather or Scatter).  mccsSend moves count * elem_bytes(dtype) bytes from
  * sendbuff to rank `peer`, mccsRecv receives as many from rank `peer` into
@@ -810,7 +850,8 @@ mccsResult_t mccsCommRing(mccsComm_t comm, int ch, int *order);
  * (two-shot), MCCS_ALGO_ONESHOT or MCCS_ALGO_LL (LL one-shot), or one of the
  * wide-accumulate variants (mccsCommSetAllReduceWide and its siblings;
  * MCCS_ALGO_WIDE_STREAM: mccsCommSetReduceScatterWideStream,
- * mccsCommSetAllReduceWideStream) (-1 before the first). */
+ * mccsCommSetAllReduceWideStream), or MCCS_ALGO_QUANT, the block-scaled FP8
+ * AllReduce (mccsCommSetAllReduceQuant) (-1 before the first). */
 #define MCCS_ALGO_RING 0
 #define MCCS_ALGO_DIRECT 1
 #define MCCS_ALGO_ONESHOT 2
@@ -819,6 +860,7 @@ mccsResult_t mccsCommRing(mccsComm_t comm, int ch, int *order);
 #define MCCS_ALGO_WIDE_ONESHOT 5
 #define MCCS_ALGO_WIDE_DIRECT 6
 #define MCCS_ALGO_WIDE_STREAM 7
+#define MCCS_ALGO_QUANT 8
 int mccsCommLastAlgo(mccsComm_t comm);
 /* 1 when the comm may run the direct kernel: a direct region was configured
  * and every device of the communicator can perform atomics on every other's

@@ -1029,6 +1029,35 @@ extern "C" mccsResult_t mccsCommSetAllReduceWideStream(mccsComm_t comm, size_t m
   return mccsSuccess;
 }
 
+extern "C" mccsResult_t mccsCommAllReduceQuantMax(mccsComm_t comm, size_t* cap) {
+  err_clear();
+  const Comm* c = (const Comm*)comm;
+  if (!c || !cap) MCCS_FAIL(mccsInvalidArgument, "mccsCommAllReduceQuantMax: null communicator or output");
+  *cap = c->connected && c->nranks >= 2 && c->nranks <= MCCS_DIRECT_MAX_RANKS ? ar_quant_cap(c) : 0;
+  return mccsSuccess;
+}
+
+extern "C" mccsResult_t mccsCommSetAllReduceQuant(mccsComm_t comm, size_t min_bytes, size_t max_bytes) {
+  err_clear();
+  StepScope st("mccsCommSetAllReduceQuant");
+  Comm* c = (Comm*)comm;
+  if (!c || !c->connected) MCCS_FAIL(mccsInvalidUsage, "the communicator is not connected");
+  if (g_group.depth > 0 || c->plan_pending)
+    MCCS_FAIL(mccsInvalidUsage, "the communicator has a group open or a call pending: set the limits between launches");
+  const size_t cap = ar_quant_cap(c);
+  if (max_bytes > cap)
+    MCCS_FAIL(mccsInvalidArgument, "max_bytes %zu is above the %zu bytes whose FP8 codes and scale bytes fit a "
+              "two-shot slot%s", max_bytes, cap,
+              cap ? "" : " (no two-shot slots or no peer atomics: the two-shot path is closed here)");
+  if (min_bytes > max_bytes)
+    MCCS_FAIL(mccsInvalidArgument, "min_bytes %zu is above max_bytes %zu: the window is empty (max_bytes 0 = off)",
+              min_bytes, max_bytes);
+  c->ar_quant_min_bytes = min_bytes;
+  c->ar_quant_bytes = max_bytes;
+  ar_quant_prepare(c);
+  return mccsSuccess;
+}
+
 // The wide ReduceScatter's (rd = false) and Reduce's (rd = true) two limits.
 static mccsResult_t set_rs_wide(mccsComm_t comm, bool rd, size_t ll_bytes, size_t bytes) {
   err_clear();

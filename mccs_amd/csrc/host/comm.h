@@ -354,6 +354,13 @@ struct Comm {
   // and its comm's only call of the launch, is held likewise and runs
   // direct_wide_stream_ar_kernel.  Every rank must set the same values.
   size_t ar_wide_stream_bytes = 0, ar_wide_stream_round = 0;
+  // Block-scaled FP8 AllReduce (direct_quant.h).  The opt-in window in bytes of
+  // the whole buffer (mccsCommSetAllReduceQuant; MCCS_AR_QUANT_MIN_BYTES /
+  // MCCS_AR_QUANT_BYTES at creation), max 0 = off: a qualifying AllReduce (the
+  // wide paths' conditions) of min <= bytes <= max is held in `direct` (wide =
+  // true) BEFORE the wide limits see it and runs direct_quant_kernel.  Every
+  // rank must set the same values.
+  size_t ar_quant_min_bytes = 0, ar_quant_bytes = 0;
   // Direct Broadcast and Reduce (direct_rooted.h).  The four opt-in limits in
   // bytes of the whole buffer (mccsCommSetRootedDirect; MCCS_BC_DIRECT_BYTES /
   // MCCS_BC_LL_BYTES / MCCS_RD_DIRECT_BYTES / MCCS_RD_LL_BYTES at creation),
@@ -515,6 +522,11 @@ void rs_wide_stream_prepare(const Comm* c);  // probes the four streamed kernels
 // the cap > 0) and MCCS_AR_WIDE_STREAM_ROUND_BYTES (clamped to the cap, cut to a multiple of 16).
 size_t ar_wide_stream_cap(const Comm* c);
 void ar_wide_stream_prepare(const Comm* c);  // probes the four streamed AllReduce kernels' co-residency once
+// Block-scaled FP8 AllReduce: the cap is 2 x MCCS_QUANT_PAY(one two-shot slot) bytes, one code per 2-byte element
+// (0 unless direct_ok).  ar_quant_read_env reads MCCS_AR_QUANT_MIN_BYTES / MCCS_AR_QUANT_BYTES, clamped to the cap.
+size_t ar_quant_cap(const Comm* c);
+void ar_quant_read_env(Comm* c);
+void ar_quant_prepare(const Comm* c);  // after the limits changed: probes the four quant kernels' co-residency once
 mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_t>& user_streams);
 // ring.hip
 const void* ring_kernel_ptr(int func, int dtype, int op);
@@ -538,6 +550,8 @@ const void* direct_wide_rd_kernel_ptr(int dtype, int op);
 const void* direct_wide_stream_kernel_ptr(int dtype, int op);
 // direct_wide_stream_ar.hip (likewise)
 const void* direct_wide_stream_ar_kernel_ptr(int dtype, int op);
+// direct_quant.hip (likewise)
+const void* direct_quant_kernel_ptr(int dtype, int op);
 hipError_t ring_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_flush_caches(hipStream_t st);
 

@@ -581,6 +581,22 @@ void ar_wide_read_env(Comm* c) {
   ar_wide_stream_prepare(c);
 }
 
+// ---- block-scaled FP8 AllReduce (direct_quant.h) --------------------------------
+// One two-shot slot holds PAY codes and their scale bytes, so a buffer of up
+// to PAY 2-byte elements; its counts are remote atomics.
+size_t ar_quant_cap(const Comm* c) { return c->direct_ok ? 2 * (size_t)MCCS_QUANT_PAY(c->layout.direct_slot) : 0; }
+
+void ar_quant_read_env(Comm* c) {
+  auto read = [&](const char* name) {
+    const char* v = std::getenv(name);
+    const long long x = v ? std::atoll(v) : 0;
+    return x > 0 ? std::min((size_t)x, ar_quant_cap(c)) : (size_t)0;
+  };
+  c->ar_quant_min_bytes = read("MCCS_AR_QUANT_MIN_BYTES");
+  c->ar_quant_bytes = read("MCCS_AR_QUANT_BYTES");
+  ar_quant_prepare(c);
+}
+
 // The wide ReduceScatter's and Reduce's limits (direct_wide_rs.h): the direct
 // ReduceScatter's caps and conditions, per block / over the whole buffer.
 void rs_wide_read_env(Comm* c) {
@@ -623,6 +639,9 @@ static int wide_mode(const Comm* c, int func, size_t bytes) {
     return -1;
   }
   if (func != mccsFuncAllReduce) return -1;
+  // the block-scaled FP8 window is decided before the wide limits
+  if (c->ar_quant_bytes > 0 && bytes >= c->ar_quant_min_bytes && bytes <= c->ar_quant_bytes && bytes <= ar_quant_cap(c))
+    return MCCS_DIRECT_QUANT_TWO_SHOT;
   if (bytes <= c->ar_wide_ll_bytes && bytes <= rs_ll_cap(c)) return MCCS_DIRECT_WIDE_LL;
   if (bytes <= c->ar_wide_oneshot_bytes && bytes <= rs_direct_cap(c)) return MCCS_DIRECT_WIDE_ONE_SHOT;
   if (bytes <= c->ar_wide_bytes && bytes <= ar_wide_cap(c)) return MCCS_DIRECT_WIDE_TWO_SHOT;
@@ -1099,6 +1118,7 @@ static bool direct_group(std::vector<Comm*>& comms, const std::vector<int>& idx)
         ck->rd_wide_ll_bytes != c0->rd_wide_ll_bytes || ck->rd_wide_bytes != c0->rd_wide_bytes ||
         ck->rs_wide_stream_bytes != c0->rs_wide_stream_bytes || ck->rs_wide_stream_round != c0->rs_wide_stream_round ||
         ck->ar_wide_stream_bytes != c0->ar_wide_stream_bytes || ck->ar_wide_stream_round != c0->ar_wide_stream_round ||
+        ck->ar_quant_min_bytes != c0->ar_quant_min_bytes || ck->ar_quant_bytes != c0->ar_quant_bytes ||
         ck->direct.op_arg != c0->direct.op_arg)  // one scalar for every rank slot (mccsDirectArgs.op_arg)
       return false;
   }
@@ -1475,11 +1495,12 @@ static mccsResult_t build_direct_rooted(std::vector<Comm*>& comms, const std::ve
 // instead, cached apart, so opting in to them changes no AllReduce launch;
 // `stream`: the four streamed ReduceScatter kernels (direct_wide_stream.h), or
 // with rs = false the four streamed AllReduce kernels
-// (direct_wide_stream_ar.h), each cached apart again.
-static int coresident_wide_blocks(int device, int* ncu_out, bool rs = false, bool stream = false) {
+// (direct_wide_stream_ar.h), each cached apart again; `quant`: the four
+// block-scaled FP8 AllReduce kernels (direct_quant.h), cached apart too.
+static int coresident_wide_blocks(int device, int* ncu_out, bool rs = false, bool stream = false, bool quant = false) {
   static std::mutex mu;
   static std::map<std::tuple<unsigned, int, int>, std::pair<int, int>> cache;  // (runtime, device, family) -> (blocks, CUs)
-  const auto key = std::make_tuple(rt_generation(), device, stream ? (rs ? 2 : 3) : rs ? 1 : 0);
+  const auto key = std::make_tuple(rt_generation(), device, quant ? 4 : stream ? (rs ? 2 : 3) : rs ? 1 : 0);
   {
     std::lock_guard<std::mutex> lk(mu);
     auto it = cache.find(key);
@@ -1494,7 +1515,8 @@ static int coresident_wide_blocks(int device, int* ncu_out, bool rs = false, boo
   int best = 1 << 30;
   for (int dt : {(int)mccsFloat16, (int)mccsBfloat16})
     for (int op : {(int)mccsDevSum, (int)mccsDevPreMulSum}) {
-      for (const void* fn : {stream ? (rs ? direct_wide_stream_kernel_ptr(dt, op) : direct_wide_stream_ar_kernel_ptr(dt, op))
+      for (const void* fn : {quant    ? direct_quant_kernel_ptr(dt, op)
+                             : stream ? (rs ? direct_wide_stream_kernel_ptr(dt, op) : direct_wide_stream_ar_kernel_ptr(dt, op))
                              : rs   ? direct_wide_rs_kernel_ptr(dt, op)
                                     : direct_wide_kernel_ptr(dt, op),
                              rs && !stream ? direct_wide_rd_kernel_ptr(dt, op) : nullptr}) {
@@ -1527,6 +1549,11 @@ void rs_wide_stream_prepare(const Comm* c) {
   if (c->rs_wide_stream_bytes > 0) (void)coresident_wide_blocks(c->device, &ncu, /*rs=*/true, /*stream=*/true);
 }
 
+void ar_quant_prepare(const Comm* c) {
+  int ncu = 0;
+  if (c->ar_quant_bytes > 0) (void)coresident_wide_blocks(c->device, &ncu, false, false, /*quant=*/true);
+}
+
 void ar_wide_stream_prepare(const Comm* c) {
   int ncu = 0;
   if (c->ar_wide_stream_bytes > 0) (void)coresident_wide_blocks(c->device, &ncu, /*rs=*/false, /*stream=*/true);
@@ -1542,6 +1569,9 @@ void ar_wide_stream_prepare(const Comm* c) {
 // are sized from ONE round.  The streamed AllReduce has both: the two-shot's
 // owned[], and rounds = ceil(largest share / round_elems) with round_elems from
 // the comm's round bytes (0: ar_wide_stream_cap); sized from one round too.
+// The block-scaled FP8 AllReduce (direct_quant.h) is built here as well: the
+// two-shot's shape with owned[] cut by MCCS_QUANT_SHARE (shares start on units
+// of 512 elements); its pieces, multiples of 2048 elements, are whole units.
 static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vector<int>& idx, mccsDirectArgs* da,
                                       unsigned* grid_x) {
   const Comm* c0 = comms[idx[0]];
@@ -1567,6 +1597,8 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
   const bool oneshot = mode == MCCS_DIRECT_WIDE_ONE_SHOT;
   const bool ar_stream = mode == MCCS_DIRECT_WIDE_AR_STREAM;
   const bool stream = mode == MCCS_DIRECT_WIDE_RS_STREAM || ar_stream;
+  const bool quant = mode == MCCS_DIRECT_QUANT_TWO_SHOT;
+  if (quant && da->count > MCCS_QUANT_PAY(da->slot_bytes)) return mccsInternalError;  // wide_mode: within ar_quant_cap
   size_t rbytes = nbytes;  // the bytes of one block a data phase moves: the streamed modes', of one round
   if (ar_stream) {
     const size_t cap = ar_wide_stream_cap(c0);
@@ -1590,6 +1622,10 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
   da->timeout_ticks = c0->kcfg.timeout_ticks;
   if (mode == MCCS_DIRECT_WIDE_TWO_SHOT || ar_stream) {
     const uint64_t q = MCCS_WIDE_SHARE((uint64_t)da->count, (uint64_t)n);
+    for (int t = 0; t < n; ++t) da->owned[t] = (uint64_t)t * q >= da->count ? 0 : std::min(q, da->count - (uint64_t)t * q);
+  }
+  if (quant) {
+    const uint64_t q = MCCS_QUANT_SHARE((uint64_t)da->count, (uint64_t)n);
     for (int t = 0; t < n; ++t) da->owned[t] = (uint64_t)t * q >= da->count ? 0 : std::min(q, da->count - (uint64_t)t * q);
   }
   for (size_t k = 0; k < idx.size(); ++k) {
@@ -1622,7 +1658,7 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
                          : (oneshot || rd) ? nbytes
                                            : nbytes - nbytes / (size_t)n;
   int ncu = 0;
-  const int cap = coresident_wide_blocks(c0->device, &ncu, rs || rd, stream);
+  const int cap = coresident_wide_blocks(c0->device, &ncu, rs || rd, stream, quant);
   if (ncu <= 0) ncu = cap;
   long g = std::min<long>((long)((scatter + 4095) / 4096), c0->direct_blocks);
   const size_t ll_words = (rs ? (size_t)(n - 1) : 1) * ((nbytes + 7) / 8);
@@ -1845,7 +1881,8 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
       if (c0->direct.wide) {
         const int func = c0->plan_func, dt = c0->plan_dtype, op = c0->plan_op;  // before the build clears the plan
         MCCS_CHECK(build_direct_wide(comms, idx, &da, &grid));
-        fn = da.mode == MCCS_DIRECT_WIDE_AR_STREAM   ? direct_wide_stream_ar_kernel_ptr(dt, op)
+        fn = da.mode == MCCS_DIRECT_QUANT_TWO_SHOT   ? direct_quant_kernel_ptr(dt, op)
+             : da.mode == MCCS_DIRECT_WIDE_AR_STREAM ? direct_wide_stream_ar_kernel_ptr(dt, op)
              : da.mode == MCCS_DIRECT_WIDE_RS_STREAM ? direct_wide_stream_kernel_ptr(dt, op)
              : func == mccsFuncReduceScatter     ? direct_wide_rs_kernel_ptr(dt, op)
              : func == mccsFuncReduce      ? direct_wide_rd_kernel_ptr(dt, op)
@@ -1988,6 +2025,7 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
                                            da.mode == MCCS_DIRECT_WIDE_RD_ONE_SHOT
                                      ? MCCS_ALGO_WIDE_ONESHOT
                                  : da.mode == MCCS_DIRECT_WIDE_TWO_SHOT ? MCCS_ALGO_WIDE_DIRECT
+                                 : da.mode == MCCS_DIRECT_QUANT_TWO_SHOT ? MCCS_ALGO_QUANT
                                  : da.mode == MCCS_DIRECT_WIDE_RS_STREAM || da.mode == MCCS_DIRECT_WIDE_AR_STREAM
                                      ? MCCS_ALGO_WIDE_STREAM
                                  : da.mode == MCCS_DIRECT_TWO_SHOT ? MCCS_ALGO_DIRECT

@@ -407,7 +407,7 @@ class FakeRuntime final : public DeviceRuntime {
       for (int op : {(int)mccsDevSum, (int)mccsDevPreMulSum})
         direct = direct || (fn && (fn == direct_wide_kernel_ptr(dt, op) || fn == direct_wide_rs_kernel_ptr(dt, op) ||
                                    fn == direct_wide_rd_kernel_ptr(dt, op) || fn == direct_wide_stream_kernel_ptr(dt, op) ||
-                                   fn == direct_wide_stream_ar_kernel_ptr(dt, op)));
+                                   fn == direct_wide_stream_ar_kernel_ptr(dt, op) || fn == direct_quant_kernel_ptr(dt, op)));
     const bool a2all = fn && fn == a2a_ll_kernel_ptr();
     if (fn && args && grid.y >= 1 && grid.y <= MCCS_MULTI_MAX_RANKS) {
       if (a2all) {
@@ -460,6 +460,7 @@ class FakeRuntime final : public DeviceRuntime {
                             : da->mode == MCCS_DIRECT_WIDE_RD_ONE_SHOT ? "wide-rd-oneshot"
                             : da->mode == MCCS_DIRECT_WIDE_RS_STREAM   ? "wide-rs-stream"
                             : da->mode == MCCS_DIRECT_WIDE_AR_STREAM   ? "wide-ar-stream"
+                            : da->mode == MCCS_DIRECT_QUANT_TWO_SHOT   ? "quant-twoshot"
                                                                   : "twoshot") +
                 " gx=" + std::to_string(grid.x) + " llslot=" + std::to_string(da->ll_slot_bytes) +
                 " piece=" + std::to_string(da->piece) + " piece2=" + std::to_string(da->piece2) +
@@ -472,7 +473,9 @@ class FakeRuntime final : public DeviceRuntime {
                                  da->mode == MCCS_DIRECT_WIDE_RD_LL || da->mode == MCCS_DIRECT_WIDE_RD_ONE_SHOT;
         if (rooted_mode) extra += " root=" + std::to_string(da->root);  // a direct Broadcast / Reduce names its root
         // a wide launch names its scalar (hex); a wide AllReduce's share table is owned= above
-        const bool wide_mode = da->mode >= MCCS_DIRECT_WIDE_LL && da->mode <= MCCS_DIRECT_WIDE_AR_STREAM;
+        // (a block-scaled FP8 AllReduce too, and the payload bytes of a slot)
+        const bool wide_mode = da->mode >= MCCS_DIRECT_WIDE_LL && da->mode <= MCCS_DIRECT_QUANT_TWO_SHOT;
+        if (da->mode == MCCS_DIRECT_QUANT_TWO_SHOT) extra += " pay=" + std::to_string(MCCS_QUANT_PAY(da->slot_bytes));
         if (wide_mode) {
           char hex[32];
           std::snprintf(hex, sizeof(hex), " op_arg=%llx", (unsigned long long)da->op_arg);
@@ -602,7 +605,7 @@ class FakeRuntime final : public DeviceRuntime {
       for (int op : {(int)mccsDevSum, (int)mccsDevPreMulSum})
         if (fn == direct_wide_kernel_ptr(dt, op) || fn == direct_wide_rs_kernel_ptr(dt, op) ||
             fn == direct_wide_rd_kernel_ptr(dt, op) || fn == direct_wide_stream_kernel_ptr(dt, op) ||
-            fn == direct_wide_stream_ar_kernel_ptr(dt, op))
+            fn == direct_wide_stream_ar_kernel_ptr(dt, op) || fn == direct_quant_kernel_ptr(dt, op))
           return;
     const mccsMultiLaunchArgs* ma = (const mccsMultiLaunchArgs*)args[0];
     if (ma->inline_works) return;

@@ -521,6 +521,26 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 // same rank sends other ranges.
 // Every wait is direct_wait: it polls the abort flag and the watchdog and
 // returns on either.
+//
+// Block-scaled FP8 AllReduce (direct_quant.h, opt-in: mccsCommSetAllReduceQuant;
+// fp16 and bf16, Sum and PreMulSum) uses the two-shot slots, counts and state
+// and adds no slot; only the bytes inside a slot differ (MCCS_QUANT_PAY below).
+// Its hand-offs are the wide two-shot's with owned[t] = rank t's share by
+// MCCS_QUANT_SHARE (multiples of 512 elements; trailing ranks may own nothing):
+// sender s adds owned[t] ELEMENTS to t's IN_CNT(s), owner o adds owned[o] to
+// every peer's OUT_CNT(o), E_IN += owned[self], E_OUT[t] += owned[t], LAUNCHES
+// += 1.  So the reuse paragraphs and the parity of the one-shot and LL slots
+// hold across any mix with the other direct launches, by the wide two-shot's
+// argument: count >= 1 makes rank 0 an owner, every rank hands rank 0 its part
+// of that share inside the launch, and a rank that owns nothing reads no in
+// slot and writes no out slot.
+// In place (recv == send).  Phase 2 loads and stores each element of the own
+// share through one lane, and phase 1 never reads the own share.  Phase 3
+// stores into foreign shares, which only phase 1 reads: both phases deal their
+// pieces through one function with the same numbering (piece p to workgroup p
+// mod G, unit u of a piece to wave u mod waves), so the wave that stores a unit
+// in phase 3 is the one that loaded it in phase 1, two count-outs (each a drain
+// and a barrier) earlier.  That is direct_body's argument, with units for packs.
 #define MCCS_DIRECT_MAX_RANKS 8
 #define MCCS_DIRECT_CTRL_BYTES 65536
 // u64, added to by sender s; a rank's own line IN_CNT(rank) counts its own
@@ -577,6 +597,19 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 #define MCCS_DIRECT_WIDE_RS_STREAM 18    // rounds through the one-shot slots, counted on IN_CNT, acknowledged on ACK
 // wide streamed AllReduce (direct_wide_stream_ar.h; count of any size, owned[] the two-shot's split, rounds x round_elems)
 #define MCCS_DIRECT_WIDE_AR_STREAM 19    // scatter through the one-shot slots, gather through the halves of the two-shot in slots
+// block-scaled FP8 AllReduce (direct_quant.h; fp16 / bf16, op_arg as WIDE, owned[] = the split by MCCS_QUANT_SHARE)
+#define MCCS_DIRECT_QUANT_TWO_SHOT 20  // through the two-shot slots: E4M3 codes and one E8M0 byte per 32 elements
+// Its wire layout.  Every two-shot slot it uses (the in slot per sender, the out
+// slot) is split in two: a payload of PAY bytes, the code of element e at byte
+// e, and behind it the scale region, the byte of block k (elements [32k, 32k +
+// 32) of the buffer) at PAY + k.  PAY = slot_bytes x 32 / 33 cut down to a
+// multiple of 512, so PAY + PAY / 32 <= slot_bytes; count <= PAY.  A wave moves
+// units of 512 elements (512 payload bytes + 16 scale bytes, always whole on
+// the slot side), so shares start on multiples of 512 elements.
+#define MCCS_QUANT_UNIT 512
+#define MCCS_QUANT_PAY(slot_bytes) (((uint64_t)(slot_bytes) * 32 / 33) & ~(uint64_t)(MCCS_QUANT_UNIT - 1))
+#define MCCS_QUANT_SHARE(count, n) \
+  ((((count) + (n) - 1) / (n) + (MCCS_QUANT_UNIT - 1)) & ~(uint64_t)(MCCS_QUANT_UNIT - 1))
 
 struct mccsDirectRank {  // one rank slot of a direct launch (blockIdx.y)
   const void* send;
@@ -599,13 +632,13 @@ struct mccsDirectArgs {
   uint64_t timeout_ticks;  // s_memrealtime ticks; 0 = never
   uint32_t nranks, nch, nthr_ref, buff_size;  // the ring walk this launch reproduces
   uint32_t fence_mode;                        // MCCS_FENCE_*
-  uint32_t mode;                              // MCCS_DIRECT_* above (RS: direct_rs_kernel only; RD / BC: direct_rooted.h's kernels only; WIDE: direct_wide_kernel only; WIDE_RS / WIDE_RD: direct_wide_rs.h's kernels only; WIDE_RS_STREAM: direct_wide_stream_kernel only; WIDE_AR_STREAM: direct_wide_stream_ar_kernel only)
+  uint32_t mode;                              // MCCS_DIRECT_* above (RS: direct_rs_kernel only; RD / BC: direct_rooted.h's kernels only; WIDE: direct_wide_kernel only; WIDE_RS / WIDE_RD: direct_wide_rs.h's kernels only; WIDE_RS_STREAM: direct_wide_stream_kernel only; WIDE_AR_STREAM: direct_wide_stream_ar_kernel only; QUANT: direct_quant_kernel only)
   uint32_t piece;                             // elements per piece of the scatter / gather phases
   uint32_t piece2;                            // elements per piece of the reduction phase
   uint32_t no_guard;                          // 1: skip the launch guard (test hook only)
   uint32_t root;                              // the RD / BC / WIDE_RD modes: the root (one for all rank slots); else 0
   uint64_t guard_order;                       // rank slots by guard address, 4 bits each (launch_guard.h)
-  uint64_t owned[MCCS_DIRECT_MAX_RANKS];      // elements of the walk's chunks each rank owns (wide two-shot and WIDE_AR_STREAM: of its share)
+  uint64_t owned[MCCS_DIRECT_MAX_RANKS];      // elements of the walk's chunks each rank owns (wide two-shot, WIDE_AR_STREAM and QUANT: of its share)
   uint8_t idx2rank[MCCS_MAX_NCHANNELS][MCCS_DIRECT_MAX_RANKS];  // rank at ring index k of channel bid
   uint64_t op_arg;  // the wide modes: the PreMulSum scalar (T in the low bits); else 0 (the fields above keep their place)
   uint64_t rounds;       // WIDE_RS_STREAM: K = ceil(count / round_elems) >= 1; WIDE_AR_STREAM: ceil(share / round_elems); else 0

@@ -9,6 +9,10 @@ direct kernel should take a bucket.
   python tools/direct_bench.py [--n 2 4 8] [--sizes-kib 32 128 ...] [--blocks 32 128]
 Per (n, size): ring / direct us per call, eager (back-to-back calls, one
 sync) and graph-replayed (20 calls per graph).
+  python tools/direct_bench.py --algos direct wide-direct quant --dtype bfloat16 [--n 4 8] [--sizes-kib 1024 4096 8192]
+The two opt-in two-shots beside the ring-order one at the same sizes, each on
+the two-shot's arena: the wide-accumulate one (mccsCommSetAllReduceWide) and the
+block-scaled FP8 one (mccsCommSetAllReduceQuant); float16 / bfloat16 only.
   python tools/direct_bench.py --reduce-scatter [--n 2 4 8] [--sizes-kib 1 4 ...]
 ReduceScatter per block size (1 KiB to the caps by default): the ring (limits
 0), the direct and the LL variant (mccsCommSetReduceScatterDirect) and the
@@ -493,7 +497,8 @@ def main():
     ap.add_argument("--dtype", default="float16")
     ap.add_argument("--oneshot-max-kib", type=int, default=2048)
     ap.add_argument("--algos", nargs="+", default=["ring", "direct", "oneshot", "ll"],
-                    help="variants to time (rocprof passes isolate one kernel mode each)")
+                    help="variants to time, among ring direct oneshot ll wide-direct quant (rocprof passes isolate one "
+                         "kernel mode each)")
     ap.add_argument("--allgather", action="store_true", help="time AllGather (size = bytes per rank): ring vs one-shot")
     ap.add_argument("--reduce-scatter", action="store_true",
                     help="time ReduceScatter (size = bytes per block, 1 KiB to the caps): ring vs direct vs LL, and "
@@ -513,6 +518,7 @@ def main():
     ap.add_argument("--graph-calls", type=int, default=4, help="--wide --stream: calls captured into each replayed graph")
     ap.add_argument("--regions", type=int, default=5, help="--rooted, --wide: timed regions of --calls calls per variant")
     args = ap.parse_args()
+    args.algos = [a for word in args.algos for a in word.split(",") if a]  # "direct,quant" or "direct quant"
     dt = getattr(torch, args.dtype)
     code = {torch.float16: 6, torch.float32: 7, torch.bfloat16: 9}[dt]
     es = torch.empty(0, dtype=dt).element_size()
@@ -541,13 +547,23 @@ def main():
         cfgs = {"ring": C.CommConfig(direct_bytes=-1, oneshot_bytes=-1, ll_bytes=-1),
                 "direct": C.CommConfig(direct_bytes=top, oneshot_bytes=-1, ll_bytes=-1),
                 "oneshot": C.CommConfig(direct_bytes=-1, ll_bytes=-1, oneshot_bytes=min(top, args.oneshot_max_kib << 10)),
-                "ll": C.CommConfig(direct_bytes=-1, oneshot_bytes=-1, ll_bytes=1 << 20)}
+                "ll": C.CommConfig(direct_bytes=-1, oneshot_bytes=-1, ll_bytes=1 << 20),
+                # the two opt-in two-shots on the two-shot's own arena (float16 / bfloat16 only)
+                "wide-direct": C.CommConfig(direct_bytes=top, oneshot_bytes=-1, ll_bytes=-1),
+                "quant": C.CommConfig(direct_bytes=top, oneshot_bytes=-1, ll_bytes=-1)}
+        cfgs = {a: cfg for a, cfg in cfgs.items() if a in args.algos}
+        assert es == 2 or not {"wide-direct", "quant"} & set(cfgs), "wide-direct and quant time float16 / bfloat16"
+
+        def opt_in(algo, comms):
+            for c in comms:
+                if algo == "wide-direct":
+                    c.set_all_reduce_wide(twoshot_bytes=top)
+                if algo == "quant":
+                    c.set_all_reduce_quant(top)
+            return comms
         if len(args.blocks) == 1:
             os.environ["MCCS_DIRECT_BLOCKS"] = str(args.blocks[0])
-        sets = {a: C.init_all([0] * n, cfg) for a, cfg in cfgs.items()}
-        for a in [a for a in sets if a not in args.algos]:
-            for c in sets.pop(a):
-                c.destroy()
+        sets = {a: opt_in(a, C.init_all([0] * n, cfg)) for a, cfg in cfgs.items()}
         for kib in args.sizes_kib:
             cnt = (kib << 10) // es
             xs = [torch.randn(cnt, device="cuda").to(dt) for _ in range(n)]
@@ -564,7 +580,7 @@ def main():
                         os.environ["MCCS_DIRECT_BLOCKS"] = str(blocks)
                         for c in comms:
                             c.destroy()
-                        comms = sets[algo] = C.init_all([0] * n, cfgs[algo])
+                        comms = sets[algo] = opt_in(algo, C.init_all([0] * n, cfgs[algo]))
 
                     def once():
                         with C.group():
@@ -577,7 +593,7 @@ def main():
                     for _ in range(5):
                         once()
                     st.synchronize()
-                    assert comms[0].last_algo() == algo, (algo, comms[0].last_algo())
+                    assert comms[0].last_algo() == {"quant": "quant-direct"}.get(algo, algo), (algo, comms[0].last_algo())
                     t0 = time.perf_counter()
                     for _ in range(args.calls):
                         once()
