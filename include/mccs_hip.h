@@ -718,6 +718,55 @@ mccsResult_t mccsCommAllReduceWideStreamMax(mccsComm_t comm, size_t *round_cap);
  * node gate does not cover this path. */
 mccsResult_t mccsCommSetAllReduceQuant(mccsComm_t comm, size_t min_bytes, size_t max_bytes);
 mccsResult_t mccsCommAllReduceQuantMax(mccsComm_t comm, size_t *cap);
+/* The block-scaled FP8 streamed ReduceScatter, for mccsFloat16 and mccsBfloat16
+ * with Sum or PreMulSum (so mccsAvgOp), for a block of ANY size: the streamed
+ * ReduceScatter's rounds through the one-shot slots, with the n-1 foreign
+ * blocks crossing the links in the FP8 AllReduce's wire format (an E4M3FN code
+ * per element plus one E8M0 scale byte per 32 elements, about 8.25 bits per
+ * element), ONCE: the owner's own input never crosses the wire and the binary32
+ * sum is rounded straight to the output.  IT IS LOSSY ON PURPOSE: on N(0,1)
+ * bf16 inputs the relative L2 error against the exact sum is 1.9e-2, 2.3e-2 and
+ * 2.5e-2 at 2, 4 and 8 ranks (computed on the CPU from the definition;
+ * DESIGN.md section 8).  Off by default.
+ * Definition.  recvcount = c elements per block.  A quantisation block is the
+ * 32 elements [32k, 32k + 32) counted from the start of a ReduceScatter block
+ * (not of the buffer), elements past c counting as +0; QDQ as above.  For
+ * output block t on rank t, in RANK order: y_r = f32(x_r[t]) for r == t (the
+ * owner's own input, exact), QDQ(f32(x_r[t])) otherwise; t_r = y_r, or
+ * fl32(y_r * f32(s)) for PreMulSum (never a fused multiply-add); acc = t_0;
+ * acc = fl32(acc + t_r); out = T(acc), one rounding to nearest even.  The
+ * result is a function of the inputs, nranks and t alone, in place or not,
+ * whatever the rings, the round size and the number of rounds.  ONE Inf OR NaN
+ * IN A FOREIGN INPUT MAKES THAT BLOCK OF 32 NaN ON THE OWNER; one in the
+ * owner's own input touches only its element.
+ * mccsCommReduceScatterQuantMax: *round_cap, the largest round in INPUT bytes:
+ * twice the payload bytes of a one-shot slot (slot * 32 / 33 cut to a multiple
+ * of 512), about 1.94 times a 16-bit round of the same slot; 0 without one-shot
+ * slots, outside 2..8 ranks, without peer atomics or unconnected.
+ * mccsCommSetReduceScatterQuant: a qualifying mccsReduceScatter (count > 0,
+ * 2 <= nranks <= 8) of min_block_bytes <= bytes PER BLOCK <= max_block_bytes
+ * that is its communicator's only call of the launch takes this path
+ * (mccsCommLastAlgo reports MCCS_ALGO_QUANT_STREAM), decided BEFORE the wide
+ * limits and the ring-order direct variants see the call; max_block_bytes 0 =
+ * off, and then every call plans exactly as without this entry point; there is
+ * no maximum.  round_bytes: the input bytes of one round, 0 = *round_cap, else
+ * a multiple of 1024 (512 elements) of at most *round_cap.  An unconnected
+ * communicator, min_block_bytes > max_block_bytes, a round_bytes that is no
+ * multiple of 1024 or above *round_cap, and a max_block_bytes > 0 where
+ * *round_cap is 0 are refused with mccsInvalidArgument; a call while the
+ * communicator has a group open or a call pending, with mccsInvalidUsage.
+ * MCCS_RS_QUANT_MIN_BYTES / MCCS_RS_QUANT_BYTES / MCCS_RS_QUANT_ROUND_BYTES in
+ * the environment set the three at creation (the round clamped to *round_cap
+ * and cut to a multiple of 1024, at least 1024).  EVERY RANK MUST SET THE SAME
+ * THREE VALUES: ranks that disagree run different rounds of one call and stall
+ * until the watchdog; this is not detected.  One sharing a group with a second
+ * call of the communicator goes to the ring with its scalar; every other dtype
+ * and op plans as before.  In place is supported; ranks sharing a GPU are
+ * fused into one launch; the call may be captured into a HIP graph.  The node
+ * gate does not cover this path. */
+mccsResult_t mccsCommSetReduceScatterQuant(mccsComm_t comm, size_t min_block_bytes, size_t max_block_bytes,
+                                           size_t round_bytes);
+mccsResult_t mccsCommReduceScatterQuantMax(mccsComm_t comm, size_t *round_cap);
 /* Send / Recv: grouped point-to-point (torch's batch_isend_irecv; the pieces of
  * a Gather or Scatter).  mccsSend moves count * elem_bytes(dtype) bytes from
  * sendbuff to rank `peer`, mccsRecv receives as many from rank `peer` into
@@ -851,7 +900,9 @@ mccsResult_t mccsCommRing(mccsComm_t comm, int ch, int *order);
  * wide-accumulate variants (mccsCommSetAllReduceWide and its siblings;
  * MCCS_ALGO_WIDE_STREAM: mccsCommSetReduceScatterWideStream,
  * mccsCommSetAllReduceWideStream), or MCCS_ALGO_QUANT, the block-scaled FP8
- * AllReduce (mccsCommSetAllReduceQuant) (-1 before the first). */
+ * AllReduce (mccsCommSetAllReduceQuant), or MCCS_ALGO_QUANT_STREAM, the
+ * block-scaled FP8 ReduceScatter (mccsCommSetReduceScatterQuant) (-1 before
+ * the first). */
 #define MCCS_ALGO_RING 0
 #define MCCS_ALGO_DIRECT 1
 #define MCCS_ALGO_ONESHOT 2
@@ -861,6 +912,7 @@ mccsResult_t mccsCommRing(mccsComm_t comm, int ch, int *order);
 #define MCCS_ALGO_WIDE_DIRECT 6
 #define MCCS_ALGO_WIDE_STREAM 7
 #define MCCS_ALGO_QUANT 8
+#define MCCS_ALGO_QUANT_STREAM 9
 int mccsCommLastAlgo(mccsComm_t comm);
 /* 1 when the comm may run the direct kernel: a direct region was configured
  * and every device of the communicator can perform atomics on every other's

@@ -48,6 +48,13 @@
 // no send reads the own block, and a fold loads and stores each element through
 // one thread.  With an odd recvcount block t starts 2 bytes off a pack, so the
 // copies and the own operand take direct_reduce's / wide_reduce's typed path.
+//
+// The round loop, its counts and its waits are written once, in
+// direct_stream_body, templated on the data path: a Path supplies piece() (a
+// planner's piece made usable), send() (one piece of a foreign block into a
+// slot) and fold() (one piece of the own block out of the n-1 slots).
+// WideStreamPath below is this file's 16-bit path; direct_quant_stream.h's
+// QuantStreamPath puts FP8 codes and scale bytes into the same slots.
 #pragma once
 #include "direct_wide.h"
 
@@ -58,8 +65,33 @@ static_assert(MCCS_DIRECT_SEND_DONE(4) <= MCCS_DIRECT_CTRL_BYTES && MCCS_DIRECT_
 
 namespace mccs {
 
+// The 16-bit data path: element e of a round at byte 2 e of the slot.
 template <int DT, bool PRE>
-__device__ __forceinline__ void direct_wide_stream_body(const mccsDirectArgs& a) {
+struct WideStreamPath {
+  using T = typename Elem<DT>::T;
+  static __device__ __forceinline__ uint32_t piece(uint32_t p) { return p > 0 ? p : 1; }
+  // ne elements at src (a foreign block's, at round offset off) into the owner's slot for this rank
+  static __device__ __forceinline__ void send(int64_t, const T* src1, char* slot, int64_t off, int64_t ne) {
+    const void* src[MCCS_DIRECT_MAX_RANKS] = {src1};
+    void* dst[MCCS_DIRECT_MAX_RANKS] = {slot + off * (int64_t)sizeof(T)};
+    direct_reduce<DT, OpSum>(src, 1, dst, 1, ne);  // one source: a copy
+  }
+  // ne elements of the own block at `own` and of the n-1 slots of this parity at round offset off, into out
+  static __device__ __forceinline__ void fold(int64_t oslot, int n, uint32_t rank, const T* own, const char* slots,
+                                              int64_t off, T* out, int64_t ne, float s) {
+    const void* src[MCCS_DIRECT_MAX_RANKS];
+    void* dst[MCCS_DIRECT_MAX_RANKS] = {out};
+#pragma unroll
+    for (int r = 0; r < MCCS_DIRECT_MAX_RANKS; ++r)
+      src[r] = r >= n           ? nullptr
+               : r == (int)rank ? (const void*)own
+                                : (const void*)(slots + (int64_t)r * oslot + off * (int64_t)sizeof(T));
+    wide_reduce<DT, PRE>(src, n, dst, 1, ne, s);
+  }
+};
+
+template <int DT, bool PRE, class Path>
+__device__ __forceinline__ void direct_stream_body(const mccsDirectArgs& a) {
   using T = typename Elem<DT>::T;
   __shared__ DirectShm sh;  // (its idx2rank stays unwritten: there is no walk)
   __shared__ uint64_t need[MCCS_DIRECT_MAX_RANKS];
@@ -93,11 +125,9 @@ __device__ __forceinline__ void direct_wide_stream_body(const mccsDirectArgs& a)
   }
   __syncthreads();
   const uint64_t seq0 = sh.seq, e_in = sh.e_in;
-  const int64_t esz = (int64_t)sizeof(T);
   const uint32_t G = gridDim.x, bx = blockIdx.x;
   const uint32_t peers = ((1u << n) - 1u) & ~(1u << rank);
-  const uint32_t piece = a.piece > 0 ? a.piece : 1;
-  const uint32_t piece2 = a.piece2 > 0 ? a.piece2 : 1;
+  const uint32_t piece = Path::piece(a.piece), piece2 = Path::piece(a.piece2);
   const int64_t oslot = (int64_t)a.oslot_bytes;
   const int64_t obase = MCCS_DIRECT_CTRL_BYTES + (int64_t)MCCS_DIRECT_SLOTS * (int64_t)a.slot_bytes;
   // a full round's and the last round's lengths and piece counts: four divisions per launch
@@ -125,9 +155,7 @@ __device__ __forceinline__ void direct_wide_stream_body(const mccsDirectArgs& a)
       for (uint32_t j = bx >= sbase ? bx - sbase : bx + G - sbase; j < nps && sh.ok; j += G) {
         const int64_t off = (int64_t)j * piece;
         const int64_t ne = (int64_t)len - off < (int64_t)piece ? (int64_t)len - off : (int64_t)piece;
-        const void* src[MCCS_DIRECT_MAX_RANKS] = {blk + off};
-        void* dst[MCCS_DIRECT_MAX_RANKS] = {slot + off * esz};
-        direct_reduce<DT, OpSum>(src, 1, dst, 1, ne);  // one source: a copy
+        Path::send(oslot, blk + off, slot, off, ne);
       }
       sbase += nps;
       while (sbase >= G) sbase -= G;
@@ -167,14 +195,7 @@ __device__ __forceinline__ void direct_wide_stream_body(const mccsDirectArgs& a)
     for (uint32_t j = bx >= fbase ? bx - fbase : bx + G - fbase; j < np2 && sh.ok; j += G) {
       const int64_t off = (int64_t)j * piece2;
       const int64_t ne = (int64_t)len - off < (int64_t)piece2 ? (int64_t)len - off : (int64_t)piece2;
-      const void* src[MCCS_DIRECT_MAX_RANKS];
-      void* dst[MCCS_DIRECT_MAX_RANKS] = {(T*)me.recv + roff + off};
-#pragma unroll
-      for (int r = 0; r < MCCS_DIRECT_MAX_RANKS; ++r)
-        src[r] = r >= n           ? nullptr
-                 : r == (int)rank ? (const void*)(own + off)
-                                  : (const void*)(slots + (int64_t)r * oslot + off * esz);
-      wide_reduce<DT, PRE>(src, n, dst, 1, ne, s);
+      Path::fold(oslot, n, rank, own + off, slots, off, (T*)me.recv + roff + off, ne, s);
     }
     fbase += np2;
     while (fbase >= G) fbase -= G;
@@ -226,6 +247,11 @@ __device__ __forceinline__ void direct_wide_stream_body(const mccsDirectArgs& a)
     if (k < K) arrive(k - 1);  // rounds 0 .. K-2 are acknowledged
   }
   if (K >= 2) (void)wait(MCCS_DIRECT_ACK(0), seq0 + K - 2);  // hazard 3: the next launch's first parity is read out
+}
+
+template <int DT, bool PRE>
+__device__ __forceinline__ void direct_wide_stream_body(const mccsDirectArgs& a) {
+  direct_stream_body<DT, PRE, WideStreamPath<DT, PRE>>(a);
 }
 
 }  // namespace mccs

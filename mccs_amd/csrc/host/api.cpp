@@ -1133,6 +1133,43 @@ extern "C" mccsResult_t mccsCommSetReduceScatterWideStream(mccsComm_t comm, size
   return mccsSuccess;
 }
 
+extern "C" mccsResult_t mccsCommReduceScatterQuantMax(mccsComm_t comm, size_t* round_cap) {
+  err_clear();
+  const Comm* c = (const Comm*)comm;
+  if (!c || !round_cap) MCCS_FAIL(mccsInvalidArgument, "mccsCommReduceScatterQuantMax: null communicator or output");
+  *round_cap = c->connected && c->nranks >= 2 && c->nranks <= MCCS_DIRECT_MAX_RANKS ? rs_quant_cap(c) : 0;
+  return mccsSuccess;
+}
+
+extern "C" mccsResult_t mccsCommSetReduceScatterQuant(mccsComm_t comm, size_t min_block_bytes, size_t max_block_bytes,
+                                                      size_t round_bytes) {
+  err_clear();
+  StepScope st("mccsCommSetReduceScatterQuant");
+  Comm* c = (Comm*)comm;
+  if (!c || !c->connected) MCCS_FAIL(mccsInvalidArgument, "the communicator is not connected");
+  if (g_group.depth > 0 || c->plan_pending)
+    MCCS_FAIL(mccsInvalidUsage, "the communicator has a group open or a call pending: set the limits between launches");
+  const size_t cap = c->nranks >= 2 && c->nranks <= MCCS_DIRECT_MAX_RANKS ? rs_quant_cap(c) : 0;
+  const char* closed = cap ? "" : " (no one-shot slots or no peer atomics: the count-based path is closed here)";
+  if (max_block_bytes > 0 && cap == 0)
+    MCCS_FAIL(mccsInvalidArgument, "max_block_bytes %zu: there is no one-shot slot to stream a block through%s",
+              max_block_bytes, closed);
+  if (min_block_bytes > max_block_bytes)
+    MCCS_FAIL(mccsInvalidArgument, "min_block_bytes %zu is above max_block_bytes %zu: the window is empty "
+              "(max_block_bytes 0 = off)", min_block_bytes, max_block_bytes);
+  if (round_bytes % (2 * MCCS_QUANT_UNIT))
+    MCCS_FAIL(mccsInvalidArgument, "round_bytes %zu is not a multiple of 1024 (a round is whole units of 512 elements; "
+              "0 = the largest round of %zu bytes)", round_bytes, cap);
+  if (round_bytes > cap)
+    MCCS_FAIL(mccsInvalidArgument, "round_bytes %zu is above the %zu bytes whose FP8 codes and scale bytes fit a "
+              "one-shot slot%s", round_bytes, cap, closed);
+  c->rs_quant_min_bytes = min_block_bytes;
+  c->rs_quant_bytes = max_block_bytes;
+  c->rs_quant_round = round_bytes;
+  rs_quant_prepare(c);
+  return mccsSuccess;
+}
+
 extern "C" mccsResult_t mccsCommAllToAllRoute(mccsComm_t comm, int* info2) {
   const Comm* c = (const Comm*)comm;
   if (!c || !info2) return mccsInvalidArgument;

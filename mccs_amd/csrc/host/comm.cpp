@@ -578,6 +578,7 @@ mccsResult_t comm_build_device(Comm* c) {
   ar_wide_read_env(c);        // and the wide AllReduce's
   rs_wide_read_env(c);        // and the wide ReduceScatter's / Reduce's
   ar_quant_read_env(c);       // and the block-scaled FP8 AllReduce's
+  rs_quant_read_env(c);       // and the block-scaled FP8 ReduceScatter's
   {
     std::lock_guard<std::mutex> lk(g_live_mu);
     g_live_fifo_slots[c->d_comm] = c->cfg.fifo_slots;

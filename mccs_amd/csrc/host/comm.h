@@ -361,6 +361,15 @@ struct Comm {
   // true) BEFORE the wide limits see it and runs direct_quant_kernel.  Every
   // rank must set the same values.
   size_t ar_quant_min_bytes = 0, ar_quant_bytes = 0;
+  // Block-scaled FP8 streamed ReduceScatter (direct_quant_stream.h).  The
+  // opt-in window in bytes per block, max without a cap and 0 = off
+  // (mccsCommSetReduceScatterQuant; MCCS_RS_QUANT_MIN_BYTES / MCCS_RS_QUANT_BYTES
+  // at creation), and the INPUT bytes of one round (0 = the largest, rs_quant_cap,
+  // else a multiple of 1024 within it; MCCS_RS_QUANT_ROUND_BYTES): a qualifying
+  // ReduceScatter of min <= block bytes <= max is held in `direct` (wide =
+  // true) BEFORE the wide limits see it and runs direct_quant_stream_kernel.
+  // Every rank must set the same values.
+  size_t rs_quant_min_bytes = 0, rs_quant_bytes = 0, rs_quant_round = 0;
   // Direct Broadcast and Reduce (direct_rooted.h).  The four opt-in limits in
   // bytes of the whole buffer (mccsCommSetRootedDirect; MCCS_BC_DIRECT_BYTES /
   // MCCS_BC_LL_BYTES / MCCS_RD_DIRECT_BYTES / MCCS_RD_LL_BYTES at creation),
@@ -527,6 +536,12 @@ void ar_wide_stream_prepare(const Comm* c);  // probes the four streamed AllRedu
 size_t ar_quant_cap(const Comm* c);
 void ar_quant_read_env(Comm* c);
 void ar_quant_prepare(const Comm* c);  // after the limits changed: probes the four quant kernels' co-residency once
+// Block-scaled FP8 streamed ReduceScatter: the round cap is 2 x MCCS_QUANT_PAY(one one-shot slot) input bytes (0
+// unless direct_ok).  rs_quant_read_env reads MCCS_RS_QUANT_MIN_BYTES / MCCS_RS_QUANT_BYTES (kept only where the cap
+// > 0) and MCCS_RS_QUANT_ROUND_BYTES (clamped to the cap, cut to a multiple of 1024, at least 1024).
+size_t rs_quant_cap(const Comm* c);
+void rs_quant_read_env(Comm* c);
+void rs_quant_prepare(const Comm* c);  // probes the four streamed quant kernels' co-residency once
 mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_t>& user_streams);
 // ring.hip
 const void* ring_kernel_ptr(int func, int dtype, int op);
@@ -552,6 +567,8 @@ const void* direct_wide_stream_kernel_ptr(int dtype, int op);
 const void* direct_wide_stream_ar_kernel_ptr(int dtype, int op);
 // direct_quant.hip (likewise)
 const void* direct_quant_kernel_ptr(int dtype, int op);
+// direct_quant_stream.hip (likewise)
+const void* direct_quant_stream_kernel_ptr(int dtype, int op);
 hipError_t ring_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_flush_caches(hipStream_t st);
 

@@ -597,6 +597,29 @@ void ar_quant_read_env(Comm* c) {
   ar_quant_prepare(c);
 }
 
+// ---- block-scaled FP8 streamed ReduceScatter (direct_quant_stream.h) ------------
+// One one-shot slot holds PAY_O codes and their scale bytes, so a round of up
+// to PAY_O 2-byte elements: the cap is in INPUT bytes; its counts are remote
+// atomics.  The block itself has no cap.
+size_t rs_quant_cap(const Comm* c) { return c->direct_ok ? 2 * (size_t)MCCS_QUANT_PAY(c->layout.oneshot_slot) : 0; }
+
+void rs_quant_read_env(Comm* c) {
+  auto read = [&](const char* name, size_t cap) {
+    const char* v = std::getenv(name);
+    const long long x = v ? std::atoll(v) : 0;
+    return x > 0 ? std::min((size_t)x, cap) : (size_t)0;
+  };
+  const size_t cap = rs_quant_cap(c);
+  c->rs_quant_min_bytes = cap > 0 ? read("MCCS_RS_QUANT_MIN_BYTES", SIZE_MAX) : 0;
+  c->rs_quant_bytes = cap > 0 ? read("MCCS_RS_QUANT_BYTES", SIZE_MAX) : 0;
+  // the round: clamped to the cap, cut to whole units of 512 elements
+  // (1 .. 1023 is the smallest round, not 0 = the largest)
+  const size_t round = read("MCCS_RS_QUANT_ROUND_BYTES", cap);
+  c->rs_quant_round = round & ~(size_t)(2 * MCCS_QUANT_UNIT - 1);
+  if (c->rs_quant_round == 0 && round > 0) c->rs_quant_round = 2 * MCCS_QUANT_UNIT;
+  rs_quant_prepare(c);
+}
+
 // The wide ReduceScatter's and Reduce's limits (direct_wide_rs.h): the direct
 // ReduceScatter's caps and conditions, per block / over the whole buffer.
 void rs_wide_read_env(Comm* c) {
@@ -630,6 +653,9 @@ void rs_wide_read_env(Comm* c) {
 static int wide_mode(const Comm* c, int func, size_t bytes) {
   if (func == mccsFuncReduceScatter || func == mccsFuncReduce) {
     const bool rd = func == mccsFuncReduce;
+    // the block-scaled FP8 window of a ReduceScatter is decided before the wide limits, at any block size
+    if (!rd && c->rs_quant_bytes > 0 && bytes >= c->rs_quant_min_bytes && bytes <= c->rs_quant_bytes && rs_quant_cap(c) > 0)
+      return MCCS_DIRECT_QUANT_RS_STREAM;
     if (bytes <= (rd ? c->rd_wide_ll_bytes : c->rs_wide_ll_bytes) && bytes <= rs_ll_cap(c))
       return rd ? MCCS_DIRECT_WIDE_RD_LL : MCCS_DIRECT_WIDE_RS_LL;
     if (bytes <= (rd ? c->rd_wide_bytes : c->rs_wide_bytes) && bytes <= rs_direct_cap(c))
@@ -1119,6 +1145,8 @@ static bool direct_group(std::vector<Comm*>& comms, const std::vector<int>& idx)
         ck->rs_wide_stream_bytes != c0->rs_wide_stream_bytes || ck->rs_wide_stream_round != c0->rs_wide_stream_round ||
         ck->ar_wide_stream_bytes != c0->ar_wide_stream_bytes || ck->ar_wide_stream_round != c0->ar_wide_stream_round ||
         ck->ar_quant_min_bytes != c0->ar_quant_min_bytes || ck->ar_quant_bytes != c0->ar_quant_bytes ||
+        ck->rs_quant_min_bytes != c0->rs_quant_min_bytes || ck->rs_quant_bytes != c0->rs_quant_bytes ||
+        ck->rs_quant_round != c0->rs_quant_round ||
         ck->direct.op_arg != c0->direct.op_arg)  // one scalar for every rank slot (mccsDirectArgs.op_arg)
       return false;
   }
@@ -1496,11 +1524,12 @@ static mccsResult_t build_direct_rooted(std::vector<Comm*>& comms, const std::ve
 // `stream`: the four streamed ReduceScatter kernels (direct_wide_stream.h), or
 // with rs = false the four streamed AllReduce kernels
 // (direct_wide_stream_ar.h), each cached apart again; `quant`: the four
-// block-scaled FP8 AllReduce kernels (direct_quant.h), cached apart too.
+// block-scaled FP8 AllReduce kernels (direct_quant.h), or with rs = true the
+// four streamed FP8 ReduceScatter kernels (direct_quant_stream.h), cached apart too.
 static int coresident_wide_blocks(int device, int* ncu_out, bool rs = false, bool stream = false, bool quant = false) {
   static std::mutex mu;
   static std::map<std::tuple<unsigned, int, int>, std::pair<int, int>> cache;  // (runtime, device, family) -> (blocks, CUs)
-  const auto key = std::make_tuple(rt_generation(), device, quant ? 4 : stream ? (rs ? 2 : 3) : rs ? 1 : 0);
+  const auto key = std::make_tuple(rt_generation(), device, quant ? (rs ? 5 : 4) : stream ? (rs ? 2 : 3) : rs ? 1 : 0);
   {
     std::lock_guard<std::mutex> lk(mu);
     auto it = cache.find(key);
@@ -1515,11 +1544,11 @@ static int coresident_wide_blocks(int device, int* ncu_out, bool rs = false, boo
   int best = 1 << 30;
   for (int dt : {(int)mccsFloat16, (int)mccsBfloat16})
     for (int op : {(int)mccsDevSum, (int)mccsDevPreMulSum}) {
-      for (const void* fn : {quant    ? direct_quant_kernel_ptr(dt, op)
+      for (const void* fn : {quant    ? (rs ? direct_quant_stream_kernel_ptr(dt, op) : direct_quant_kernel_ptr(dt, op))
                              : stream ? (rs ? direct_wide_stream_kernel_ptr(dt, op) : direct_wide_stream_ar_kernel_ptr(dt, op))
                              : rs   ? direct_wide_rs_kernel_ptr(dt, op)
                                     : direct_wide_kernel_ptr(dt, op),
-                             rs && !stream ? direct_wide_rd_kernel_ptr(dt, op) : nullptr}) {
+                             rs && !stream && !quant ? direct_wide_rd_kernel_ptr(dt, op) : nullptr}) {
         int per_cu = 0;
         if (!fn) continue;
         if (rt().BlocksPerCu(&per_cu, fn, MCCS_DIRECT_THREADS) != hipSuccess) return 0;  // not cached
@@ -1554,6 +1583,11 @@ void ar_quant_prepare(const Comm* c) {
   if (c->ar_quant_bytes > 0) (void)coresident_wide_blocks(c->device, &ncu, false, false, /*quant=*/true);
 }
 
+void rs_quant_prepare(const Comm* c) {
+  int ncu = 0;
+  if (c->rs_quant_bytes > 0) (void)coresident_wide_blocks(c->device, &ncu, /*rs=*/true, false, /*quant=*/true);
+}
+
 void ar_wide_stream_prepare(const Comm* c) {
   int ncu = 0;
   if (c->ar_wide_stream_bytes > 0) (void)coresident_wide_blocks(c->device, &ncu, /*rs=*/false, /*stream=*/true);
@@ -1572,6 +1606,10 @@ void ar_wide_stream_prepare(const Comm* c) {
 // The block-scaled FP8 AllReduce (direct_quant.h) is built here as well: the
 // two-shot's shape with owned[] cut by MCCS_QUANT_SHARE (shares start on units
 // of 512 elements); its pieces, multiples of 2048 elements, are whole units.
+// The block-scaled FP8 streamed ReduceScatter (direct_quant_stream.h) is the
+// streamed ReduceScatter with a round of whole units: round_elems from the
+// comm's round bytes / 2 (0: MCCS_QUANT_PAY of a one-shot slot), sized from one
+// round's INPUT bytes, so its pieces are whole units as well.
 static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vector<int>& idx, mccsDirectArgs* da,
                                       unsigned* grid_x) {
   const Comm* c0 = comms[idx[0]];
@@ -1598,6 +1636,7 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
   const bool ar_stream = mode == MCCS_DIRECT_WIDE_AR_STREAM;
   const bool stream = mode == MCCS_DIRECT_WIDE_RS_STREAM || ar_stream;
   const bool quant = mode == MCCS_DIRECT_QUANT_TWO_SHOT;
+  const bool quant_rs = mode == MCCS_DIRECT_QUANT_RS_STREAM;
   if (quant && da->count > MCCS_QUANT_PAY(da->slot_bytes)) return mccsInternalError;  // wide_mode: within ar_quant_cap
   size_t rbytes = nbytes;  // the bytes of one block a data phase moves: the streamed modes', of one round
   if (ar_stream) {
@@ -1609,6 +1648,14 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
     da->round_elems = (uint32_t)(round / esize);
     da->rounds = (q + da->round_elems - 1) / da->round_elems;
     rbytes = std::min((size_t)q * esize, round);
+  } else if (quant_rs) {
+    // a round is whole units of 512 elements within the payload of one one-shot slot
+    const size_t cap = rs_quant_cap(c0);
+    const size_t round = c0->rs_quant_round ? c0->rs_quant_round : cap;
+    if (round < 2 * MCCS_QUANT_UNIT || round % (2 * MCCS_QUANT_UNIT) || round > cap) return mccsInternalError;  // api.cpp
+    da->round_elems = (uint32_t)(round / esize);
+    da->rounds = (da->count + da->round_elems - 1) / da->round_elems;
+    rbytes = std::min(nbytes, round);
   } else if (stream) {
     const size_t round = c0->rs_wide_stream_round ? c0->rs_wide_stream_round : c0->layout.oneshot_slot;
     if (round < 16 || round % 16 || round > c0->layout.oneshot_slot) return mccsInternalError;  // api.cpp checked it
@@ -1658,7 +1705,7 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
                          : (oneshot || rd) ? nbytes
                                            : nbytes - nbytes / (size_t)n;
   int ncu = 0;
-  const int cap = coresident_wide_blocks(c0->device, &ncu, rs || rd, stream, quant);
+  const int cap = coresident_wide_blocks(c0->device, &ncu, rs || rd, stream, quant || quant_rs);
   if (ncu <= 0) ncu = cap;
   long g = std::min<long>((long)((scatter + 4095) / 4096), c0->direct_blocks);
   const size_t ll_words = (rs ? (size_t)(n - 1) : 1) * ((nbytes + 7) / 8);
@@ -1882,6 +1929,7 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
         const int func = c0->plan_func, dt = c0->plan_dtype, op = c0->plan_op;  // before the build clears the plan
         MCCS_CHECK(build_direct_wide(comms, idx, &da, &grid));
         fn = da.mode == MCCS_DIRECT_QUANT_TWO_SHOT   ? direct_quant_kernel_ptr(dt, op)
+             : da.mode == MCCS_DIRECT_QUANT_RS_STREAM ? direct_quant_stream_kernel_ptr(dt, op)
              : da.mode == MCCS_DIRECT_WIDE_AR_STREAM ? direct_wide_stream_ar_kernel_ptr(dt, op)
              : da.mode == MCCS_DIRECT_WIDE_RS_STREAM ? direct_wide_stream_kernel_ptr(dt, op)
              : func == mccsFuncReduceScatter     ? direct_wide_rs_kernel_ptr(dt, op)
@@ -2026,6 +2074,7 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
                                      ? MCCS_ALGO_WIDE_ONESHOT
                                  : da.mode == MCCS_DIRECT_WIDE_TWO_SHOT ? MCCS_ALGO_WIDE_DIRECT
                                  : da.mode == MCCS_DIRECT_QUANT_TWO_SHOT ? MCCS_ALGO_QUANT
+                                 : da.mode == MCCS_DIRECT_QUANT_RS_STREAM ? MCCS_ALGO_QUANT_STREAM
                                  : da.mode == MCCS_DIRECT_WIDE_RS_STREAM || da.mode == MCCS_DIRECT_WIDE_AR_STREAM
                                      ? MCCS_ALGO_WIDE_STREAM
                                  : da.mode == MCCS_DIRECT_TWO_SHOT ? MCCS_ALGO_DIRECT

@@ -431,6 +431,19 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 // rounds, so induction on j from rounds 0 and 1 (which wait for no ack) ends.
 // Every wait is direct_wait: it polls the abort flag and the watchdog and
 // returns on either.
+// The block-scaled FP8 streamed ReduceScatter (direct_quant_stream.h, opt-in:
+// mccsCommSetReduceScatterQuant; mode MCCS_DIRECT_QUANT_RS_STREAM) is this
+// launch with other bytes inside the slots, and runs the same round loop
+// (direct_stream_body): the counts stay in ELEMENTS, the lines, the three
+// hazard waits and the state words are the ones above, so the argument holds
+// word for word.  Only the slot layout differs: slot [parity][sender] is split
+// as the FP8 AllReduce splits a two-shot slot (MCCS_QUANT_PAY below, of
+// oslot_bytes): the code of round element e at byte e, the scale byte of the
+// round's block k at PAY_O + k.  B is a multiple of 512 of at most PAY_O, so a
+// round is a whole number of units on the slot side, a sender writes only
+// bytes of its own slot and only below PAY_O + B / 32 <= oslot_bytes, and a
+// reader that saw the round's count reads only bytes that round's senders
+// wrote (the padding of a tail unit included: it is written as +0 codes).
 //
 // Wide streamed AllReduce (direct_wide_stream_ar.h, opt-in:
 // mccsCommSetAllReduceWideStream; fp16 and bf16, Sum and PreMulSum) runs
@@ -606,6 +619,8 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 // multiple of 512, so PAY + PAY / 32 <= slot_bytes; count <= PAY.  A wave moves
 // units of 512 elements (512 payload bytes + 16 scale bytes, always whole on
 // the slot side), so shares start on multiples of 512 elements.
+// block-scaled FP8 streamed ReduceScatter (direct_quant_stream.h; count = recvcount of any size, rounds x round_elems)
+#define MCCS_DIRECT_QUANT_RS_STREAM 21  // WIDE_RS_STREAM's rounds and lines; the one-shot slots split as above, PAY of oslot_bytes
 #define MCCS_QUANT_UNIT 512
 #define MCCS_QUANT_PAY(slot_bytes) (((uint64_t)(slot_bytes) * 32 / 33) & ~(uint64_t)(MCCS_QUANT_UNIT - 1))
 #define MCCS_QUANT_SHARE(count, n) \
@@ -632,7 +647,7 @@ struct mccsDirectArgs {
   uint64_t timeout_ticks;  // s_memrealtime ticks; 0 = never
   uint32_t nranks, nch, nthr_ref, buff_size;  // the ring walk this launch reproduces
   uint32_t fence_mode;                        // MCCS_FENCE_*
-  uint32_t mode;                              // MCCS_DIRECT_* above (RS: direct_rs_kernel only; RD / BC: direct_rooted.h's kernels only; WIDE: direct_wide_kernel only; WIDE_RS / WIDE_RD: direct_wide_rs.h's kernels only; WIDE_RS_STREAM: direct_wide_stream_kernel only; WIDE_AR_STREAM: direct_wide_stream_ar_kernel only; QUANT: direct_quant_kernel only)
+  uint32_t mode;                              // MCCS_DIRECT_* above (RS: direct_rs_kernel only; RD / BC: direct_rooted.h's kernels only; WIDE: direct_wide_kernel only; WIDE_RS / WIDE_RD: direct_wide_rs.h's kernels only; WIDE_RS_STREAM: direct_wide_stream_kernel only; WIDE_AR_STREAM: direct_wide_stream_ar_kernel only; QUANT: direct_quant_kernel only; QUANT_RS_STREAM: direct_quant_stream_kernel only)
   uint32_t piece;                             // elements per piece of the scatter / gather phases
   uint32_t piece2;                            // elements per piece of the reduction phase
   uint32_t no_guard;                          // 1: skip the launch guard (test hook only)
@@ -641,8 +656,8 @@ struct mccsDirectArgs {
   uint64_t owned[MCCS_DIRECT_MAX_RANKS];      // elements of the walk's chunks each rank owns (wide two-shot, WIDE_AR_STREAM and QUANT: of its share)
   uint8_t idx2rank[MCCS_MAX_NCHANNELS][MCCS_DIRECT_MAX_RANKS];  // rank at ring index k of channel bid
   uint64_t op_arg;  // the wide modes: the PreMulSum scalar (T in the low bits); else 0 (the fields above keep their place)
-  uint64_t rounds;       // WIDE_RS_STREAM: K = ceil(count / round_elems) >= 1; WIDE_AR_STREAM: ceil(share / round_elems); else 0
-  uint32_t round_elems;  // the STREAM modes: elements of one round (a multiple of 8, at most one one-shot slot; AR: and half a two-shot slot); else 0
+  uint64_t rounds;       // WIDE_RS_STREAM, QUANT_RS_STREAM: K = ceil(count / round_elems) >= 1; WIDE_AR_STREAM: ceil(share / round_elems); else 0
+  uint32_t round_elems;  // the STREAM modes: elements of one round (a multiple of 8, at most one one-shot slot; AR: and half a two-shot slot; QUANT_RS_STREAM: a multiple of 512, at most MCCS_QUANT_PAY(oslot_bytes)); else 0
   uint32_t pad4;
 };
 #ifdef __cplusplus
