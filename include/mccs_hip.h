@@ -718,6 +718,49 @@ mccsResult_t mccsCommAllReduceWideStreamMax(mccsComm_t comm, size_t *round_cap);
  * node gate does not cover this path. */
 mccsResult_t mccsCommSetAllReduceQuant(mccsComm_t comm, size_t min_bytes, size_t max_bytes);
 mccsResult_t mccsCommAllReduceQuantMax(mccsComm_t comm, size_t *cap);
+/* The block-scaled FP8 streamed AllReduce, for mccsFloat16 and mccsBfloat16
+ * with Sum or PreMulSum (so mccsAvgOp), for a buffer of ANY size: the streamed
+ * AllReduce's rounds (scatter through the one-shot slots, gather through the
+ * halves of the two-shot in slots, one launch), with both legs in the FP8
+ * AllReduce's wire format, about 8.25 bits per element instead of 16.
+ * Definition: mccsCommSetAllReduceQuant's above, UNCHANGED, quantisation blocks
+ * counted from the start of the buffer; the result is a function of the inputs
+ * and nranks alone, the same on every rank, in place or not, whatever the
+ * rings, the round size and the number of rounds, and equal to that path's bits
+ * for a buffer that fits both.  IT IS LOSSY ON PURPOSE (the same relative L2
+ * error, 3.7e-2 to 3.9e-2 on N(0,1) bf16 inputs), and ONE
+ * Inf OR NaN, OR A SUM THAT LEAVES BINARY32, MAKES ITS BLOCK OF 32 NaN ON EVERY
+ * RANK.  Off by default.
+ * mccsCommAllReduceQuantStreamMax: *round_cap, the largest round in INPUT
+ * bytes: twice the smaller of the payload bytes of a one-shot slot and of half
+ * a two-shot slot (bytes * 32 / 33 cut to a multiple of 512); 0 without either
+ * kind of slot, outside 2..8 ranks, without peer atomics or unconnected.
+ * mccsCommSetAllReduceQuantStream: a qualifying mccsAllReduce /
+ * mccsAllReduceOpArg (count > 0, 2 <= nranks <= 8) of min_bytes <= bytes <=
+ * max_bytes that is its communicator's only call of the launch, that the window
+ * of mccsCommSetAllReduceQuant (decided first) leaves, and in which every rank
+ * owns an element -- (nranks - 1) * q < count for q = ceil(count / nranks)
+ * rounded up to 512 -- takes this path (mccsCommLastAlgo reports
+ * MCCS_ALGO_QUANT_STREAM), decided BEFORE the wide limits and the ring-order
+ * direct variants see the call; a count that fails the ownership test plans as
+ * without this entry point.  max_bytes 0 = off; there is no maximum.
+ * round_bytes: the input bytes of one round, 0 = *round_cap, else a multiple of
+ * 1024 (512 elements) of at most *round_cap.  An unconnected communicator,
+ * min_bytes > max_bytes, a round_bytes that is no multiple of 1024 or above
+ * *round_cap, and a max_bytes > 0 where *round_cap is 0 (so outside 2..8 ranks)
+ * are refused with mccsInvalidArgument; a call while the communicator has a
+ * group open or a call pending, with mccsInvalidUsage.
+ * MCCS_AR_QUANT_STREAM_MIN_BYTES / MCCS_AR_QUANT_STREAM_BYTES /
+ * MCCS_AR_QUANT_STREAM_ROUND_BYTES in the environment set the three at creation
+ * (the round clamped to *round_cap and cut to a multiple of 1024, at least
+ * 1024).  EVERY RANK MUST SET THE SAME THREE VALUES: ranks that disagree run
+ * different rounds of one call and stall until the watchdog; this is not
+ * detected.  One sharing a group with a second call of the communicator goes to
+ * the ring with its scalar; every other dtype and op plans as before.  Ranks
+ * sharing a GPU are fused into one launch; the call may be captured into a HIP
+ * graph.  The node gate does not cover this path. */
+mccsResult_t mccsCommSetAllReduceQuantStream(mccsComm_t comm, size_t min_bytes, size_t max_bytes, size_t round_bytes);
+mccsResult_t mccsCommAllReduceQuantStreamMax(mccsComm_t comm, size_t *round_cap);
 /* The block-scaled FP8 streamed ReduceScatter, for mccsFloat16 and mccsBfloat16
  * with Sum or PreMulSum (so mccsAvgOp), for a block of ANY size: the streamed
  * ReduceScatter's rounds through the one-shot slots, with the n-1 foreign
@@ -901,7 +944,8 @@ mccsResult_t mccsCommRing(mccsComm_t comm, int ch, int *order);
  * MCCS_ALGO_WIDE_STREAM: mccsCommSetReduceScatterWideStream,
  * mccsCommSetAllReduceWideStream), or MCCS_ALGO_QUANT, the block-scaled FP8
  * AllReduce (mccsCommSetAllReduceQuant), or MCCS_ALGO_QUANT_STREAM, the
- * block-scaled FP8 ReduceScatter (mccsCommSetReduceScatterQuant) (-1 before
+ * block-scaled FP8 streamed ReduceScatter and AllReduce
+ * (mccsCommSetReduceScatterQuant, mccsCommSetAllReduceQuantStream) (-1 before
  * the first). */
 #define MCCS_ALGO_RING 0
 #define MCCS_ALGO_DIRECT 1

@@ -117,6 +117,8 @@ SIGNATURES: dict[str, tuple] = {
     "mccsCommAllReduceQuantMax": (_c_int, [_c_void_p, _P(_c_size_t)]),
     "mccsCommSetReduceScatterQuant": (_c_int, [_c_void_p, _c_size_t, _c_size_t, _c_size_t]),
     "mccsCommReduceScatterQuantMax": (_c_int, [_c_void_p, _P(_c_size_t)]),
+    "mccsCommSetAllReduceQuantStream": (_c_int, [_c_void_p, _c_size_t, _c_size_t, _c_size_t]),
+    "mccsCommAllReduceQuantStreamMax": (_c_int, [_c_void_p, _P(_c_size_t)]),
     "mccsCommSetAllReduceWide": (_c_int, [_c_void_p, _c_size_t, _c_size_t, _c_size_t]),
     "mccsCommAllReduceWideMax": (_c_int, [_c_void_p, _P(_c_size_t), _P(_c_size_t), _P(_c_size_t)]),
     "mccsCommSetAllReduceWideStream": (_c_int, [_c_void_p, _c_size_t, _c_size_t]),

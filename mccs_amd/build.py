@@ -46,6 +46,7 @@ EXTRA_CFLAGS = {
     "direct_wide_stream_ar.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "direct_quant.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "direct_quant_stream.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "direct_quant_stream_ar.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

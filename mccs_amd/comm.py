@@ -189,7 +189,7 @@ class Communicator:
         """"ring", "direct" (two-shot), "oneshot" or "ll", or a wide-accumulate
         variant ("wide-ll", "wide-oneshot", "wide-direct", "wide-stream"), or
         "quant-direct" (the block-scaled FP8 all_reduce) or "quant-stream" (the
-        block-scaled FP8 reduce_scatter): the
+        block-scaled FP8 reduce_scatter and streamed all_reduce): the
         algorithm of the latest launch (None before one)."""
         a = _sig().mccsCommLastAlgo(self._h)
         return {0: "ring", 1: "direct", 2: "oneshot", 3: "ll", 4: "wide-ll", 5: "wide-oneshot",
@@ -415,6 +415,30 @@ class Communicator:
         block-scaled FP8 all_reduce takes (0 where it cannot be used)."""
         cap = ctypes.c_size_t(0)
         _lib.check(_sig().mccsCommAllReduceQuantMax(self._h, ctypes.byref(cap)), "mccsCommAllReduceQuantMax")
+        return int(cap.value)
+
+    def set_all_reduce_quant_stream(self, max_bytes: int, min_bytes: int = 0, round_bytes: int = 0) -> None:
+        """mccsCommSetAllReduceQuantStream: opts the communicator in to the
+        block-scaled FP8 streamed all_reduce (max_bytes = 0: off, the default;
+        there is no cap).  A Float16 / BFloat16 all_reduce / all_reduce_avg of
+        Sum or PreMulSum that is the communicator's only call of its launch,
+        whose buffer has min_bytes <= bytes <= max_bytes, that
+        set_all_reduce_quant's window (decided first) leaves and in which every
+        rank owns an element runs scatter, fold and gather in rounds of
+        round_bytes of input (0: the largest; else a multiple of 1024 of at
+        most all_reduce_quant_stream_max()) with E4M3 codes and one scale byte
+        per 32 elements on both legs: last_algo() == "quant-stream", decided
+        before the wide limits.  The definition and the bits are
+        set_all_reduce_quant's (LOSSY by design), whatever the round size.
+        Every rank must set the same three values."""
+        _lib.check(_sig().mccsCommSetAllReduceQuantStream(self._h, int(min_bytes), int(max_bytes), int(round_bytes)),
+                   "mccsCommSetAllReduceQuantStream")
+
+    def all_reduce_quant_stream_max(self) -> int:
+        """mccsCommAllReduceQuantStreamMax: the largest round in input bytes of
+        the block-scaled FP8 streamed all_reduce (0 where it cannot be used)."""
+        cap = ctypes.c_size_t(0)
+        _lib.check(_sig().mccsCommAllReduceQuantStreamMax(self._h, ctypes.byref(cap)), "mccsCommAllReduceQuantStreamMax")
         return int(cap.value)
 
     def set_reduce_scatter_quant(self, max_block_bytes: int, min_block_bytes: int = 0, round_bytes: int = 0) -> None:

@@ -47,16 +47,49 @@
 // The launch leaves LAUNCHES += K + 1, E_IN += owned[me], E_OUT[t] += owned[t],
 // E_SELF untouched.  Every wait is direct_wait; none is for the own rank.  Why
 // this is free of races and cycles: ring_cfg.h.
+//
+// The round loop, its counts and its waits are written once, in
+// direct_stream_ar_body, templated on the data path: a Path supplies share()
+// (q), piece() (a planner's piece made usable), send() (one piece of a foreign
+// share into a scatter slot), at() (where a round offset lies in a buffer; the
+// body builds fold's tables with it: per rank in rank order the own input or
+// the scatter slot, and the output or the peer's gather buffer), fold() (one
+// piece of the own share through those tables) and copy() (one piece of a
+// foreign share's results out of a gather buffer).
+// WideStreamArPath below is this file's 16-bit path; direct_quant_stream_ar.h's
+// QuantStreamArPath puts FP8 codes and scale bytes into the same buffers.
 #pragma once
-#include "direct_wide.h"
+#include "direct_wide_stream.h"
 
 static_assert(MCCS_DIRECT_FOLD_DONE(4) <= MCCS_DIRECT_CTRL_BYTES && MCCS_DIRECT_SEND_DONE(4) <= MCCS_DIRECT_FOLD_DONE(0),
               "the streamed AllReduce's arrival words lie in the control block's unused part");
 
 namespace mccs {
 
+// The 16-bit data path: element e of a round at byte 2 e of a scatter slot and
+// of a gather buffer; piece() and send() are the streamed ReduceScatter's.
 template <int DT, bool PRE>
-__device__ __forceinline__ void direct_wide_stream_ar_body(const mccsDirectArgs& a) {
+struct WideStreamArPath : WideStreamPath<DT, PRE> {
+  using T = typename Elem<DT>::T;
+  static __device__ __forceinline__ uint64_t share(uint64_t count, uint64_t n) { return MCCS_WIDE_SHARE(count, n); }
+  // where round element off lies in a scatter slot and in a gather buffer (bytes)
+  static __device__ __forceinline__ int64_t at(int64_t off) { return off * (int64_t)sizeof(T); }
+  // ne elements in rank order: src[r] the own input (r == rank) or scatter slot r at at(off), dst[r] the output or
+  // peer r's gather buffer for this rank at at(off)
+  static __device__ __forceinline__ void fold(int64_t, int64_t, int n, uint32_t, const void** src, void** dst, int64_t,
+                                              int64_t ne, float s) {
+    wide_reduce<DT, PRE>(src, n, dst, n, ne, s);
+  }
+  // ne elements of a foreign share's results at round offset off of this rank's gather buffer for their owner
+  static __device__ __forceinline__ void copy(int64_t, const char* gath, int64_t off, T* out, int64_t ne) {
+    const void* src[MCCS_DIRECT_MAX_RANKS] = {gath + off * (int64_t)sizeof(T)};
+    void* dst[MCCS_DIRECT_MAX_RANKS] = {out};
+    direct_reduce<DT, OpSum>(src, 1, dst, 1, ne);  // one source: a copy
+  }
+};
+
+template <int DT, bool PRE, class Path>
+__device__ __forceinline__ void direct_stream_ar_body(const mccsDirectArgs& a) {
   using T = typename Elem<DT>::T;
   __shared__ DirectShm sh;  // (its idx2rank stays unwritten: there is no walk)
   __shared__ uint64_t need[MCCS_DIRECT_MAX_RANKS];
@@ -93,12 +126,10 @@ __device__ __forceinline__ void direct_wide_stream_ar_body(const mccsDirectArgs&
   }
   __syncthreads();
   const uint64_t seq0 = sh.seq;
-  const int64_t esz = (int64_t)sizeof(T);
   const uint32_t G = gridDim.x, bx = blockIdx.x;
   const uint32_t peers = ((1u << n) - 1u) & ~(1u << rank);
-  const uint32_t piece = a.piece > 0 ? a.piece : 1;
-  const uint32_t piece2 = a.piece2 > 0 ? a.piece2 : 1;
-  const uint64_t q = MCCS_WIDE_SHARE(a.count, (uint64_t)n);  // one 64-bit division per launch
+  const uint32_t piece = Path::piece(a.piece), piece2 = Path::piece(a.piece2);
+  const uint64_t q = Path::share(a.count, (uint64_t)n);  // one 64-bit division per launch
   const int64_t oslot = (int64_t)a.oslot_bytes, slot = (int64_t)a.slot_bytes;
   const int64_t obase = MCCS_DIRECT_CTRL_BYTES + (int64_t)MCCS_DIRECT_SLOTS * slot;
   const int64_t half = (slot / 2) & ~(int64_t)15;  // of a two-shot in slot: one parity's gather buffer
@@ -174,9 +205,7 @@ __device__ __forceinline__ void direct_wide_stream_ar_body(const mccsDirectArgs&
     const int64_t roff = (int64_t)(k * (uint64_t)B);
     const int64_t pbase = obase + (int64_t)((seq0 + k) & 1) * MCCS_DIRECT_MAX_RANKS * oslot + (int64_t)rank * oslot;
     foreign(k, sbase, [&](uint32_t t, int64_t off, int64_t ne) {
-      const void* src[MCCS_DIRECT_MAX_RANKS] = {(const T*)me.send + (int64_t)(t * q) + roff + off};
-      void* dst[MCCS_DIRECT_MAX_RANKS] = {sh.region[t] + pbase + off * esz};
-      direct_reduce<DT, OpSum>(src, 1, dst, 1, ne);  // one source: a copy
+      Path::send(oslot, (const T*)me.send + (int64_t)(t * q) + roff + off, sh.region[t] + pbase, off, ne);
     });
     count_whole(MCCS_DIRECT_SEND_DONE((seq0 + k) & 3), MCCS_DIRECT_IN_CNT(0), [&](uint32_t t) { return len_of(t, k); });
   };
@@ -192,6 +221,7 @@ __device__ __forceinline__ void direct_wide_stream_ar_body(const mccsDirectArgs&
     for (uint32_t j = bx >= fbase ? bx - fbase : bx + G - fbase; j < np2 && sh.ok; j += G) {
       const int64_t off = (int64_t)j * piece2;
       const int64_t ne = (int64_t)len - off < (int64_t)piece2 ? (int64_t)len - off : (int64_t)piece2;
+      const int64_t boff = Path::at(off);
       const void* src[MCCS_DIRECT_MAX_RANKS];
       void* dst[MCCS_DIRECT_MAX_RANKS];
 #pragma unroll
@@ -200,11 +230,11 @@ __device__ __forceinline__ void direct_wide_stream_ar_body(const mccsDirectArgs&
         dst[r] = nullptr;
         if (r < n) {
           src[r] = r == (int)rank ? (const void*)((const T*)me.send + roff + off)
-                                  : (const void*)(slots + (int64_t)r * oslot + off * esz);
-          dst[r] = r == (int)rank ? (void*)((T*)me.recv + roff + off) : (void*)(sh.region[r] + gbase + off * esz);
+                                  : (const void*)(slots + (int64_t)r * oslot + boff);
+          dst[r] = r == (int)rank ? (void*)((T*)me.recv + roff + off) : (void*)(sh.region[r] + gbase + boff);
         }
       }
-      wide_reduce<DT, PRE>(src, n, dst, n, ne, s);
+      Path::fold(oslot, half, n, rank, src, dst, off, ne, s);
     }
     fbase += np2;
     while (fbase >= G) fbase -= G;
@@ -215,9 +245,7 @@ __device__ __forceinline__ void direct_wide_stream_ar_body(const mccsDirectArgs&
     const int64_t roff = (int64_t)(k * (uint64_t)B);
     const char* const gath = mine + MCCS_DIRECT_CTRL_BYTES + (int64_t)((seq0 + k) & 1) * half;
     foreign(k, cbase, [&](uint32_t t, int64_t off, int64_t ne) {
-      const void* src[MCCS_DIRECT_MAX_RANKS] = {gath + (int64_t)t * slot + off * esz};
-      void* dst[MCCS_DIRECT_MAX_RANKS] = {(T*)me.recv + (int64_t)(t * q) + roff + off};
-      direct_reduce<DT, OpSum>(src, 1, dst, 1, ne);
+      Path::copy(half, gath + (int64_t)t * slot, off, (T*)me.recv + (int64_t)(t * q) + roff + off, ne);
     });
   };
   // This workgroup has read all it reads of step i's buffers (the scatter slots
@@ -277,6 +305,11 @@ __device__ __forceinline__ void direct_wide_stream_ar_body(const mccsDirectArgs&
   // Every peer has read every scatter slot and gather buffer of this launch:
   // the next launch of any kind may refill either at once.
   (void)wait_ack(seq0 + K);
+}
+
+template <int DT, bool PRE>
+__device__ __forceinline__ void direct_wide_stream_ar_body(const mccsDirectArgs& a) {
+  direct_stream_ar_body<DT, PRE, WideStreamArPath<DT, PRE>>(a);
 }
 
 }  // namespace mccs

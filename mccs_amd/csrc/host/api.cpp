@@ -1058,6 +1058,42 @@ extern "C" mccsResult_t mccsCommSetAllReduceQuant(mccsComm_t comm, size_t min_by
   return mccsSuccess;
 }
 
+extern "C" mccsResult_t mccsCommAllReduceQuantStreamMax(mccsComm_t comm, size_t* round_cap) {
+  err_clear();
+  const Comm* c = (const Comm*)comm;
+  if (!c || !round_cap) MCCS_FAIL(mccsInvalidArgument, "mccsCommAllReduceQuantStreamMax: null communicator or output");
+  *round_cap = c->connected && c->nranks >= 2 && c->nranks <= MCCS_DIRECT_MAX_RANKS ? ar_quant_stream_cap(c) : 0;
+  return mccsSuccess;
+}
+
+extern "C" mccsResult_t mccsCommSetAllReduceQuantStream(mccsComm_t comm, size_t min_bytes, size_t max_bytes,
+                                                        size_t round_bytes) {
+  err_clear();
+  StepScope st("mccsCommSetAllReduceQuantStream");
+  Comm* c = (Comm*)comm;
+  if (!c || !c->connected) MCCS_FAIL(mccsInvalidArgument, "the communicator is not connected");
+  if (g_group.depth > 0 || c->plan_pending)
+    MCCS_FAIL(mccsInvalidUsage, "the communicator has a group open or a call pending: set the limits between launches");
+  const size_t cap = c->nranks >= 2 && c->nranks <= MCCS_DIRECT_MAX_RANKS ? ar_quant_stream_cap(c) : 0;
+  const char* closed = cap ? "" : " (no one-shot or two-shot slots, or no peer atomics: the count-based path is closed here)";
+  if (max_bytes > 0 && cap == 0)
+    MCCS_FAIL(mccsInvalidArgument, "max_bytes %zu: there are no slots to stream a buffer through%s", max_bytes, closed);
+  if (min_bytes > max_bytes)
+    MCCS_FAIL(mccsInvalidArgument, "min_bytes %zu is above max_bytes %zu: the window is empty (max_bytes 0 = off)",
+              min_bytes, max_bytes);
+  if (round_bytes % (2 * MCCS_QUANT_UNIT))
+    MCCS_FAIL(mccsInvalidArgument, "round_bytes %zu is not a multiple of 1024 (a round is whole units of 512 elements; "
+              "0 = the largest round of %zu bytes)", round_bytes, cap);
+  if (round_bytes > cap)
+    MCCS_FAIL(mccsInvalidArgument, "round_bytes %zu is above the %zu bytes whose FP8 codes and scale bytes fit a "
+              "one-shot slot and half a two-shot slot%s", round_bytes, cap, closed);
+  c->ar_quant_stream_min_bytes = min_bytes;
+  c->ar_quant_stream_bytes = max_bytes;
+  c->ar_quant_stream_round = round_bytes;
+  ar_quant_stream_prepare(c);
+  return mccsSuccess;
+}
+
 // The wide ReduceScatter's (rd = false) and Reduce's (rd = true) two limits.
 static mccsResult_t set_rs_wide(mccsComm_t comm, bool rd, size_t ll_bytes, size_t bytes) {
   err_clear();

@@ -579,6 +579,7 @@ mccsResult_t comm_build_device(Comm* c) {
   rs_wide_read_env(c);        // and the wide ReduceScatter's / Reduce's
   ar_quant_read_env(c);       // and the block-scaled FP8 AllReduce's
   rs_quant_read_env(c);       // and the block-scaled FP8 ReduceScatter's
+  ar_quant_stream_read_env(c);  // and the block-scaled FP8 streamed AllReduce's
   {
     std::lock_guard<std::mutex> lk(g_live_mu);
     g_live_fifo_slots[c->d_comm] = c->cfg.fifo_slots;

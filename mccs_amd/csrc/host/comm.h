@@ -370,6 +370,17 @@ struct Comm {
   // true) BEFORE the wide limits see it and runs direct_quant_stream_kernel.
   // Every rank must set the same values.
   size_t rs_quant_min_bytes = 0, rs_quant_bytes = 0, rs_quant_round = 0;
+  // Block-scaled FP8 streamed AllReduce (direct_quant_stream_ar.h).  The opt-in
+  // window in bytes of the whole buffer, max without a cap and 0 = off
+  // (mccsCommSetAllReduceQuantStream; MCCS_AR_QUANT_STREAM_MIN_BYTES /
+  // MCCS_AR_QUANT_STREAM_BYTES at creation), and the INPUT bytes of one round
+  // (0 = the largest, ar_quant_stream_cap, else a multiple of 1024 within it;
+  // MCCS_AR_QUANT_STREAM_ROUND_BYTES): a qualifying AllReduce of min <= bytes <=
+  // max that the two-shot window of ar_quant_* leaves and in which every rank
+  // owns an element of the MCCS_QUANT_SHARE split is held in `direct` (wide =
+  // true) BEFORE the wide limits see it and runs direct_quant_stream_ar_kernel.
+  // Every rank must set the same values.
+  size_t ar_quant_stream_min_bytes = 0, ar_quant_stream_bytes = 0, ar_quant_stream_round = 0;
   // Direct Broadcast and Reduce (direct_rooted.h).  The four opt-in limits in
   // bytes of the whole buffer (mccsCommSetRootedDirect; MCCS_BC_DIRECT_BYTES /
   // MCCS_BC_LL_BYTES / MCCS_RD_DIRECT_BYTES / MCCS_RD_LL_BYTES at creation),
@@ -542,6 +553,13 @@ void ar_quant_prepare(const Comm* c);  // after the limits changed: probes the f
 size_t rs_quant_cap(const Comm* c);
 void rs_quant_read_env(Comm* c);
 void rs_quant_prepare(const Comm* c);  // probes the four streamed quant kernels' co-residency once
+// Block-scaled FP8 streamed AllReduce: the round cap is 2 x min(MCCS_QUANT_PAY(one one-shot slot), MCCS_QUANT_PAY(half
+// a two-shot slot, cut to 16 bytes)) input bytes (0 unless direct_ok).  ar_quant_stream_read_env reads
+// MCCS_AR_QUANT_STREAM_MIN_BYTES / MCCS_AR_QUANT_STREAM_BYTES (kept only where the cap > 0) and
+// MCCS_AR_QUANT_STREAM_ROUND_BYTES (clamped and cut as rs_quant_read_env does).
+size_t ar_quant_stream_cap(const Comm* c);
+void ar_quant_stream_read_env(Comm* c);
+void ar_quant_stream_prepare(const Comm* c);  // probes the four streamed quant AllReduce kernels' co-residency once
 mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_t>& user_streams);
 // ring.hip
 const void* ring_kernel_ptr(int func, int dtype, int op);
@@ -569,6 +587,8 @@ const void* direct_wide_stream_ar_kernel_ptr(int dtype, int op);
 const void* direct_quant_kernel_ptr(int dtype, int op);
 // direct_quant_stream.hip (likewise)
 const void* direct_quant_stream_kernel_ptr(int dtype, int op);
+// direct_quant_stream_ar.hip (likewise)
+const void* direct_quant_stream_ar_kernel_ptr(int dtype, int op);
 hipError_t ring_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_flush_caches(hipStream_t st);
 

@@ -620,6 +620,33 @@ void rs_quant_read_env(Comm* c) {
   rs_quant_prepare(c);
 }
 
+// ---- block-scaled FP8 streamed AllReduce (direct_quant_stream_ar.h) -------------
+// A round scatters through one one-shot slot and gathers through one half of a
+// two-shot in slot, each split into codes and scale bytes: up to min(PAY_O,
+// PAY_H) 2-byte elements, the cap in INPUT bytes.  The buffer itself has no cap.
+size_t ar_quant_stream_cap(const Comm* c) {
+  if (!c->direct_ok) return 0;
+  return 2 * (size_t)std::min(MCCS_QUANT_PAY(c->layout.oneshot_slot),
+                              MCCS_QUANT_PAY((c->layout.direct_slot / 2) & ~(size_t)15));
+}
+
+void ar_quant_stream_read_env(Comm* c) {
+  auto read = [&](const char* name, size_t cap) {
+    const char* v = std::getenv(name);
+    const long long x = v ? std::atoll(v) : 0;
+    return x > 0 ? std::min((size_t)x, cap) : (size_t)0;
+  };
+  const size_t cap = ar_quant_stream_cap(c);
+  c->ar_quant_stream_min_bytes = cap > 0 ? read("MCCS_AR_QUANT_STREAM_MIN_BYTES", SIZE_MAX) : 0;
+  c->ar_quant_stream_bytes = cap > 0 ? read("MCCS_AR_QUANT_STREAM_BYTES", SIZE_MAX) : 0;
+  // the round, as rs_quant_read_env: clamped to the cap, cut to whole units of
+  // 512 elements (1 .. 1023 is the smallest round, not 0 = the largest)
+  const size_t round = read("MCCS_AR_QUANT_STREAM_ROUND_BYTES", cap);
+  c->ar_quant_stream_round = round & ~(size_t)(2 * MCCS_QUANT_UNIT - 1);
+  if (c->ar_quant_stream_round == 0 && round > 0) c->ar_quant_stream_round = 2 * MCCS_QUANT_UNIT;
+  ar_quant_stream_prepare(c);
+}
+
 // The wide ReduceScatter's and Reduce's limits (direct_wide_rs.h): the direct
 // ReduceScatter's caps and conditions, per block / over the whole buffer.
 void rs_wide_read_env(Comm* c) {
@@ -668,6 +695,13 @@ static int wide_mode(const Comm* c, int func, size_t bytes) {
   // the block-scaled FP8 window is decided before the wide limits
   if (c->ar_quant_bytes > 0 && bytes >= c->ar_quant_min_bytes && bytes <= c->ar_quant_bytes && bytes <= ar_quant_cap(c))
     return MCCS_DIRECT_QUANT_TWO_SHOT;
+  // then the streamed FP8 window, at any size, where every rank owns an element
+  // of the MCCS_QUANT_SHARE split (ring_cfg.h: the round-0 hand-off); a count
+  // that fails that falls through to the wide limits
+  if (c->ar_quant_stream_bytes > 0 && bytes >= c->ar_quant_stream_min_bytes && bytes <= c->ar_quant_stream_bytes &&
+      ar_quant_stream_cap(c) > 0 &&
+      (uint64_t)(c->nranks - 1) * MCCS_QUANT_SHARE((uint64_t)(bytes / 2), (uint64_t)c->nranks) < bytes / 2)  // (2-byte elements)
+    return MCCS_DIRECT_QUANT_AR_STREAM;
   if (bytes <= c->ar_wide_ll_bytes && bytes <= rs_ll_cap(c)) return MCCS_DIRECT_WIDE_LL;
   if (bytes <= c->ar_wide_oneshot_bytes && bytes <= rs_direct_cap(c)) return MCCS_DIRECT_WIDE_ONE_SHOT;
   if (bytes <= c->ar_wide_bytes && bytes <= ar_wide_cap(c)) return MCCS_DIRECT_WIDE_TWO_SHOT;
@@ -1147,6 +1181,8 @@ static bool direct_group(std::vector<Comm*>& comms, const std::vector<int>& idx)
         ck->ar_quant_min_bytes != c0->ar_quant_min_bytes || ck->ar_quant_bytes != c0->ar_quant_bytes ||
         ck->rs_quant_min_bytes != c0->rs_quant_min_bytes || ck->rs_quant_bytes != c0->rs_quant_bytes ||
         ck->rs_quant_round != c0->rs_quant_round ||
+        ck->ar_quant_stream_min_bytes != c0->ar_quant_stream_min_bytes ||
+        ck->ar_quant_stream_bytes != c0->ar_quant_stream_bytes || ck->ar_quant_stream_round != c0->ar_quant_stream_round ||
         ck->direct.op_arg != c0->direct.op_arg)  // one scalar for every rank slot (mccsDirectArgs.op_arg)
       return false;
   }
@@ -1525,11 +1561,13 @@ static mccsResult_t build_direct_rooted(std::vector<Comm*>& comms, const std::ve
 // with rs = false the four streamed AllReduce kernels
 // (direct_wide_stream_ar.h), each cached apart again; `quant`: the four
 // block-scaled FP8 AllReduce kernels (direct_quant.h), or with rs = true the
-// four streamed FP8 ReduceScatter kernels (direct_quant_stream.h), cached apart too.
+// four streamed FP8 ReduceScatter kernels (direct_quant_stream.h), or with
+// stream = true the four streamed FP8 AllReduce kernels
+// (direct_quant_stream_ar.h), cached apart too.
 static int coresident_wide_blocks(int device, int* ncu_out, bool rs = false, bool stream = false, bool quant = false) {
   static std::mutex mu;
   static std::map<std::tuple<unsigned, int, int>, std::pair<int, int>> cache;  // (runtime, device, family) -> (blocks, CUs)
-  const auto key = std::make_tuple(rt_generation(), device, quant ? (rs ? 5 : 4) : stream ? (rs ? 2 : 3) : rs ? 1 : 0);
+  const auto key = std::make_tuple(rt_generation(), device, quant ? (rs ? 5 : stream ? 6 : 4) : stream ? (rs ? 2 : 3) : rs ? 1 : 0);
   {
     std::lock_guard<std::mutex> lk(mu);
     auto it = cache.find(key);
@@ -1544,7 +1582,9 @@ static int coresident_wide_blocks(int device, int* ncu_out, bool rs = false, boo
   int best = 1 << 30;
   for (int dt : {(int)mccsFloat16, (int)mccsBfloat16})
     for (int op : {(int)mccsDevSum, (int)mccsDevPreMulSum}) {
-      for (const void* fn : {quant    ? (rs ? direct_quant_stream_kernel_ptr(dt, op) : direct_quant_kernel_ptr(dt, op))
+      for (const void* fn : {quant    ? (rs       ? direct_quant_stream_kernel_ptr(dt, op)
+                                         : stream ? direct_quant_stream_ar_kernel_ptr(dt, op)
+                                                  : direct_quant_kernel_ptr(dt, op))
                              : stream ? (rs ? direct_wide_stream_kernel_ptr(dt, op) : direct_wide_stream_ar_kernel_ptr(dt, op))
                              : rs   ? direct_wide_rs_kernel_ptr(dt, op)
                                     : direct_wide_kernel_ptr(dt, op),
@@ -1588,6 +1628,11 @@ void rs_quant_prepare(const Comm* c) {
   if (c->rs_quant_bytes > 0) (void)coresident_wide_blocks(c->device, &ncu, /*rs=*/true, false, /*quant=*/true);
 }
 
+void ar_quant_stream_prepare(const Comm* c) {
+  int ncu = 0;
+  if (c->ar_quant_stream_bytes > 0) (void)coresident_wide_blocks(c->device, &ncu, false, /*stream=*/true, /*quant=*/true);
+}
+
 void ar_wide_stream_prepare(const Comm* c) {
   int ncu = 0;
   if (c->ar_wide_stream_bytes > 0) (void)coresident_wide_blocks(c->device, &ncu, /*rs=*/false, /*stream=*/true);
@@ -1610,6 +1655,9 @@ void ar_wide_stream_prepare(const Comm* c) {
 // streamed ReduceScatter with a round of whole units: round_elems from the
 // comm's round bytes / 2 (0: MCCS_QUANT_PAY of a one-shot slot), sized from one
 // round's INPUT bytes, so its pieces are whole units as well.
+// The block-scaled FP8 streamed AllReduce (direct_quant_stream_ar.h) is the
+// streamed AllReduce with owned[] cut by MCCS_QUANT_SHARE and a round of whole
+// units within ar_quant_stream_cap, sized from one round's INPUT bytes too.
 static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vector<int>& idx, mccsDirectArgs* da,
                                       unsigned* grid_x) {
   const Comm* c0 = comms[idx[0]];
@@ -1637,6 +1685,7 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
   const bool stream = mode == MCCS_DIRECT_WIDE_RS_STREAM || ar_stream;
   const bool quant = mode == MCCS_DIRECT_QUANT_TWO_SHOT;
   const bool quant_rs = mode == MCCS_DIRECT_QUANT_RS_STREAM;
+  const bool quant_ar = mode == MCCS_DIRECT_QUANT_AR_STREAM;
   if (quant && da->count > MCCS_QUANT_PAY(da->slot_bytes)) return mccsInternalError;  // wide_mode: within ar_quant_cap
   size_t rbytes = nbytes;  // the bytes of one block a data phase moves: the streamed modes', of one round
   if (ar_stream) {
@@ -1644,6 +1693,16 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
     const size_t round = c0->ar_wide_stream_round ? c0->ar_wide_stream_round : cap;
     if (round < 16 || round % 16 || round > cap) return mccsInternalError;  // api.cpp checked it
     const uint64_t q = MCCS_WIDE_SHARE((uint64_t)da->count, (uint64_t)n);
+    if ((uint64_t)(n - 1) * q >= da->count) return mccsInternalError;  // wide_mode: every rank owns an element
+    da->round_elems = (uint32_t)(round / esize);
+    da->rounds = (q + da->round_elems - 1) / da->round_elems;
+    rbytes = std::min((size_t)q * esize, round);
+  } else if (quant_ar) {
+    // a round is whole units of 512 elements within the payloads of a one-shot slot and of half a two-shot slot
+    const size_t cap = ar_quant_stream_cap(c0);
+    const size_t round = c0->ar_quant_stream_round ? c0->ar_quant_stream_round : cap;
+    if (round < 2 * MCCS_QUANT_UNIT || round % (2 * MCCS_QUANT_UNIT) || round > cap) return mccsInternalError;  // api.cpp
+    const uint64_t q = MCCS_QUANT_SHARE((uint64_t)da->count, (uint64_t)n);
     if ((uint64_t)(n - 1) * q >= da->count) return mccsInternalError;  // wide_mode: every rank owns an element
     da->round_elems = (uint32_t)(round / esize);
     da->rounds = (q + da->round_elems - 1) / da->round_elems;
@@ -1671,7 +1730,7 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
     const uint64_t q = MCCS_WIDE_SHARE((uint64_t)da->count, (uint64_t)n);
     for (int t = 0; t < n; ++t) da->owned[t] = (uint64_t)t * q >= da->count ? 0 : std::min(q, da->count - (uint64_t)t * q);
   }
-  if (quant) {
+  if (quant || quant_ar) {
     const uint64_t q = MCCS_QUANT_SHARE((uint64_t)da->count, (uint64_t)n);
     for (int t = 0; t < n; ++t) da->owned[t] = (uint64_t)t * q >= da->count ? 0 : std::min(q, da->count - (uint64_t)t * q);
   }
@@ -1701,11 +1760,11 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
   // whole input (one-shot; a Reduce sender), of the n-1 foreign shares
   // (two-shot) or of the n-1 foreign blocks (ReduceScatter), or (LL) one 8-byte
   // word of phase 1 per thread; capped by co-residency.
-  const size_t scatter = rs || ar_stream ? rbytes * (size_t)(n - 1)
+  const size_t scatter = rs || ar_stream || quant_ar ? rbytes * (size_t)(n - 1)
                          : (oneshot || rd) ? nbytes
                                            : nbytes - nbytes / (size_t)n;
   int ncu = 0;
-  const int cap = coresident_wide_blocks(c0->device, &ncu, rs || rd, stream, quant || quant_rs);
+  const int cap = coresident_wide_blocks(c0->device, &ncu, rs || rd, stream || quant_ar, quant || quant_rs || quant_ar);
   if (ncu <= 0) ncu = cap;
   long g = std::min<long>((long)((scatter + 4095) / 4096), c0->direct_blocks);
   const size_t ll_words = (rs ? (size_t)(n - 1) : 1) * ((nbytes + 7) / 8);
@@ -1725,7 +1784,7 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
     return (uint32_t)(p / esize);
   };
   da->piece = piece(scatter);
-  da->piece2 = piece(rs || ar_stream ? rbytes : oneshot || rd ? nbytes : nbytes / (size_t)n + 1);
+  da->piece2 = piece(rs || ar_stream || quant_ar ? rbytes : oneshot || rd ? nbytes : nbytes / (size_t)n + 1);
   for (size_t k = 0; k < idx.size(); ++k) {
     Comm* ck = comms[idx[k]];
     ck->plan_direct = false;
@@ -1930,6 +1989,7 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
         MCCS_CHECK(build_direct_wide(comms, idx, &da, &grid));
         fn = da.mode == MCCS_DIRECT_QUANT_TWO_SHOT   ? direct_quant_kernel_ptr(dt, op)
              : da.mode == MCCS_DIRECT_QUANT_RS_STREAM ? direct_quant_stream_kernel_ptr(dt, op)
+             : da.mode == MCCS_DIRECT_QUANT_AR_STREAM ? direct_quant_stream_ar_kernel_ptr(dt, op)
              : da.mode == MCCS_DIRECT_WIDE_AR_STREAM ? direct_wide_stream_ar_kernel_ptr(dt, op)
              : da.mode == MCCS_DIRECT_WIDE_RS_STREAM ? direct_wide_stream_kernel_ptr(dt, op)
              : func == mccsFuncReduceScatter     ? direct_wide_rs_kernel_ptr(dt, op)
@@ -2074,7 +2134,8 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
                                      ? MCCS_ALGO_WIDE_ONESHOT
                                  : da.mode == MCCS_DIRECT_WIDE_TWO_SHOT ? MCCS_ALGO_WIDE_DIRECT
                                  : da.mode == MCCS_DIRECT_QUANT_TWO_SHOT ? MCCS_ALGO_QUANT
-                                 : da.mode == MCCS_DIRECT_QUANT_RS_STREAM ? MCCS_ALGO_QUANT_STREAM
+                                 : da.mode == MCCS_DIRECT_QUANT_RS_STREAM || da.mode == MCCS_DIRECT_QUANT_AR_STREAM
+                                     ? MCCS_ALGO_QUANT_STREAM
                                  : da.mode == MCCS_DIRECT_WIDE_RS_STREAM || da.mode == MCCS_DIRECT_WIDE_AR_STREAM
                                      ? MCCS_ALGO_WIDE_STREAM
                                  : da.mode == MCCS_DIRECT_TWO_SHOT ? MCCS_ALGO_DIRECT

@@ -408,7 +408,8 @@ class FakeRuntime final : public DeviceRuntime {
         direct = direct || (fn && (fn == direct_wide_kernel_ptr(dt, op) || fn == direct_wide_rs_kernel_ptr(dt, op) ||
                                    fn == direct_wide_rd_kernel_ptr(dt, op) || fn == direct_wide_stream_kernel_ptr(dt, op) ||
                                    fn == direct_wide_stream_ar_kernel_ptr(dt, op) || fn == direct_quant_kernel_ptr(dt, op) ||
-            fn == direct_quant_stream_kernel_ptr(dt, op)));
+                                   fn == direct_quant_stream_kernel_ptr(dt, op) ||
+                                   fn == direct_quant_stream_ar_kernel_ptr(dt, op)));
     const bool a2all = fn && fn == a2a_ll_kernel_ptr();
     if (fn && args && grid.y >= 1 && grid.y <= MCCS_MULTI_MAX_RANKS) {
       if (a2all) {
@@ -463,6 +464,7 @@ class FakeRuntime final : public DeviceRuntime {
                             : da->mode == MCCS_DIRECT_WIDE_AR_STREAM   ? "wide-ar-stream"
                             : da->mode == MCCS_DIRECT_QUANT_TWO_SHOT   ? "quant-twoshot"
                             : da->mode == MCCS_DIRECT_QUANT_RS_STREAM  ? "quant-rs-stream"
+                            : da->mode == MCCS_DIRECT_QUANT_AR_STREAM  ? "quant-ar-stream"
                                                                   : "twoshot") +
                 " gx=" + std::to_string(grid.x) + " llslot=" + std::to_string(da->ll_slot_bytes) +
                 " piece=" + std::to_string(da->piece) + " piece2=" + std::to_string(da->piece2) +
@@ -476,10 +478,14 @@ class FakeRuntime final : public DeviceRuntime {
         if (rooted_mode) extra += " root=" + std::to_string(da->root);  // a direct Broadcast / Reduce names its root
         // a wide launch names its scalar (hex); a wide AllReduce's share table is owned= above
         // (a block-scaled FP8 AllReduce too, and the payload bytes of a slot)
-        const bool wide_mode = da->mode >= MCCS_DIRECT_WIDE_LL && da->mode <= MCCS_DIRECT_QUANT_RS_STREAM;
+        const bool wide_mode = da->mode >= MCCS_DIRECT_WIDE_LL && da->mode <= MCCS_DIRECT_QUANT_AR_STREAM;
         if (da->mode == MCCS_DIRECT_QUANT_TWO_SHOT) extra += " pay=" + std::to_string(MCCS_QUANT_PAY(da->slot_bytes));
         // (the streamed FP8 ReduceScatter's payload is a one-shot slot's)
         if (da->mode == MCCS_DIRECT_QUANT_RS_STREAM) extra += " pay=" + std::to_string(MCCS_QUANT_PAY(da->oslot_bytes));
+        // (the streamed FP8 AllReduce's is the smaller of a one-shot slot's and half a two-shot slot's)
+        if (da->mode == MCCS_DIRECT_QUANT_AR_STREAM)
+          extra += " pay=" + std::to_string(std::min(MCCS_QUANT_PAY(da->oslot_bytes),
+                                                     MCCS_QUANT_PAY((da->slot_bytes / 2) & ~(uint64_t)15)));
         if (wide_mode) {
           char hex[32];
           std::snprintf(hex, sizeof(hex), " op_arg=%llx", (unsigned long long)da->op_arg);
@@ -487,7 +493,7 @@ class FakeRuntime final : public DeviceRuntime {
         }
         // a streamed ReduceScatter / AllReduce names its rounds and the elements of one
         if (da->mode == MCCS_DIRECT_WIDE_RS_STREAM || da->mode == MCCS_DIRECT_WIDE_AR_STREAM ||
-            da->mode == MCCS_DIRECT_QUANT_RS_STREAM)
+            da->mode == MCCS_DIRECT_QUANT_RS_STREAM || da->mode == MCCS_DIRECT_QUANT_AR_STREAM)
           extra += " rounds=" + std::to_string(da->rounds) + " round=" + std::to_string(da->round_elems);
         if (da->mode == MCCS_DIRECT_RS_ONE_SHOT || da->mode == MCCS_DIRECT_RS_LL || rooted_mode || wide_mode) {
           extra += " slots=";
@@ -611,7 +617,7 @@ class FakeRuntime final : public DeviceRuntime {
         if (fn == direct_wide_kernel_ptr(dt, op) || fn == direct_wide_rs_kernel_ptr(dt, op) ||
             fn == direct_wide_rd_kernel_ptr(dt, op) || fn == direct_wide_stream_kernel_ptr(dt, op) ||
             fn == direct_wide_stream_ar_kernel_ptr(dt, op) || fn == direct_quant_kernel_ptr(dt, op) ||
-            fn == direct_quant_stream_kernel_ptr(dt, op))
+            fn == direct_quant_stream_kernel_ptr(dt, op) || fn == direct_quant_stream_ar_kernel_ptr(dt, op))
           return;
     const mccsMultiLaunchArgs* ma = (const mccsMultiLaunchArgs*)args[0];
     if (ma->inline_works) return;

@@ -534,6 +534,34 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 // same rank sends other ranges.
 // Every wait is direct_wait: it polls the abort flag and the watchdog and
 // returns on either.
+// The block-scaled FP8 streamed AllReduce (direct_quant_stream_ar.h, opt-in:
+// mccsCommSetAllReduceQuantStream; mode MCCS_DIRECT_QUANT_AR_STREAM) is this
+// launch with other bytes inside the buffers, and runs the same round loop
+// (direct_stream_ar_body): the counts stay in ELEMENTS, the lines, the one ACK
+// wait per step, the round-0 hand-off, the closing wait and the state words are
+// the ones above, so the argument holds word for word, with q and owned[] from
+// MCCS_QUANT_SHARE (multiples of 512 elements).  Only the layout differs, and
+// it is one layout for both kinds of buffer, the FP8 AllReduce's split of a
+// two-shot slot (MCCS_QUANT_PAY below): a scatter slot [parity][sender] has
+// PAY_O = MCCS_QUANT_PAY(oslot_bytes) code bytes, a gather buffer (the half
+// [parity] of the in slot [owner], floor16(slot_bytes / 2) bytes) has PAY_H =
+// MCCS_QUANT_PAY(half); the code of round element e lies at byte e, the scale
+// byte of the round's block k at PAY + k.  B is a multiple of 512 of at most
+// min(PAY_O, PAY_H) and pieces are whole units, so a round is a whole number of
+// units on the slot side: a sender writes only bytes of its own scatter slot
+// and only below PAY_O + B / 32 <= oslot_bytes, an owner only bytes of its own
+// half of each peer's in slot [owner] and only below PAY_H + B / 32 <= half (so
+// never into the other parity's half or the next slot), and a reader that saw
+// a round's in-count or out-count reads only the units of len_k, all of which
+// that round's writers wrote, codes and scale row alike (the padding of a tail
+// unit included: it is written as zero codes of either sign, which neither
+// move a block's scale nor are stored to recv).  The round-0 hand-off needs every
+// rank to add something to every owner's line, i.e. owned[n-1] >= 1 under
+// MCCS_QUANT_SHARE: (n-1) q < count, which is 512 times coarser than the 16-bit
+// split's condition; the planner tests it and streams nothing else.  In place:
+// send(k) and copy(k) deal pieces through the one function and split a piece
+// into units alike (unit u to wave u mod waves, lane l its 8 elements), so the
+// lane that stores an element in copy(k) is the one that loaded it in send(k).
 //
 // Block-scaled FP8 AllReduce (direct_quant.h, opt-in: mccsCommSetAllReduceQuant;
 // fp16 and bf16, Sum and PreMulSum) uses the two-shot slots, counts and state
@@ -621,6 +649,8 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 // the slot side), so shares start on multiples of 512 elements.
 // block-scaled FP8 streamed ReduceScatter (direct_quant_stream.h; count = recvcount of any size, rounds x round_elems)
 #define MCCS_DIRECT_QUANT_RS_STREAM 21  // WIDE_RS_STREAM's rounds and lines; the one-shot slots split as above, PAY of oslot_bytes
+// block-scaled FP8 streamed AllReduce (direct_quant_stream_ar.h; count of any size, owned[] the split by MCCS_QUANT_SHARE, rounds x round_elems)
+#define MCCS_DIRECT_QUANT_AR_STREAM 22  // WIDE_AR_STREAM's rounds and lines; scatter slots and gather halves split as above
 #define MCCS_QUANT_UNIT 512
 #define MCCS_QUANT_PAY(slot_bytes) (((uint64_t)(slot_bytes) * 32 / 33) & ~(uint64_t)(MCCS_QUANT_UNIT - 1))
 #define MCCS_QUANT_SHARE(count, n) \
@@ -647,17 +677,17 @@ struct mccsDirectArgs {
   uint64_t timeout_ticks;  // s_memrealtime ticks; 0 = never
   uint32_t nranks, nch, nthr_ref, buff_size;  // the ring walk this launch reproduces
   uint32_t fence_mode;                        // MCCS_FENCE_*
-  uint32_t mode;                              // MCCS_DIRECT_* above (RS: direct_rs_kernel only; RD / BC: direct_rooted.h's kernels only; WIDE: direct_wide_kernel only; WIDE_RS / WIDE_RD: direct_wide_rs.h's kernels only; WIDE_RS_STREAM: direct_wide_stream_kernel only; WIDE_AR_STREAM: direct_wide_stream_ar_kernel only; QUANT: direct_quant_kernel only; QUANT_RS_STREAM: direct_quant_stream_kernel only)
+  uint32_t mode;                              // MCCS_DIRECT_* above (RS: direct_rs_kernel only; RD / BC: direct_rooted.h's kernels only; WIDE: direct_wide_kernel only; WIDE_RS / WIDE_RD: direct_wide_rs.h's kernels only; WIDE_RS_STREAM: direct_wide_stream_kernel only; WIDE_AR_STREAM: direct_wide_stream_ar_kernel only; QUANT: direct_quant_kernel only; QUANT_RS_STREAM: direct_quant_stream_kernel only; QUANT_AR_STREAM: direct_quant_stream_ar_kernel only)
   uint32_t piece;                             // elements per piece of the scatter / gather phases
   uint32_t piece2;                            // elements per piece of the reduction phase
   uint32_t no_guard;                          // 1: skip the launch guard (test hook only)
   uint32_t root;                              // the RD / BC / WIDE_RD modes: the root (one for all rank slots); else 0
   uint64_t guard_order;                       // rank slots by guard address, 4 bits each (launch_guard.h)
-  uint64_t owned[MCCS_DIRECT_MAX_RANKS];      // elements of the walk's chunks each rank owns (wide two-shot, WIDE_AR_STREAM and QUANT: of its share)
+  uint64_t owned[MCCS_DIRECT_MAX_RANKS];      // elements of the walk's chunks each rank owns (wide two-shot, WIDE_AR_STREAM, QUANT and QUANT_AR_STREAM: of its share)
   uint8_t idx2rank[MCCS_MAX_NCHANNELS][MCCS_DIRECT_MAX_RANKS];  // rank at ring index k of channel bid
   uint64_t op_arg;  // the wide modes: the PreMulSum scalar (T in the low bits); else 0 (the fields above keep their place)
-  uint64_t rounds;       // WIDE_RS_STREAM, QUANT_RS_STREAM: K = ceil(count / round_elems) >= 1; WIDE_AR_STREAM: ceil(share / round_elems); else 0
-  uint32_t round_elems;  // the STREAM modes: elements of one round (a multiple of 8, at most one one-shot slot; AR: and half a two-shot slot; QUANT_RS_STREAM: a multiple of 512, at most MCCS_QUANT_PAY(oslot_bytes)); else 0
+  uint64_t rounds;       // WIDE_RS_STREAM, QUANT_RS_STREAM: K = ceil(count / round_elems) >= 1; WIDE_AR_STREAM, QUANT_AR_STREAM: ceil(share / round_elems); else 0
+  uint32_t round_elems;  // the STREAM modes: elements of one round (a multiple of 8, at most one one-shot slot; AR: and half a two-shot slot; QUANT_RS_STREAM: a multiple of 512, at most MCCS_QUANT_PAY(oslot_bytes); QUANT_AR_STREAM: and at most MCCS_QUANT_PAY of half a two-shot slot); else 0
   uint32_t pad4;
 };
 #ifdef __cplusplus

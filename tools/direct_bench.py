@@ -47,6 +47,11 @@ The block-scaled FP8 streamed ReduceScatter (mccsCommSetReduceScatterQuant,
 largest rounds of a 1 MiB slot) at blocks of 1 to 32 MiB, per graph-replayed
 call, beside the ring and the wide streamed kernel of the same size; the three
 alternate region by region.
+  python tools/direct_bench.py --wide --stream --quant --dtype bfloat16 [--n 4 8] [--sizes-kib 4096 16384 65536]
+The block-scaled FP8 streamed AllReduce (mccsCommSetAllReduceQuantStream,
+largest rounds of a 1 MiB one-shot slot and half a 2 MiB two-shot slot) at
+buffers of 4 to 64 MiB, likewise beside the ring and the wide streamed
+AllReduce.
 """
 import argparse
 import json
@@ -557,6 +562,79 @@ def quant_rs_mode(args, torch, C, st, dt, code, es):
                       "calls": args.calls, "graph_calls": per, "regions": args.regions, "rows": rows}), flush=True)
 
 
+def quant_ar_mode(args, torch, C, st, dt, code, es):
+    """--wide --stream --quant: per buffer size (4 to 64 MiB) the ring AllReduce
+    ("ring": where such a buffer goes without an opt-in), the wide streamed
+    kernel ("stream", 16-bit rounds of 1 MiB per share) and the block-scaled FP8
+    streamed kernel ("quant", the largest rounds of the same slots).  Each
+    variant is captured as a graph of --graph-calls calls after an eager
+    warm-up; a region replays it until --calls calls ran, and the regions
+    alternate between the three."""
+    import statistics
+
+    assert es == 2, "--quant times float16 / bfloat16"
+    slot = 2 << 20
+    sizes = args.sizes_kib if args.sizes_kib != DEFAULT_SIZES_KIB else [4096, 16384, 65536]
+    per, rows = args.graph_calls, []
+    for n in args.n:
+        cfg = C.CommConfig(ll_bytes=-1, oneshot_bytes=slot // 2, direct_bytes=slot)
+        sets = {a: C.init_all([0] * n, cfg) for a in ("ring", "stream", "quant")}
+        for c in sets["stream"]:
+            c.set_all_reduce_wide_stream(max(sizes) << 10, 0)
+        for c in sets["quant"]:
+            c.set_all_reduce_quant_stream(max(sizes) << 10, 0, 0)
+        round_q = sets["quant"][0].all_reduce_quant_stream_max() // es
+        want = {"ring": "ring", "stream": "wide-stream", "quant": "quant-stream"}
+        for kib in sizes:
+            nbytes = kib << 10
+            cnt = nbytes // es
+            xs = [torch.randn(cnt, device="cuda").to(dt) for _ in range(n)]
+            ys = [torch.empty(cnt, dtype=dt, device="cuda") for _ in xs]
+            row = {"n": n, "func": "allreduce", "bytes": nbytes, "slot_bytes": slot,
+                   "rounds_stream": -(-((-(-cnt // n) + 7) // 8 * 8) // (slot // 2 // es)),
+                   "rounds_quant": -(-((-(-cnt // n) + 511) // 512 * 512) // round_q)}
+
+            def once(a):
+                with C.group():
+                    for r, c in enumerate(sets[a]):
+                        C.all_reduce(c, xs[r], ys[r], cnt, code, 0, stream=st)
+
+            graphs = {}
+            for a in sets:  # warm-up (every kernel's code object), then one graph of `per` calls per variant
+                for _ in range(3):
+                    once(a)
+                st.synchronize()
+                assert sets[a][0].last_algo() == want[a], (a, sets[a][0].last_algo())
+                graphs[a] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[a], stream=st):
+                    for _ in range(per):
+                        once(a)
+                graphs[a].replay()
+                torch.cuda.synchronize()
+            us = {a: [] for a in sets}
+            for _ in range(args.regions):
+                for a in sets:  # the variants alternate region by region
+                    t0 = time.perf_counter()
+                    for _ in range(max(1, args.calls // per)):
+                        graphs[a].replay()
+                    torch.cuda.synchronize()
+                    us[a].append((time.perf_counter() - t0) / (max(1, args.calls // per) * per) * 1e6)
+            for a in sets:
+                row[a + "_us"] = round(statistics.median(us[a]), 2)
+                row[a + "_min_us"], row[a + "_max_us"] = round(min(us[a]), 2), round(max(us[a]), 2)
+                for c in sets[a]:
+                    c.sync()
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            del graphs, xs, ys
+        torch.cuda.synchronize()
+        for comms in sets.values():
+            for c in comms:
+                c.destroy()
+    print(json.dumps({"tool": "direct_bench", "collective": "allreduce-quant-stream", "dtype": args.dtype, "timed": "graph",
+                      "calls": args.calls, "graph_calls": per, "regions": args.regions, "rows": rows}), flush=True)
+
+
 DEFAULT_SIZES_KIB = [32, 128, 512, 2048, 8192, 32768]
 
 
@@ -594,7 +672,8 @@ def main():
                          "against the ring and a host-issued sequence of slot-sized wide two-shot launches")
     ap.add_argument("--quant", action="store_true",
                     help="with --wide --reduce-scatter --stream: a quant row, the block-scaled FP8 streamed ReduceScatter "
-                         "at 1 to 32 MiB per block, graph-replayed, against the ring and the wide streamed kernel")
+                         "at 1 to 32 MiB per block, graph-replayed, against the ring and the wide streamed kernel; "
+                         "with --wide --stream: the block-scaled FP8 streamed AllReduce at 4 to 64 MiB likewise")
     ap.add_argument("--graph-calls", type=int, default=4, help="--wide --stream: calls captured into each replayed graph")
     ap.add_argument("--regions", type=int, default=5, help="--rooted, --wide: timed regions of --calls calls per variant")
     args = ap.parse_args()
@@ -606,6 +685,9 @@ def main():
     st = side_stream(torch, 0, slot=1)
     if args.wide and args.reduce_scatter and args.stream and args.quant:
         quant_rs_mode(args, torch, C, st, dt, code, es)
+        return
+    if args.wide and args.stream and args.quant:
+        quant_ar_mode(args, torch, C, st, dt, code, es)
         return
     if args.wide and args.reduce_scatter and args.stream:
         wide_stream_mode(args, torch, C, st, dt, code, es)
