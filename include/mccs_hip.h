@@ -810,6 +810,54 @@ mccsResult_t mccsCommAllReduceQuantStreamMax(mccsComm_t comm, size_t *round_cap)
 mccsResult_t mccsCommSetReduceScatterQuant(mccsComm_t comm, size_t min_block_bytes, size_t max_block_bytes,
                                            size_t round_bytes);
 mccsResult_t mccsCommReduceScatterQuantMax(mccsComm_t comm, size_t *round_cap);
+/* The block-scaled FP8 streamed AllGather, for mccsFloat16 and mccsBfloat16 and
+ * a block of ANY size: the other half of quantised sharded training (gradients
+ * go out through mccsCommSetReduceScatterQuant, parameters come back through
+ * this).  Every rank's block crosses the links ONCE, to all n-1 peers at the
+ * same time, in the FP8 AllReduce's wire format (an E4M3FN code per element
+ * plus one E8M0 scale byte per 32 elements, about 8.25 bits per element) instead
+ * of the ring's n-1 serial hops at 16 bits.  IT IS LOSSY ON PURPOSE, so it is a
+ * call of its own: mccsAllGather is byte-typed, stays exactly as it is and
+ * never takes this path.  On N(0,1) bf16 inputs the relative L2 error is 2.7e-2
+ * (QDQ alone; computed on the CPU from the definition).
+ * Definition.  sendcount = c >= 1 elements per rank, 2 <= nranks <= 8; recvbuff
+ * holds nranks * c elements.  A quantisation block is the 32 elements [32k,
+ * 32k + 32) counted from the start of EACH RANK'S block (not of recvbuff),
+ * elements past c counting as +0 and never stored; QDQ as above.  For every
+ * rank and every source r: recv[r * c + i] = T(QDQ(f32(x_r))[i]), one rounding
+ * to nearest even.  THE OWN BLOCK IS QUANTISED TOO: every rank ends with the
+ * same bits, as after the FP8 AllReduce, so ranks do not compute on different
+ * weights.  The bits are a function of the inputs alone, whatever the rings,
+ * the channels, the workgroup count, the round size and the number of rounds.
+ * ONE Inf OR NaN MAKES ITS BLOCK OF 32 NaN ON EVERY RANK.  In place is
+ * supported (sendbuff == recvbuff + rank * c * sizeof(T)); ranks sharing a GPU
+ * are fused into one launch; the call may be captured into a HIP graph (call
+ * mccsCommSetAllGatherQuant once before the first capture: it probes the
+ * kernels' co-residency, which the first launch otherwise does).
+ * mccsCommLastAlgo reports MCCS_ALGO_QUANT_STREAM.  There is no ring fallback
+ * with these bits, so the call is REFUSED, never rerouted, with
+ * mccsInvalidUsage and a diagnosis naming the reason: outside 2..8 ranks; no
+ * one-shot slots in the direct region or no peer atomics (mccsCommDirectEnabled
+ * is 0); a group in which the communicator has a second call, before it or
+ * after it; a dtype other than the two; an unconnected communicator.
+ * sendcount 0 does nothing.
+ * mccsCommAllGatherQuantMax: *round_cap, the largest round in INPUT bytes,
+ * mccsCommReduceScatterQuantMax's value (twice the payload bytes of a one-shot
+ * slot); 0 where the call would be refused.
+ * mccsCommSetAllGatherQuant: round_bytes, the input bytes of one round, 0 =
+ * *round_cap (the default), else a multiple of 1024 (512 elements) of at most
+ * *round_cap; refused as mccsCommSetReduceScatterQuant refuses its round (an
+ * unconnected communicator, no multiple of 1024, above *round_cap:
+ * mccsInvalidArgument; a group open or a call pending: mccsInvalidUsage).
+ * MCCS_AG_QUANT_ROUND_BYTES in the environment sets it at creation (clamped to
+ * *round_cap and cut to a multiple of 1024, at least 1024).  EVERY RANK MUST
+ * SET THE SAME VALUE: ranks that disagree run different rounds of one call and
+ * stall until the watchdog; this is not detected.  The node gate does not cover
+ * this path. */
+mccsResult_t mccsAllGatherQuant(const void *sendbuff, void *recvbuff, size_t sendcount, int dtype, mccsComm_t comm,
+                                hipStream_t stream);
+mccsResult_t mccsCommSetAllGatherQuant(mccsComm_t comm, size_t round_bytes);
+mccsResult_t mccsCommAllGatherQuantMax(mccsComm_t comm, size_t *round_cap);
 /* Send / Recv: grouped point-to-point (torch's batch_isend_irecv; the pieces of
  * a Gather or Scatter).  mccsSend moves count * elem_bytes(dtype) bytes from
  * sendbuff to rank `peer`, mccsRecv receives as many from rank `peer` into
@@ -944,9 +992,9 @@ mccsResult_t mccsCommRing(mccsComm_t comm, int ch, int *order);
  * MCCS_ALGO_WIDE_STREAM: mccsCommSetReduceScatterWideStream,
  * mccsCommSetAllReduceWideStream), or MCCS_ALGO_QUANT, the block-scaled FP8
  * AllReduce (mccsCommSetAllReduceQuant), or MCCS_ALGO_QUANT_STREAM, the
- * block-scaled FP8 streamed ReduceScatter and AllReduce
- * (mccsCommSetReduceScatterQuant, mccsCommSetAllReduceQuantStream) (-1 before
- * the first). */
+ * block-scaled FP8 streamed ReduceScatter, AllReduce and AllGather
+ * (mccsCommSetReduceScatterQuant, mccsCommSetAllReduceQuantStream,
+ * mccsAllGatherQuant) (-1 before the first). */
 #define MCCS_ALGO_RING 0
 #define MCCS_ALGO_DIRECT 1
 #define MCCS_ALGO_ONESHOT 2

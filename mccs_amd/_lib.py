@@ -119,6 +119,9 @@ SIGNATURES: dict[str, tuple] = {
     "mccsCommReduceScatterQuantMax": (_c_int, [_c_void_p, _P(_c_size_t)]),
     "mccsCommSetAllReduceQuantStream": (_c_int, [_c_void_p, _c_size_t, _c_size_t, _c_size_t]),
     "mccsCommAllReduceQuantStreamMax": (_c_int, [_c_void_p, _P(_c_size_t)]),
+    "mccsAllGatherQuant": (_c_int, [_c_void_p, _c_void_p, _c_size_t, _c_int, _c_void_p, _c_void_p]),
+    "mccsCommSetAllGatherQuant": (_c_int, [_c_void_p, _c_size_t]),
+    "mccsCommAllGatherQuantMax": (_c_int, [_c_void_p, _P(_c_size_t)]),
     "mccsCommSetAllReduceWide": (_c_int, [_c_void_p, _c_size_t, _c_size_t, _c_size_t]),
     "mccsCommAllReduceWideMax": (_c_int, [_c_void_p, _P(_c_size_t), _P(_c_size_t), _P(_c_size_t)]),
     "mccsCommSetAllReduceWideStream": (_c_int, [_c_void_p, _c_size_t, _c_size_t]),

@@ -47,6 +47,7 @@ EXTRA_CFLAGS = {
     "direct_quant.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "direct_quant_stream.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "direct_quant_stream_ar.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "direct_quant_ag.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

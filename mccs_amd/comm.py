@@ -189,7 +189,8 @@ class Communicator:
         """"ring", "direct" (two-shot), "oneshot" or "ll", or a wide-accumulate
         variant ("wide-ll", "wide-oneshot", "wide-direct", "wide-stream"), or
         "quant-direct" (the block-scaled FP8 all_reduce) or "quant-stream" (the
-        block-scaled FP8 reduce_scatter and streamed all_reduce): the
+        block-scaled FP8 reduce_scatter, streamed all_reduce and
+        all_gather_quant): the
         algorithm of the latest launch (None before one)."""
         a = _sig().mccsCommLastAlgo(self._h)
         return {0: "ring", 1: "direct", 2: "oneshot", 3: "ll", 4: "wide-ll", 5: "wide-oneshot",
@@ -211,6 +212,10 @@ class Communicator:
 
     def all_gather(self, send_buf, recv_buf, size: int, stream=None) -> None:
         all_gather(self, send_buf, recv_buf, size, stream)
+
+    def all_gather_quant(self, send_buf, recv_buf, send_count: int, data_type=AllReduceDataType.Bfloat16,
+                         stream=None) -> None:
+        all_gather_quant(self, send_buf, recv_buf, send_count, data_type, stream)
 
     def reduce_scatter(self, send_buf, recv_buf, recv_count: int, data_type=AllReduceDataType.Float32,
                        op_type=AllReduceOpType.Sum, stream=None, op_arg: int | None = None) -> None:
@@ -441,6 +446,21 @@ class Communicator:
         _lib.check(_sig().mccsCommAllReduceQuantStreamMax(self._h, ctypes.byref(cap)), "mccsCommAllReduceQuantStreamMax")
         return int(cap.value)
 
+    def set_all_gather_quant(self, round_bytes: int = 0) -> None:
+        """mccsCommSetAllGatherQuant: the input bytes of one round of
+        all_gather_quant (0: the largest, all_gather_quant_max(); else a
+        multiple of 1024 of at most that).  Also probes the kernels'
+        co-residency, so call it once before capturing all_gather_quant into a
+        graph.  Every rank must set the same value."""
+        _lib.check(_sig().mccsCommSetAllGatherQuant(self._h, int(round_bytes)), "mccsCommSetAllGatherQuant")
+
+    def all_gather_quant_max(self) -> int:
+        """mccsCommAllGatherQuantMax: the largest round in input bytes of
+        all_gather_quant (0 where the call would be refused)."""
+        cap = ctypes.c_size_t(0)
+        _lib.check(_sig().mccsCommAllGatherQuantMax(self._h, ctypes.byref(cap)), "mccsCommAllGatherQuantMax")
+        return int(cap.value)
+
     def set_reduce_scatter_quant(self, max_block_bytes: int, min_block_bytes: int = 0, round_bytes: int = 0) -> None:
         """mccsCommSetReduceScatterQuant: opts the communicator in to the
         block-scaled FP8 streamed reduce_scatter (max_block_bytes = 0: off, the
@@ -595,6 +615,25 @@ def all_gather(comm: Communicator, send_buf, recv_buf, size: int, stream=None) -
     """libmccs::all_gather: `size` bytes per rank; recv holds nranks*size bytes."""
     rc = _sig().mccsAllGather(_ptr(send_buf), _ptr(recv_buf), int(size), comm._h, _stream(stream))
     _lib.check(rc, "mccsAllGather")
+
+
+def all_gather_quant(comm: Communicator, send_buf, recv_buf, send_count: int,
+                     data_type=AllReduceDataType.Bfloat16, stream=None) -> None:
+    """mccsAllGatherQuant: `send_count` Float16 / BFloat16 elements per rank;
+    recv holds nranks * send_count.  Every block, the own one included,
+    arrives as T(QDQ(x)): E4M3 codes with one scale byte per 32 elements
+    counted from the start of each rank's block, 8.25 bits per element on the
+    wire, one exchange instead of the ring's n-1 hops; the same bits on every
+    rank, in place or not (send == recv + rank * send_count elements).  LOSSY
+    by design (about 2.7e-2 relative L2 error on Gaussian inputs; one Inf or
+    NaN makes its block of 32 NaN), which is why all_gather never takes this
+    path.  last_algo() == "quant-stream".  Refused (MccsError, invalid usage),
+    never rerouted: outside 2..8 ranks, without one-shot slots or peer
+    atomics, another dtype, or a second call of the communicator in the
+    group.  Stream-ordered."""
+    rc = _sig().mccsAllGatherQuant(_ptr(send_buf), _ptr(recv_buf), int(send_count), int(data_type), comm._h,
+                                   _stream(stream))
+    _lib.check(rc, "mccsAllGatherQuant")
 
 
 def reduce_scatter(comm: Communicator, send_buf, recv_buf, recv_count: int, data_type=AllReduceDataType.Float32,

@@ -1094,6 +1094,83 @@ extern "C" mccsResult_t mccsCommSetAllReduceQuantStream(mccsComm_t comm, size_t 
   return mccsSuccess;
 }
 
+// ---- block-scaled FP8 streamed AllGather (direct_quant_ag.h) --------------------
+extern "C" mccsResult_t mccsCommAllGatherQuantMax(mccsComm_t comm, size_t* round_cap) {
+  err_clear();
+  const Comm* c = (const Comm*)comm;
+  if (!c || !round_cap) MCCS_FAIL(mccsInvalidArgument, "mccsCommAllGatherQuantMax: null communicator or output");
+  *round_cap = c->connected && c->nranks >= 2 && c->nranks <= MCCS_DIRECT_MAX_RANKS ? ag_quant_cap(c) : 0;
+  return mccsSuccess;
+}
+
+extern "C" mccsResult_t mccsCommSetAllGatherQuant(mccsComm_t comm, size_t round_bytes) {
+  err_clear();
+  StepScope st("mccsCommSetAllGatherQuant");
+  Comm* c = (Comm*)comm;
+  if (!c || !c->connected) MCCS_FAIL(mccsInvalidArgument, "the communicator is not connected");
+  if (g_group.depth > 0 || c->plan_pending)
+    MCCS_FAIL(mccsInvalidUsage, "the communicator has a group open or a call pending: set the round between launches");
+  const size_t cap = c->nranks >= 2 && c->nranks <= MCCS_DIRECT_MAX_RANKS ? ag_quant_cap(c) : 0;
+  if (round_bytes % (2 * MCCS_QUANT_UNIT))
+    MCCS_FAIL(mccsInvalidArgument, "round_bytes %zu is not a multiple of 1024 (a round is whole units of 512 elements; "
+              "0 = the largest round of %zu bytes)", round_bytes, cap);
+  if (round_bytes > cap)
+    MCCS_FAIL(mccsInvalidArgument, "round_bytes %zu is above the %zu bytes whose FP8 codes and scale bytes fit a "
+              "one-shot slot%s", round_bytes, cap,
+              cap ? "" : " (no one-shot slots or no peer atomics: the count-based path is closed here)");
+  c->ag_quant_round = round_bytes;
+  ag_quant_prepare(c);
+  return mccsSuccess;
+}
+
+// The explicit lossy AllGather: launch_single's group handling with refusals
+// of its own, because no ring carries its bits.
+extern "C" mccsResult_t mccsAllGatherQuant(const void* sendbuff, void* recvbuff, size_t sendcount, int dtype,
+                                           mccsComm_t comm, hipStream_t stream) {
+  Comm* c = (Comm*)comm;
+  if (g_group.depth == 0) err_clear();
+  mccsResult_t er;
+  {
+    StepScope st("mccsAllGatherQuant");
+    if (!c || !c->connected) return reject_call(mccsInvalidUsage, "the communicator is not connected");
+    if (c->failed) return reject_call(mccsRemoteError, "the communicator failed earlier (watchdog or abort): destroy it");
+    char why[200];
+    if (dtype != mccsFloat16 && dtype != mccsBfloat16) {
+      std::snprintf(why, sizeof(why), "dtype %d is neither mccsFloat16 nor mccsBfloat16 (the FP8 wire format is defined "
+                    "for 16-bit floating point only)", dtype);
+      return reject_call(mccsInvalidUsage, why);
+    }
+    if (c->nranks < 2 || c->nranks > MCCS_DIRECT_MAX_RANKS) {
+      std::snprintf(why, sizeof(why), "%d ranks are outside 2..%d and there is no ring fallback with these bits",
+                    c->nranks, MCCS_DIRECT_MAX_RANKS);
+      return reject_call(mccsInvalidUsage, why);
+    }
+    if (ag_quant_cap(c) == 0)
+      return reject_call(mccsInvalidUsage, "no one-shot slots in the direct region or no peer atomics "
+                         "(mccsCommDirectEnabled is 0): the count-based path is closed here and there is no ring fallback");
+    if (sendcount == 0) return mccsSuccess;
+    if (!sendbuff || !recvbuff) return reject_call(mccsInvalidArgument, "null send or recv buffer");
+    er = plan_enqueue_ag_quant(c, dtype, sendbuff, recvbuff, sendcount);
+  }
+  if (er != mccsSuccess) {
+    // (the refused call joined nothing: an earlier call of the group stays with its group)
+    if (g_group.depth == 0) group_discard();
+    else if (g_group.error == mccsSuccess) g_group.error = er;
+    return er;
+  }
+  if (std::find(g_group.comms.begin(), g_group.comms.end(), c) == g_group.comms.end()) {
+    g_group.comms.push_back(c);
+    g_group.streams.push_back(stream);
+  }
+  if (g_group.depth == 0) {
+    StepScope st("mccsAllGatherQuant launch");
+    const mccsResult_t r = plan_launch_group(g_group.comms, g_group.streams);
+    group_discard();
+    return r;
+  }
+  return mccsSuccess;
+}
+
 // The wide ReduceScatter's (rd = false) and Reduce's (rd = true) two limits.
 static mccsResult_t set_rs_wide(mccsComm_t comm, bool rd, size_t ll_bytes, size_t bytes) {
   err_clear();

@@ -580,6 +580,7 @@ mccsResult_t comm_build_device(Comm* c) {
   ar_quant_read_env(c);       // and the block-scaled FP8 AllReduce's
   rs_quant_read_env(c);       // and the block-scaled FP8 ReduceScatter's
   ar_quant_stream_read_env(c);  // and the block-scaled FP8 streamed AllReduce's
+  ag_quant_read_env(c);         // and the block-scaled FP8 streamed AllGather's round
   {
     std::lock_guard<std::mutex> lk(g_live_mu);
     g_live_fifo_slots[c->d_comm] = c->cfg.fifo_slots;

@@ -381,6 +381,13 @@ struct Comm {
   // true) BEFORE the wide limits see it and runs direct_quant_stream_ar_kernel.
   // Every rank must set the same values.
   size_t ar_quant_stream_min_bytes = 0, ar_quant_stream_bytes = 0, ar_quant_stream_round = 0;
+  // Block-scaled FP8 streamed AllGather (direct_quant_ag.h).  There is no
+  // window: the call is explicit (mccsAllGatherQuant) and held in `direct`
+  // (wide = true) under plan_func kFuncAllGatherQuant; only the INPUT bytes of
+  // one round are kept (mccsCommSetAllGatherQuant; MCCS_AG_QUANT_ROUND_BYTES at
+  // creation; 0 = the largest, ag_quant_cap, else a multiple of 1024 within
+  // it).  It runs direct_quant_ag_kernel.  Every rank must set the same value.
+  size_t ag_quant_round = 0;
   // Direct Broadcast and Reduce (direct_rooted.h).  The four opt-in limits in
   // bytes of the whole buffer (mccsCommSetRootedDirect; MCCS_BC_DIRECT_BYTES /
   // MCCS_BC_LL_BYTES / MCCS_RD_DIRECT_BYTES / MCCS_RD_LL_BYTES at creation),
@@ -560,6 +567,16 @@ void rs_quant_prepare(const Comm* c);  // probes the four streamed quant kernels
 size_t ar_quant_stream_cap(const Comm* c);
 void ar_quant_stream_read_env(Comm* c);
 void ar_quant_stream_prepare(const Comm* c);  // probes the four streamed quant AllReduce kernels' co-residency once
+// Block-scaled FP8 streamed AllGather (mccsAllGatherQuant): the planner's own function code, past every MCCS_FUNC_*
+// of ring_cfg.h and never sent to a kernel or to the ring; the round cap is rs_quant_cap's (the same split of a
+// one-shot slot).  ag_quant_read_env reads MCCS_AG_QUANT_ROUND_BYTES (clamped and cut as rs_quant_read_env does).
+constexpr int kFuncAllGatherQuant = 12;
+size_t ag_quant_cap(const Comm* c);
+void ag_quant_read_env(Comm* c);
+void ag_quant_prepare(const Comm* c);  // probes the two quant AllGather kernels' co-residency once
+// One mccsAllGatherQuant (api.cpp checked dtype, ranks and the cap): held for direct_quant_ag_kernel as the comm's
+// only call of its launch; mccsInvalidUsage where the communicator already has a call pending.
+mccsResult_t plan_enqueue_ag_quant(Comm* c, int dtype, const void* send, void* recv, size_t count);
 mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_t>& user_streams);
 // ring.hip
 const void* ring_kernel_ptr(int func, int dtype, int op);
@@ -589,6 +606,8 @@ const void* direct_quant_kernel_ptr(int dtype, int op);
 const void* direct_quant_stream_kernel_ptr(int dtype, int op);
 // direct_quant_stream_ar.hip (likewise)
 const void* direct_quant_stream_ar_kernel_ptr(int dtype, int op);
+// direct_quant_ag.hip (fp16 / bf16; else null: there is no op)
+const void* direct_quant_ag_kernel_ptr(int dtype);
 hipError_t ring_read_profile(unsigned long long* out, bool reset);
 hipError_t ring_flush_caches(hipStream_t st);
 

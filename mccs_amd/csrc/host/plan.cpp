@@ -484,6 +484,10 @@ static mccsResult_t demote_direct(Comm* c) {
   // (a held Broadcast / Reduce goes back with its root, a held wide PreMulSum with its scalar; every other
   // held call has root 0 and op_arg 0, the defaults)
   c->direct.wide = false;
+  // (a held mccsAllGatherQuant has no ring to go to: the launch is refused)
+  if (c->plan_func == kFuncAllGatherQuant)
+    MCCS_FAIL(mccsInvalidUsage, "mccsAllGatherQuant cannot run as one direct launch here (the ranks sharing the device "
+              "issued different calls, counts or round sizes) and has no ring fallback");
   return ring_enqueue(c, c->plan_func, c->plan_dtype, c->plan_op, c->direct.send, c->direct.recv, c->direct.count,
                       c->direct.root, c->direct.op_arg);
 }
@@ -647,6 +651,43 @@ void ar_quant_stream_read_env(Comm* c) {
   ar_quant_stream_prepare(c);
 }
 
+// ---- block-scaled FP8 streamed AllGather (direct_quant_ag.h) --------------------
+// A round goes through one one-shot slot split as the streamed ReduceScatter
+// splits it, so the round cap is rs_quant_cap's.  There is no window to read:
+// the call is explicit.  The round is clamped and cut as rs_quant_read_env's.
+size_t ag_quant_cap(const Comm* c) { return rs_quant_cap(c); }
+
+void ag_quant_read_env(Comm* c) {
+  const char* v = std::getenv("MCCS_AG_QUANT_ROUND_BYTES");
+  const long long x = v ? std::atoll(v) : 0;
+  const size_t round = x > 0 ? std::min((size_t)x, ag_quant_cap(c)) : (size_t)0;
+  c->ag_quant_round = round & ~(size_t)(2 * MCCS_QUANT_UNIT - 1);
+  if (c->ag_quant_round == 0 && round > 0) c->ag_quant_round = 2 * MCCS_QUANT_UNIT;
+  if (round > 0) ag_quant_prepare(c);  // a communicator that names a round means to call it
+}
+
+mccsResult_t plan_enqueue_ag_quant(Comm* c, int dtype, const void* send, void* recv, size_t count) {
+  // No ring carries these bits, so nothing can be demoted: the call shares its
+  // launch with no other call of its communicator, before it or after it (a
+  // later call of any kind meets plan_func != its own below and in plan_enqueue).
+  if (c->plan_pending || c->plan_calls > 0)
+    MCCS_FAIL(mccsInvalidUsage, "the group holds a second call of this communicator: the quantised AllGather has no "
+              "ring fallback and must be its communicator's only call of the launch");
+  c->plan_calls++;
+  c->plan_direct = true;
+  c->direct.send = send;
+  c->direct.recv = recv;
+  c->direct.count = count;
+  c->direct.root = 0;
+  c->direct.wide = true;
+  c->direct.op_arg = 0;
+  c->plan_pending = true;
+  c->plan_func = kFuncAllGatherQuant;
+  c->plan_dtype = dtype;
+  c->plan_op = mccsDevSum;
+  return mccsSuccess;
+}
+
 // The wide ReduceScatter's and Reduce's limits (direct_wide_rs.h): the direct
 // ReduceScatter's caps and conditions, per block / over the whole buffer.
 void rs_wide_read_env(Comm* c) {
@@ -678,6 +719,8 @@ void rs_wide_read_env(Comm* c) {
 // (ring_cfg.h: the round-0 hand-off).  Every rank sees the same limits and the
 // same call, so every rank decides alike.
 static int wide_mode(const Comm* c, int func, size_t bytes) {
+  // the explicit FP8 AllGather has one mode at every size (api.cpp refused it where the cap is 0)
+  if (func == kFuncAllGatherQuant) return ag_quant_cap(c) > 0 ? MCCS_DIRECT_QUANT_AG_STREAM : -1;
   if (func == mccsFuncReduceScatter || func == mccsFuncReduce) {
     const bool rd = func == mccsFuncReduce;
     // the block-scaled FP8 window of a ReduceScatter is decided before the wide limits, at any block size
@@ -1183,6 +1226,7 @@ static bool direct_group(std::vector<Comm*>& comms, const std::vector<int>& idx)
         ck->rs_quant_round != c0->rs_quant_round ||
         ck->ar_quant_stream_min_bytes != c0->ar_quant_stream_min_bytes ||
         ck->ar_quant_stream_bytes != c0->ar_quant_stream_bytes || ck->ar_quant_stream_round != c0->ar_quant_stream_round ||
+        ck->ag_quant_round != c0->ag_quant_round ||
         ck->direct.op_arg != c0->direct.op_arg)  // one scalar for every rank slot (mccsDirectArgs.op_arg)
       return false;
   }
@@ -1563,11 +1607,14 @@ static mccsResult_t build_direct_rooted(std::vector<Comm*>& comms, const std::ve
 // block-scaled FP8 AllReduce kernels (direct_quant.h), or with rs = true the
 // four streamed FP8 ReduceScatter kernels (direct_quant_stream.h), or with
 // stream = true the four streamed FP8 AllReduce kernels
-// (direct_quant_stream_ar.h), cached apart too.
-static int coresident_wide_blocks(int device, int* ncu_out, bool rs = false, bool stream = false, bool quant = false) {
+// (direct_quant_stream_ar.h), cached apart too; `ag`: the two block-scaled
+// FP8 AllGather kernels (direct_quant_ag.h) and no other, an entry of their own.
+static int coresident_wide_blocks(int device, int* ncu_out, bool rs = false, bool stream = false, bool quant = false,
+                                  bool ag = false) {
   static std::mutex mu;
   static std::map<std::tuple<unsigned, int, int>, std::pair<int, int>> cache;  // (runtime, device, family) -> (blocks, CUs)
-  const auto key = std::make_tuple(rt_generation(), device, quant ? (rs ? 5 : stream ? 6 : 4) : stream ? (rs ? 2 : 3) : rs ? 1 : 0);
+  const auto key = std::make_tuple(rt_generation(), device,
+                                   ag ? 7 : quant ? (rs ? 5 : stream ? 6 : 4) : stream ? (rs ? 2 : 3) : rs ? 1 : 0);
   {
     std::lock_guard<std::mutex> lk(mu);
     auto it = cache.find(key);
@@ -1582,7 +1629,8 @@ static int coresident_wide_blocks(int device, int* ncu_out, bool rs = false, boo
   int best = 1 << 30;
   for (int dt : {(int)mccsFloat16, (int)mccsBfloat16})
     for (int op : {(int)mccsDevSum, (int)mccsDevPreMulSum}) {
-      for (const void* fn : {quant    ? (rs       ? direct_quant_stream_kernel_ptr(dt, op)
+      for (const void* fn : {ag       ? (op == (int)mccsDevSum ? direct_quant_ag_kernel_ptr(dt) : nullptr)
+                             : quant  ? (rs       ? direct_quant_stream_kernel_ptr(dt, op)
                                          : stream ? direct_quant_stream_ar_kernel_ptr(dt, op)
                                                   : direct_quant_kernel_ptr(dt, op))
                              : stream ? (rs ? direct_wide_stream_kernel_ptr(dt, op) : direct_wide_stream_ar_kernel_ptr(dt, op))
@@ -1633,6 +1681,12 @@ void ar_quant_stream_prepare(const Comm* c) {
   if (c->ar_quant_stream_bytes > 0) (void)coresident_wide_blocks(c->device, &ncu, false, /*stream=*/true, /*quant=*/true);
 }
 
+// (no window gates it: mccsCommSetAllGatherQuant and a round in the environment are the opt-in)
+void ag_quant_prepare(const Comm* c) {
+  int ncu = 0;
+  if (ag_quant_cap(c) > 0) (void)coresident_wide_blocks(c->device, &ncu, false, false, false, /*ag=*/true);
+}
+
 void ar_wide_stream_prepare(const Comm* c) {
   int ncu = 0;
   if (c->ar_wide_stream_bytes > 0) (void)coresident_wide_blocks(c->device, &ncu, /*rs=*/false, /*stream=*/true);
@@ -1658,6 +1712,11 @@ void ar_wide_stream_prepare(const Comm* c) {
 // The block-scaled FP8 streamed AllReduce (direct_quant_stream_ar.h) is the
 // streamed AllReduce with owned[] cut by MCCS_QUANT_SHARE and a round of whole
 // units within ar_quant_stream_cap, sized from one round's INPUT bytes too.
+// The block-scaled FP8 streamed AllGather (direct_quant_ag.h; plan_func
+// kFuncAllGatherQuant) has the streamed FP8 ReduceScatter's rounds with count =
+// sendcount; a round's send is ONE pass over the own block, so workgroups and
+// both pieces are sized from one round's INPUT bytes, not n-1 times that, and
+// the workgroup cap comes from its own co-residency entry.
 static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vector<int>& idx, mccsDirectArgs* da,
                                       unsigned* grid_x) {
   const Comm* c0 = comms[idx[0]];
@@ -1686,6 +1745,7 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
   const bool quant = mode == MCCS_DIRECT_QUANT_TWO_SHOT;
   const bool quant_rs = mode == MCCS_DIRECT_QUANT_RS_STREAM;
   const bool quant_ar = mode == MCCS_DIRECT_QUANT_AR_STREAM;
+  const bool quant_ag = mode == MCCS_DIRECT_QUANT_AG_STREAM;
   if (quant && da->count > MCCS_QUANT_PAY(da->slot_bytes)) return mccsInternalError;  // wide_mode: within ar_quant_cap
   size_t rbytes = nbytes;  // the bytes of one block a data phase moves: the streamed modes', of one round
   if (ar_stream) {
@@ -1711,6 +1771,14 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
     // a round is whole units of 512 elements within the payload of one one-shot slot
     const size_t cap = rs_quant_cap(c0);
     const size_t round = c0->rs_quant_round ? c0->rs_quant_round : cap;
+    if (round < 2 * MCCS_QUANT_UNIT || round % (2 * MCCS_QUANT_UNIT) || round > cap) return mccsInternalError;  // api.cpp
+    da->round_elems = (uint32_t)(round / esize);
+    da->rounds = (da->count + da->round_elems - 1) / da->round_elems;
+    rbytes = std::min(nbytes, round);
+  } else if (quant_ag) {
+    // the same round: whole units of 512 elements within the payload of one one-shot slot
+    const size_t cap = ag_quant_cap(c0);
+    const size_t round = c0->ag_quant_round ? c0->ag_quant_round : cap;
     if (round < 2 * MCCS_QUANT_UNIT || round % (2 * MCCS_QUANT_UNIT) || round > cap) return mccsInternalError;  // api.cpp
     da->round_elems = (uint32_t)(round / esize);
     da->rounds = (da->count + da->round_elems - 1) / da->round_elems;
@@ -1760,11 +1828,13 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
   // whole input (one-shot; a Reduce sender), of the n-1 foreign shares
   // (two-shot) or of the n-1 foreign blocks (ReduceScatter), or (LL) one 8-byte
   // word of phase 1 per thread; capped by co-residency.
-  const size_t scatter = rs || ar_stream || quant_ar ? rbytes * (size_t)(n - 1)
+  const size_t scatter = quant_ag                      ? rbytes  // one pass over the own block's round
+                         : rs || ar_stream || quant_ar ? rbytes * (size_t)(n - 1)
                          : (oneshot || rd) ? nbytes
                                            : nbytes - nbytes / (size_t)n;
   int ncu = 0;
-  const int cap = coresident_wide_blocks(c0->device, &ncu, rs || rd, stream || quant_ar, quant || quant_rs || quant_ar);
+  const int cap = coresident_wide_blocks(c0->device, &ncu, rs || rd, stream || quant_ar, quant || quant_rs || quant_ar,
+                                         quant_ag);
   if (ncu <= 0) ncu = cap;
   long g = std::min<long>((long)((scatter + 4095) / 4096), c0->direct_blocks);
   const size_t ll_words = (rs ? (size_t)(n - 1) : 1) * ((nbytes + 7) / 8);
@@ -1774,7 +1844,8 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
   g = std::max<long>(g, 1);
   if (g * (long)idx.size() > cap)
     MCCS_FAIL(mccsInvalidUsage, "wide %s launch of %zu ranks x %ld workgroups exceeds the %d co-resident ones of "
-              "device %d", rs ? "ReduceScatter" : rd ? "Reduce" : "AllReduce", idx.size(), g, cap, c0->device);
+              "device %d", rs ? "ReduceScatter" : rd ? "Reduce" : quant_ag ? "AllGather" : "AllReduce", idx.size(), g, cap,
+              c0->device);
   *grid_x = (unsigned)g;
   // pieces: each phase's bytes over the workgroups, in 4 KiB steps (pieces
   // start on 16-byte packs), 4..64 KiB
@@ -1784,7 +1855,7 @@ static mccsResult_t build_direct_wide(std::vector<Comm*>& comms, const std::vect
     return (uint32_t)(p / esize);
   };
   da->piece = piece(scatter);
-  da->piece2 = piece(rs || ar_stream || quant_ar ? rbytes : oneshot || rd ? nbytes : nbytes / (size_t)n + 1);
+  da->piece2 = piece(rs || ar_stream || quant_ar || quant_ag ? rbytes : oneshot || rd ? nbytes : nbytes / (size_t)n + 1);
   for (size_t k = 0; k < idx.size(); ++k) {
     Comm* ck = comms[idx[k]];
     ck->plan_direct = false;
@@ -1990,6 +2061,7 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
         fn = da.mode == MCCS_DIRECT_QUANT_TWO_SHOT   ? direct_quant_kernel_ptr(dt, op)
              : da.mode == MCCS_DIRECT_QUANT_RS_STREAM ? direct_quant_stream_kernel_ptr(dt, op)
              : da.mode == MCCS_DIRECT_QUANT_AR_STREAM ? direct_quant_stream_ar_kernel_ptr(dt, op)
+             : da.mode == MCCS_DIRECT_QUANT_AG_STREAM ? direct_quant_ag_kernel_ptr(dt)
              : da.mode == MCCS_DIRECT_WIDE_AR_STREAM ? direct_wide_stream_ar_kernel_ptr(dt, op)
              : da.mode == MCCS_DIRECT_WIDE_RS_STREAM ? direct_wide_stream_kernel_ptr(dt, op)
              : func == mccsFuncReduceScatter     ? direct_wide_rs_kernel_ptr(dt, op)
@@ -2134,7 +2206,8 @@ mccsResult_t plan_launch_group(std::vector<Comm*>& comms, std::vector<hipStream_
                                      ? MCCS_ALGO_WIDE_ONESHOT
                                  : da.mode == MCCS_DIRECT_WIDE_TWO_SHOT ? MCCS_ALGO_WIDE_DIRECT
                                  : da.mode == MCCS_DIRECT_QUANT_TWO_SHOT ? MCCS_ALGO_QUANT
-                                 : da.mode == MCCS_DIRECT_QUANT_RS_STREAM || da.mode == MCCS_DIRECT_QUANT_AR_STREAM
+                                 : da.mode == MCCS_DIRECT_QUANT_RS_STREAM || da.mode == MCCS_DIRECT_QUANT_AR_STREAM ||
+                                           da.mode == MCCS_DIRECT_QUANT_AG_STREAM
                                      ? MCCS_ALGO_QUANT_STREAM
                                  : da.mode == MCCS_DIRECT_WIDE_RS_STREAM || da.mode == MCCS_DIRECT_WIDE_AR_STREAM
                                      ? MCCS_ALGO_WIDE_STREAM

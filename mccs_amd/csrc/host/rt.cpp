@@ -409,7 +409,8 @@ class FakeRuntime final : public DeviceRuntime {
                                    fn == direct_wide_rd_kernel_ptr(dt, op) || fn == direct_wide_stream_kernel_ptr(dt, op) ||
                                    fn == direct_wide_stream_ar_kernel_ptr(dt, op) || fn == direct_quant_kernel_ptr(dt, op) ||
                                    fn == direct_quant_stream_kernel_ptr(dt, op) ||
-                                   fn == direct_quant_stream_ar_kernel_ptr(dt, op)));
+                                   fn == direct_quant_stream_ar_kernel_ptr(dt, op) ||
+                                   fn == direct_quant_ag_kernel_ptr(dt)));
     const bool a2all = fn && fn == a2a_ll_kernel_ptr();
     if (fn && args && grid.y >= 1 && grid.y <= MCCS_MULTI_MAX_RANKS) {
       if (a2all) {
@@ -465,6 +466,7 @@ class FakeRuntime final : public DeviceRuntime {
                             : da->mode == MCCS_DIRECT_QUANT_TWO_SHOT   ? "quant-twoshot"
                             : da->mode == MCCS_DIRECT_QUANT_RS_STREAM  ? "quant-rs-stream"
                             : da->mode == MCCS_DIRECT_QUANT_AR_STREAM  ? "quant-ar-stream"
+                            : da->mode == MCCS_DIRECT_QUANT_AG_STREAM  ? "quant-ag-stream"
                                                                   : "twoshot") +
                 " gx=" + std::to_string(grid.x) + " llslot=" + std::to_string(da->ll_slot_bytes) +
                 " piece=" + std::to_string(da->piece) + " piece2=" + std::to_string(da->piece2) +
@@ -478,10 +480,11 @@ class FakeRuntime final : public DeviceRuntime {
         if (rooted_mode) extra += " root=" + std::to_string(da->root);  // a direct Broadcast / Reduce names its root
         // a wide launch names its scalar (hex); a wide AllReduce's share table is owned= above
         // (a block-scaled FP8 AllReduce too, and the payload bytes of a slot)
-        const bool wide_mode = da->mode >= MCCS_DIRECT_WIDE_LL && da->mode <= MCCS_DIRECT_QUANT_AR_STREAM;
+        const bool wide_mode = da->mode >= MCCS_DIRECT_WIDE_LL && da->mode <= MCCS_DIRECT_QUANT_AG_STREAM;
         if (da->mode == MCCS_DIRECT_QUANT_TWO_SHOT) extra += " pay=" + std::to_string(MCCS_QUANT_PAY(da->slot_bytes));
-        // (the streamed FP8 ReduceScatter's payload is a one-shot slot's)
-        if (da->mode == MCCS_DIRECT_QUANT_RS_STREAM) extra += " pay=" + std::to_string(MCCS_QUANT_PAY(da->oslot_bytes));
+        // (the streamed FP8 ReduceScatter's and AllGather's payload is a one-shot slot's)
+        if (da->mode == MCCS_DIRECT_QUANT_RS_STREAM || da->mode == MCCS_DIRECT_QUANT_AG_STREAM)
+          extra += " pay=" + std::to_string(MCCS_QUANT_PAY(da->oslot_bytes));
         // (the streamed FP8 AllReduce's is the smaller of a one-shot slot's and half a two-shot slot's)
         if (da->mode == MCCS_DIRECT_QUANT_AR_STREAM)
           extra += " pay=" + std::to_string(std::min(MCCS_QUANT_PAY(da->oslot_bytes),
@@ -493,7 +496,8 @@ class FakeRuntime final : public DeviceRuntime {
         }
         // a streamed ReduceScatter / AllReduce names its rounds and the elements of one
         if (da->mode == MCCS_DIRECT_WIDE_RS_STREAM || da->mode == MCCS_DIRECT_WIDE_AR_STREAM ||
-            da->mode == MCCS_DIRECT_QUANT_RS_STREAM || da->mode == MCCS_DIRECT_QUANT_AR_STREAM)
+            da->mode == MCCS_DIRECT_QUANT_RS_STREAM || da->mode == MCCS_DIRECT_QUANT_AR_STREAM ||
+            da->mode == MCCS_DIRECT_QUANT_AG_STREAM)
           extra += " rounds=" + std::to_string(da->rounds) + " round=" + std::to_string(da->round_elems);
         if (da->mode == MCCS_DIRECT_RS_ONE_SHOT || da->mode == MCCS_DIRECT_RS_LL || rooted_mode || wide_mode) {
           extra += " slots=";
@@ -617,7 +621,8 @@ class FakeRuntime final : public DeviceRuntime {
         if (fn == direct_wide_kernel_ptr(dt, op) || fn == direct_wide_rs_kernel_ptr(dt, op) ||
             fn == direct_wide_rd_kernel_ptr(dt, op) || fn == direct_wide_stream_kernel_ptr(dt, op) ||
             fn == direct_wide_stream_ar_kernel_ptr(dt, op) || fn == direct_quant_kernel_ptr(dt, op) ||
-            fn == direct_quant_stream_kernel_ptr(dt, op) || fn == direct_quant_stream_ar_kernel_ptr(dt, op))
+            fn == direct_quant_stream_kernel_ptr(dt, op) || fn == direct_quant_stream_ar_kernel_ptr(dt, op) ||
+            fn == direct_quant_ag_kernel_ptr(dt))
           return;
     const mccsMultiLaunchArgs* ma = (const mccsMultiLaunchArgs*)args[0];
     if (ma->inline_works) return;

@@ -444,6 +444,23 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 // bytes of its own slot and only below PAY_O + B / 32 <= oslot_bytes, and a
 // reader that saw the round's count reads only bytes that round's senders
 // wrote (the padding of a tail unit included: it is written as +0 codes).
+// The block-scaled FP8 streamed AllGather (direct_quant_ag.h, the explicit call
+// mccsAllGatherQuant; mode MCCS_DIRECT_QUANT_AG_STREAM) uses these slots, lines,
+// counts, waits and state words with the data moving the other way: sender s
+// writes round k of its OWN block, once quantised, into slot [parity][s] of
+// every peer, and a reader dequantises the n-1 slots of one parity into n-1
+// output blocks.  The no-cycle argument carries over because it never looked at
+// what the bytes are, only at who counts and who reads: every sender still adds
+// the same length len_k to IN_CNT(s) of EVERY peer, after every one of its
+// workgroups drained its stores of the round, so IN_CNT(s) >= E_IN + k B + len_k
+// at t still means all of rounds 0 .. k from s are in t's slots; and a reader
+// still reads exactly the n-1 slots of ONE parity per round and acknowledges
+// rounds 0 .. K-2 once every one of its workgroups has read them, so hazards 1
+// to 3 and the bound of four SEND_DONE / ROUND_DONE words read as above with
+// "copy" for "fold".  The own block never enters a slot: a thread loads its 8
+// elements, and the same thread stores their QDQ to the output, so in place
+// needs no self wait.  The launch leaves LAUNCHES += K, E_IN += count, E_OUT
+// and E_SELF untouched, as the streamed ReduceScatter does.
 //
 // Wide streamed AllReduce (direct_wide_stream_ar.h, opt-in:
 // mccsCommSetAllReduceWideStream; fp16 and bf16, Sum and PreMulSum) runs
@@ -651,6 +668,8 @@ static_assert(sizeof(mccsMultiLaunchArgs) <= 1024, "ring launch arguments must s
 #define MCCS_DIRECT_QUANT_RS_STREAM 21  // WIDE_RS_STREAM's rounds and lines; the one-shot slots split as above, PAY of oslot_bytes
 // block-scaled FP8 streamed AllReduce (direct_quant_stream_ar.h; count of any size, owned[] the split by MCCS_QUANT_SHARE, rounds x round_elems)
 #define MCCS_DIRECT_QUANT_AR_STREAM 22  // WIDE_AR_STREAM's rounds and lines; scatter slots and gather halves split as above
+// block-scaled FP8 streamed AllGather (direct_quant_ag.h; count = sendcount of any size, rounds x round_elems; no op)
+#define MCCS_DIRECT_QUANT_AG_STREAM 23  // QUANT_RS_STREAM's rounds, lines and slot split; every sender's own block to every peer
 #define MCCS_QUANT_UNIT 512
 #define MCCS_QUANT_PAY(slot_bytes) (((uint64_t)(slot_bytes) * 32 / 33) & ~(uint64_t)(MCCS_QUANT_UNIT - 1))
 #define MCCS_QUANT_SHARE(count, n) \
@@ -677,7 +696,7 @@ struct mccsDirectArgs {
   uint64_t timeout_ticks;  // s_memrealtime ticks; 0 = never
   uint32_t nranks, nch, nthr_ref, buff_size;  // the ring walk this launch reproduces
   uint32_t fence_mode;                        // MCCS_FENCE_*
-  uint32_t mode;                              // MCCS_DIRECT_* above (RS: direct_rs_kernel only; RD / BC: direct_rooted.h's kernels only; WIDE: direct_wide_kernel only; WIDE_RS / WIDE_RD: direct_wide_rs.h's kernels only; WIDE_RS_STREAM: direct_wide_stream_kernel only; WIDE_AR_STREAM: direct_wide_stream_ar_kernel only; QUANT: direct_quant_kernel only; QUANT_RS_STREAM: direct_quant_stream_kernel only; QUANT_AR_STREAM: direct_quant_stream_ar_kernel only)
+  uint32_t mode;                              // MCCS_DIRECT_* above (RS: direct_rs_kernel only; RD / BC: direct_rooted.h's kernels only; WIDE: direct_wide_kernel only; WIDE_RS / WIDE_RD: direct_wide_rs.h's kernels only; WIDE_RS_STREAM: direct_wide_stream_kernel only; WIDE_AR_STREAM: direct_wide_stream_ar_kernel only; QUANT: direct_quant_kernel only; QUANT_RS_STREAM: direct_quant_stream_kernel only; QUANT_AR_STREAM: direct_quant_stream_ar_kernel only; QUANT_AG_STREAM: direct_quant_ag_kernel only)
   uint32_t piece;                             // elements per piece of the scatter / gather phases
   uint32_t piece2;                            // elements per piece of the reduction phase
   uint32_t no_guard;                          // 1: skip the launch guard (test hook only)
@@ -686,8 +705,8 @@ struct mccsDirectArgs {
   uint64_t owned[MCCS_DIRECT_MAX_RANKS];      // elements of the walk's chunks each rank owns (wide two-shot, WIDE_AR_STREAM, QUANT and QUANT_AR_STREAM: of its share)
   uint8_t idx2rank[MCCS_MAX_NCHANNELS][MCCS_DIRECT_MAX_RANKS];  // rank at ring index k of channel bid
   uint64_t op_arg;  // the wide modes: the PreMulSum scalar (T in the low bits); else 0 (the fields above keep their place)
-  uint64_t rounds;       // WIDE_RS_STREAM, QUANT_RS_STREAM: K = ceil(count / round_elems) >= 1; WIDE_AR_STREAM, QUANT_AR_STREAM: ceil(share / round_elems); else 0
-  uint32_t round_elems;  // the STREAM modes: elements of one round (a multiple of 8, at most one one-shot slot; AR: and half a two-shot slot; QUANT_RS_STREAM: a multiple of 512, at most MCCS_QUANT_PAY(oslot_bytes); QUANT_AR_STREAM: and at most MCCS_QUANT_PAY of half a two-shot slot); else 0
+  uint64_t rounds;       // WIDE_RS_STREAM, QUANT_RS_STREAM, QUANT_AG_STREAM: K = ceil(count / round_elems) >= 1; WIDE_AR_STREAM, QUANT_AR_STREAM: ceil(share / round_elems); else 0
+  uint32_t round_elems;  // the STREAM modes: elements of one round (a multiple of 8, at most one one-shot slot; AR: and half a two-shot slot; QUANT_RS_STREAM, QUANT_AG_STREAM: a multiple of 512, at most MCCS_QUANT_PAY(oslot_bytes); QUANT_AR_STREAM: and at most MCCS_QUANT_PAY of half a two-shot slot); else 0
   uint32_t pad4;
 };
 #ifdef __cplusplus

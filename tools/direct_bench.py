@@ -52,6 +52,11 @@ The block-scaled FP8 streamed AllReduce (mccsCommSetAllReduceQuantStream,
 largest rounds of a 1 MiB one-shot slot and half a 2 MiB two-shot slot) at
 buffers of 4 to 64 MiB, likewise beside the ring and the wide streamed
 AllReduce.
+  python tools/direct_bench.py --allgather --quant --dtype bfloat16 [--n 4 8] [--sizes-kib 1024 4096 16384 65536]
+The explicit block-scaled FP8 streamed AllGather (mccsAllGatherQuant, largest
+rounds of a 1 MiB slot) at 1 to 64 MiB per rank, per graph-replayed call,
+beside the ring AllGather and, where a rank's bytes fit the slot, the one-shot
+AllGather, at equal input bytes.
 """
 import argparse
 import json
@@ -562,6 +567,80 @@ def quant_rs_mode(args, torch, C, st, dt, code, es):
                       "calls": args.calls, "graph_calls": per, "regions": args.regions, "rows": rows}), flush=True)
 
 
+def quant_ag_mode(args, torch, C, st, dt, code, es):
+    """--allgather --quant: per input size per rank (1 to 64 MiB) the ring
+    AllGather ("ring": where the byte-typed call goes above the one-shot
+    limit), the one-shot AllGather ("oneshot", only where a rank's bytes fit
+    the 1 MiB slot) and the explicit block-scaled FP8 streamed AllGather
+    ("quant", the largest rounds of the same slot), at equal input bytes.
+    Captured, replayed and alternated as quant_rs_mode does."""
+    import statistics
+
+    assert es == 2, "--quant times float16 / bfloat16"
+    slot = 1 << 20
+    sizes = args.sizes_kib if args.sizes_kib != DEFAULT_SIZES_KIB else [1024, 4096, 16384, 65536]
+    per, rows = args.graph_calls, []
+    for n in args.n:
+        sets = {"ring": C.init_all([0] * n, C.CommConfig(ll_bytes=-1, oneshot_bytes=-1, direct_bytes=-1))}
+        for a in ("oneshot", "quant"):
+            sets[a] = C.init_all([0] * n, C.CommConfig(ll_bytes=-1, oneshot_bytes=slot, direct_bytes=-1))
+        for c in sets["quant"]:
+            c.set_all_gather_quant(0)
+        round_q = sets["quant"][0].all_gather_quant_max()
+        want = {"ring": "ring", "oneshot": "oneshot", "quant": "quant-stream"}
+        for kib in sizes:
+            nbytes = kib << 10
+            cnt = nbytes // es
+            xs = [torch.randn(cnt, device="cuda").to(dt) for _ in range(n)]
+            ys = [torch.empty(cnt * n, dtype=dt, device="cuda") for _ in xs]
+            row = {"n": n, "func": "allgather", "bytes_per_rank": nbytes, "slot_bytes": slot,
+                   "rounds_quant": -(-nbytes // round_q)}
+            algos = [a for a in sets if a != "oneshot" or nbytes <= slot]
+
+            def once(a):
+                with C.group():
+                    for r, c in enumerate(sets[a]):
+                        if a == "quant":
+                            C.all_gather_quant(c, xs[r], ys[r], cnt, code, stream=st)
+                        else:
+                            C.all_gather(c, xs[r], ys[r], nbytes, stream=st)
+
+            graphs = {}
+            for a in algos:  # warm-up (every kernel's code object), then one graph of `per` calls per variant
+                for _ in range(3):
+                    once(a)
+                st.synchronize()
+                assert sets[a][0].last_algo() == want[a], (a, sets[a][0].last_algo())
+                graphs[a] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[a], stream=st):
+                    for _ in range(per):
+                        once(a)
+                graphs[a].replay()
+                torch.cuda.synchronize()
+            us = {a: [] for a in algos}
+            for _ in range(args.regions):
+                for a in algos:  # the variants alternate region by region
+                    t0 = time.perf_counter()
+                    for _ in range(max(1, args.calls // per)):
+                        graphs[a].replay()
+                    torch.cuda.synchronize()
+                    us[a].append((time.perf_counter() - t0) / (max(1, args.calls // per) * per) * 1e6)
+            for a in algos:
+                row[a + "_us"] = round(statistics.median(us[a]), 2)
+                row[a + "_min_us"], row[a + "_max_us"] = round(min(us[a]), 2), round(max(us[a]), 2)
+                for c in sets[a]:
+                    c.sync()
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            del graphs, xs, ys
+        torch.cuda.synchronize()
+        for comms in sets.values():
+            for c in comms:
+                c.destroy()
+    print(json.dumps({"tool": "direct_bench", "collective": "allgather-quant-stream", "dtype": args.dtype, "timed": "graph",
+                      "calls": args.calls, "graph_calls": per, "regions": args.regions, "rows": rows}), flush=True)
+
+
 def quant_ar_mode(args, torch, C, st, dt, code, es):
     """--wide --stream --quant: per buffer size (4 to 64 MiB) the ring AllReduce
     ("ring": where such a buffer goes without an opt-in), the wide streamed
@@ -673,7 +752,9 @@ def main():
     ap.add_argument("--quant", action="store_true",
                     help="with --wide --reduce-scatter --stream: a quant row, the block-scaled FP8 streamed ReduceScatter "
                          "at 1 to 32 MiB per block, graph-replayed, against the ring and the wide streamed kernel; "
-                         "with --wide --stream: the block-scaled FP8 streamed AllReduce at 4 to 64 MiB likewise")
+                         "with --wide --stream: the block-scaled FP8 streamed AllReduce at 4 to 64 MiB likewise; with "
+                         "--allgather: the explicit block-scaled FP8 AllGather at 1 to 64 MiB per rank against the ring "
+                         "and, where a rank's bytes fit a slot, the one-shot AllGather")
     ap.add_argument("--graph-calls", type=int, default=4, help="--wide --stream: calls captured into each replayed graph")
     ap.add_argument("--regions", type=int, default=5, help="--rooted, --wide: timed regions of --calls calls per variant")
     args = ap.parse_args()
@@ -683,6 +764,9 @@ def main():
     es = torch.empty(0, dtype=dt).element_size()
     rows = []
     st = side_stream(torch, 0, slot=1)
+    if args.allgather and args.quant:
+        quant_ag_mode(args, torch, C, st, dt, code, es)
+        return
     if args.wide and args.reduce_scatter and args.stream and args.quant:
         quant_rs_mode(args, torch, C, st, dt, code, es)
         return
